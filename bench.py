@@ -163,6 +163,34 @@ def mapper_loss(depth, color, gt_depth, gt_color, stage, w_color=0.2):
     return loss
 
 
+DUMP_BUDGET_BYTES = 64_000_000      # --dump-outputs: all .npy files of one run together
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write each array of `arrays` (name -> tensor) as out_dir/<name>.npy, float64 kept, everything else
+    as float32.  When the whole set is larger than `budget`, the budget is shared out smallest array first, and an array
+    larger than its share is written as a fixed, seeded sample of its rows (a [1,C,D,H,W] feature-grid gradient: voxels of
+    C channels, [V,C]; anything else: entries of its first axis), in ascending row order with the seed taken from the name,
+    so that two runs with the same arguments write the same rows."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: (t.detach().double() if t.dtype == torch.float64 else t.detach().float()) for k, t in arrays.items()}
+    left, todo = budget, sorted(arrays, key=lambda k: arrays[k].numel() * arrays[k].element_size())
+    for i, name in enumerate(todo):
+        t = arrays[name]
+        share = max(left // (len(todo) - i) - 128, 0)              # (128 bytes of .npy header per file)
+        if t.dim() > 0 and t.numel() * t.element_size() > share:
+            rows = t[0].permute(1, 2, 3, 0).reshape(-1, t.shape[1]) if t.dim() == 5 else t.reshape(t.shape[0], -1)
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            keep = torch.randperm(rows.shape[0], generator=g)[:share // (rows.shape[1] * t.element_size())].sort().values
+            print(f"[bench] --dump-outputs: {name} {tuple(t.shape)} written as {keep.numel()} of its {rows.shape[0]} rows",
+                  file=sys.stderr)
+            t = rows[keep.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.nbytes + 128
+
+
 def cpu_baseline(sc, rays, stage, budget_s=20.0):
     """The CPU oracle (a port of the reference's PyTorch-CPU op sequence, pinned to reference goldens) timed on
     this host on the same 1000-ray workload: fwd + loss + backward, bounded to ~budget_s of CPU work."""
@@ -318,9 +346,11 @@ def spawn_ranks(n):
     return subprocess.run(cmd, env=env).returncode
 
 
-def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, want_cpu_baseline, variant=None, grid_layout=None):
+def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, want_cpu_baseline, variant=None, grid_layout=None,
+                 dump_dir=None):
     """Measure one configuration.  scaling 'weak': `rays` per rank (batch = world x rays); 'strong': `rays` per
-    iteration, split over the ranks in contiguous blocks (parallel.shard_range)."""
+    iteration, split over the ranks in contiguous blocks (parallel.shard_range).  dump_dir: rank 0 writes what the last timed
+    step computed there (dump_outputs)."""
     import evennicer_slam_amd as E
     import evennicer_slam_amd.functional as EF
     from evennicer_slam_amd import parallel as PAR
@@ -430,6 +460,14 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
             PAR.global_depth_max(gd, force=force_comm, out=dmax_static)
 
     seed_grad, comm = {}, {'bytes': 0}
+    last = {}           # dump_dir: the outputs of the latest local step, detached (no autograd graph is kept alive by them)
+
+    def outputs():
+        """What a caller of the step receives (render outputs, loss, the leaves' gradients), by reference."""
+        names = {id(grids[E._lib.GRID_NAMES[k]]): E._lib.GRID_NAMES[k] for k in kinds}
+        names.update({id(q): n for n, q in model.named_parameters()})
+        named = [(names[id(t)], t) for t in leaves] + ([] if mapper_grads else [('rays_o', ro), ('rays_d', rd)])
+        return dict({k: v for k, v in last.items() if v is not None}, **{'grad_' + n: t.grad for n, t in named if t.grad is not None})
 
     def local_step():
         # a mapper iteration follows an optimiser step: grids and decoders have changed IN PLACE (same storage, new version
@@ -448,6 +486,9 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
                 loss = E.losses.rgbd_loss(depth, color if stage == 'color' else None, gd, gc, 0.2)
         else:               # the same render and loss with the loss folded into the compositing launches
             loss, depth, var, color = renderer.render_batch_ray_rgbd_loss(grids, model, rd, ro, dev, stage, gd, gc, 0.2)
+        if dump_dir:
+            last.update((k, v.detach() if v is not None else None) for k, v in
+                        (('loss', loss), ('depth', depth), ('var', var), ('color', color)))
         if 'one' not in seed_grad:              # d(loss)/d(loss) = 1, allocated once (backward() would fill one per step)
             seed_grad['one'] = torch.ones_like(loss)
         with EF.engine_on_calling_thread():       # scoped (the library's loops do the same); see `autograd_engine`
@@ -554,6 +595,7 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
     mode = 'eager'
     gstep = None
     phases = None
+    graph_outputs = None
     if args.eager:
         elapsed, loss = env.timed(step, steps)
         eager_elapsed, eager_steps = elapsed, steps
@@ -575,6 +617,8 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
         if gstep is None:
             elapsed, loss = env.timed(step, steps)
         else:
+            if dump_dir:                # the capture's buffers, which every replay rewrites (later eager steps do not)
+                graph_outputs = outputs()
             phases = [0.0, 0.0, 0.0] if os.environ.get('ENSLAM_BENCH_PHASES') == '1' else None
 
             def graph_step():
@@ -614,6 +658,8 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
                     for t in leaves:
                         t.grad = None
             elapsed, loss = env.timed(graph_step if mode == 'hipgraph' else step, steps)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, graph_outputs if mode == 'hipgraph' else outputs())
 
     # where a multi-rank step spends its time (HIP events around the three parts of 20 extra steps, this rank's stream;
     # outside the timed region): what precedes the local step, the local step, the gradient collective with its glue
@@ -1024,6 +1070,10 @@ def main():
     ap.add_argument('--torch-loss', action='store_true', help='compute the mapper loss with torch ops instead of the fused HIP loss')
     ap.add_argument('--separate-loss', action='store_true', help='render_batch_ray, then losses.rgbd_loss as its own launches')
     ap.add_argument('--eager', action='store_true', help='time the plain Python-driven step instead of hipGraph replays')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (loss, depth, var, color, the gradients of '
+                         'every leaf) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed, seeded sample of '
+                         'the rows of the largest arrays when the whole set is larger)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and os.environ.get('ENSLAM_BENCH_FORCE_COMM') != '1':
@@ -1036,7 +1086,8 @@ def main():
     scaling = args.scaling or spec['scaling']
     primary = run_workload(env, args, scene, rays, scaling, args.steps, args.warmup,
                            want_events=not args.no_kernel_events,
-                           want_cpu_baseline=env.rank == 0 and env.world == 1 and not args.no_cpu_baseline, variant=args.variant)
+                           want_cpu_baseline=env.rank == 0 and env.world == 1 and not args.no_cpu_baseline, variant=args.variant,
+                           dump_dir=args.dump_outputs)
     primary["config"]["baseline_config"] = spec['name'] if not customised else "custom"
     if args.config == 2 and not customised and not args.no_secondary and args.stage == 'color':
         s4 = CONFIGS[4]

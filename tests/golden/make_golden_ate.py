@@ -56,6 +56,24 @@ def main():
     out['assoc_matches'] = np.array(m, dtype=np.float64)
     np.savez_compressed(os.path.join(HERE, 'ate_cases.npz'), **out)
     print({k: v.shape for k, v in out.items() if k.endswith('stats')}, len(m), 'matches')
+    checkpoint_case()
+
+
+def checkpoint_case(n=30, seed=3):
+    """tests/golden/ate_checkpoint.npz: the reference's evaluate_ate on the trajectory pair of the checkpoint that
+    tests/test_harness_cpu.py::_write_checkpoint writes (same seed, same float32 arithmetic; the test checks that the
+    checkpoint's translations equal the stored ones before it compares statistics)."""
+    rng = np.random.default_rng(seed)
+    t = np.linspace(0, 4, n)
+    gt = np.stack([np.cos(t), np.sin(0.7 * t), 0.3 * t], 1).astype(np.float32)
+    est = (gt + (0.02 * rng.standard_normal((n, 3))).astype(np.float32)) + np.array([0.3, -0.1, 0.2], dtype=np.float32)
+    first = {i: np.concatenate([gt[i], [0, 0, 0, 1]]) for i in range(n)}
+    second = {i: np.concatenate([est[i], [0, 0, 0, 1]]) for i in range(n)}
+    res = EA.evaluate_ate(first, second, "")
+    keys = sorted(res.keys())
+    np.savez_compressed(os.path.join(HERE, 'ate_checkpoint.npz'), gt_trans=gt, est_trans=est,
+                        stats=np.array([res[k] for k in keys], dtype=np.float64), stat_keys=np.array('\n'.join(keys)))
+    print('checkpoint case:', {k: res[k] for k in keys})
 
 
 if __name__ == '__main__':
