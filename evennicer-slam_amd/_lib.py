@@ -131,6 +131,10 @@ _SIGS = {
     "enslam_activation_floats": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "enslam_grid_handoff_floats": (c_size_t, [c_int32, c_int32, c_int32]),
     "enslam_eval_points": (ctypes.c_int, [c_int32, c_int64, c_void_p, POINTER(Scene), c_int32, c_void_p, c_void_p]),
+    "enslam_marching_cubes_workspace": (ctypes.c_int, [c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "enslam_marching_cubes_count": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
+    "enslam_marching_cubes_emit": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_double, POINTER(c_double),
+                                                  POINTER(c_double), c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "enslam_render_bwd": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(Scene),
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(Grid),
                                          POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,

@@ -1816,3 +1816,31 @@ class _CompositeFn(torch.autograd.Function):
 def composite(raw, z_vals):
     """(depth f64 [N], var f64 [N], rgb f32 [N,3], weights f32 [N,S]) from raw [N,S,4], z_vals [N,S]."""
     return _CompositeFn.apply(raw, z_vals)
+
+
+def marching_cubes(volume, level, origin, spacing):
+    """(verts float64 [V,3], faces int32 [F,3]) of the level set `value = level` of a lattice volume [nx, ny, nz] (z fastest,
+    evaluated as float32) whose point [ix, iy, iz] sits at origin + index * spacing: skimage.measure.marching_cubes as
+    Mesher.py:495-520 calls it, plus its `verts + origin`.  Conventions (vertex order, winding, case table): enslam_hip.h.
+    One host synchronisation: the counts, so the outputs are allocated exactly."""
+    lib = L.lib()
+    _require_hip(volume, "volume")
+    if volume.dim() != 3:
+        raise L.EnslamError(f"marching_cubes wants a [nx, ny, nz] volume (got shape {tuple(volume.shape)})")
+    vol = _f32c(volume)
+    nx, ny, nz = (int(n) for n in vol.shape)
+    dev = vol.device
+    nbytes = ctypes.c_int64()
+    L.check(lib.enslam_marching_cubes_workspace(nx, ny, nz, ctypes.byref(nbytes)), "enslam_marching_cubes_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    L.check(lib.enslam_marching_cubes_count(_ptr(vol), nx, ny, nz, float(level), _ptr(ws), _ptr(counts), _stream()),
+            "enslam_marching_cubes_count")
+    n_verts, n_faces = counts.tolist()
+    verts = torch.empty((n_verts, 3), dtype=torch.float64, device=dev)
+    faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    org = (ctypes.c_double * 3)(*[float(x) for x in origin])
+    spc = (ctypes.c_double * 3)(*[float(x) for x in spacing])
+    L.check(lib.enslam_marching_cubes_emit(_ptr(vol), nx, ny, nz, float(level), org, spc, _ptr(ws), n_verts, n_faces,
+                                           _ptr(verts), _ptr(faces), _stream()), "enslam_marching_cubes_emit")
+    return verts, faces

@@ -21,7 +21,8 @@ the checkpoints are not in the image): decoders and grids are fitted jointly to 
 sequence, the decoders are kept, the grids are re-initialised -- the run itself then optimises grids (and the colour decoder)
 only, as the reference does.
 
-Not here: mesh extraction, visualiser, wandb."""
+Mesh extraction is opt-in: `SLAM.get_mesh` (or `run(mesh_file=...)`) runs `mesher.Mesher.get_mesh` on the run's keyframes and
+poses.  Not here: visualiser, wandb."""
 import os
 import time
 import types
@@ -280,9 +281,10 @@ class SLAM:
         torch.cuda.set_rng_state(gen, dev)
         return float(loss.item()) if loss is not None else None
 
-    def run(self, max_frames=None, tracking_iters=None):
+    def run(self, max_frames=None, tracking_iters=None, mesh_file=None):
         """tracking_iters overrides cfg['tracking']['iters'] (0: poses stay at their constant-speed initialisation -- the
-        baseline an ATE improvement is measured against)."""
+        baseline an ATE improvement is measured against).  mesh_file: write the final mesh there (`get_mesh`); no meshing
+        otherwise."""
         m, t = self.cfg['mapping'], dict(self.cfg['tracking'])
         if tracking_iters is not None:
             t['iters'] = int(tracking_iters)
@@ -318,8 +320,28 @@ class SLAM:
             self.timing['map'] += time.perf_counter() - t1
             self.estimate_c2w_list[idx] = c2w.detach().cpu()
             pre_color = gt_color.float()
+        self.last_idx = n - 1
         ckpt = self.logger.log(n - 1, self.keyframe_dict, self.keyframe_list, selected_keyframes=None)
-        return dict(ckpt=ckpt, frames=n, fps=n / max(self.timing['track'] + self.timing['map'], 1e-9), timing=dict(self.timing))
+        out = dict(ckpt=ckpt, frames=n, fps=n / max(self.timing['track'] + self.timing['map'], 1e-9), timing=dict(self.timing))
+        if mesh_file is not None:
+            out['mesh'] = self.get_mesh(mesh_file)
+        return out
+
+    def get_mesh(self, path, idx=None, color=True, clean_mesh=True, get_mask_use_all_frames=False, **meshing):
+        """Mesh of the current map through `mesher.Mesher` (the reference's Mapper.py:858-876 call), with this run's keyframes
+        and estimated poses; idx defaults to the last processed frame.  cfg['meshing'] (else the reference's defaults,
+        mesher.MESHING_DEFAULTS) and cfg['mapping']['marching_cubes_bound'] (else the scene bound) configure it; keyword
+        arguments override cfg['meshing'] entries.  Returns what Mesher.get_mesh returns."""
+        from .mesher import MESHING_DEFAULTS, Mesher
+        cfg = dict(self.cfg)
+        cfg['meshing'] = dict(MESHING_DEFAULTS, **self.cfg.get('meshing', {}), **meshing)
+        if 'marching_cubes_bound' not in cfg['mapping']:
+            cfg['mapping'] = dict(cfg['mapping'], marching_cubes_bound=(self.bound / self.scale).tolist())
+        mesher = self.mesher = Mesher(cfg, None, self)
+        idx = getattr(self, 'last_idx', 0) if idx is None else idx
+        return mesher.get_mesh(path, self.shared_c, self.shared_decoders, self.keyframe_dict, self.estimate_c2w_list, idx,
+                               device=self.device, color=color, clean_mesh=clean_mesh,
+                               get_mask_use_all_frames=get_mask_use_all_frames)
 
     def evaluate(self, ckpt):
         return evaluate_checkpoint(ckpt, scale=self.scale)

@@ -52,6 +52,41 @@ class BoxRoom:
         hit = (t1 < t2) & (t1 > 0)
         return torch.where(hit & (t1 < t_wall), t1, t_wall)
 
+    def sample_surface(self, n, seed=0):
+        """n points (float64 [n,3]) spread uniformly by area over the surfaces a camera inside the room can see: the room's
+        six walls without the patches the box covers, and the box's faces without those lying on a wall (the ground truth
+        of eval_recon's metrics)."""
+        g = torch.Generator().manual_seed(seed)
+        boxes = [(self.room_lo, self.room_hi)] + ([(self.box_lo, self.box_hi)] if self.box_lo is not None else [])
+        faces = []                                          # (box, axis, side, area)
+        for b, (lo, hi) in enumerate(boxes):
+            ext = hi - lo
+            for a in range(3):
+                for side in (0, 1):
+                    faces.append((b, a, side, float(ext[(a + 1) % 3] * ext[(a + 2) % 3])))
+        area = torch.tensor([f[3] for f in faces], dtype=torch.float64)
+        out, have = [], 0
+        while have < n:
+            m = 2 * (n - have) + 64
+            pick = torch.multinomial(area, m, replacement=True, generator=g)
+            u = torch.rand(m, 3, generator=g, dtype=torch.float64)
+            p = torch.empty(m, 3, dtype=torch.float64)
+            for k, (b, a, side, _) in enumerate(faces):
+                sel = pick == k
+                lo, hi = boxes[b]
+                q = lo + u[sel] * (hi - lo)
+                q[:, a] = hi[a] if side else lo[a]
+                p[sel] = q
+            keep = torch.ones(m, dtype=torch.bool)
+            if self.box_lo is not None:
+                on_box = pick >= 6
+                covered = ((p >= self.box_lo) & (p <= self.box_hi)).all(dim=1)
+                on_wall = ((p == self.room_lo) | (p == self.room_hi)).any(dim=1)
+                keep = torch.where(on_box, ~on_wall, ~covered)
+            out.append(p[keep])
+            have += int(keep.sum())
+        return torch.cat(out)[:n]
+
     def color_at(self, pts):
         p = pts.double()
         dev = p.device

@@ -380,6 +380,24 @@ size_t enslam_grid_handoff_floats(int32_t stage, int32_t n_rays, int32_t n_sampl
 int enslam_eval_points(int32_t stage, int64_t n_points, const double *points, const enslam_scene *scene,
                        int32_t apply_mask, float *raw_out, void *stream);
 
+/* Marching cubes (the skimage.measure.marching_cubes call of Mesher.py:495-520) on a float32 lattice volume
+ * [nx, ny, nz], z fastest: the reference's z.reshape(ny, nx, nz).transpose(1, 0, 2) indexed [ix, iy, iz].
+ * A corner is occupied iff value > level; an edge carries a vertex iff its ends differ; each lattice point owns its
+ * +x, +y and +z edges.
+ *   vertices float64 [V,3]: owner point in linear [ix, iy, iz] order, then axis x < y < z; position
+ *            origin + (index + t) * spacing, t = (level - a) / (b - a), float64
+ *   faces    int32 [F,3]:   cell in linear order, then the case table's order (csrc/mc_tables.hpp, generated by
+ *            tools/gen_mc_tables.py); right-hand normals point from occupied to free.  Deterministic: no atomics.
+ * Two calls on one stream with the same workspace: the count call leaves {V, F} in counts (device int32 [2]); the caller
+ * reads them back, allocates exactly and passes them to the emit call.  Every dimension >= 2, nx*ny*nz <= 512^3
+ * (ENSLAM_EUNSUPPORTED beyond), a finite level, origin_host / spacing_host (host float64 [3]) finite. */
+int enslam_marching_cubes_workspace(int32_t nx, int32_t ny, int32_t nz, int64_t *bytes_host);
+int enslam_marching_cubes_count(const float *volume, int32_t nx, int32_t ny, int32_t nz, double level, void *workspace,
+                                int32_t *counts, void *stream);
+int enslam_marching_cubes_emit(const float *volume, int32_t nx, int32_t ny, int32_t nz, double level,
+                               const double *origin_host, const double *spacing_host, void *workspace, int32_t n_verts,
+                               int32_t n_faces, double *verts, int32_t *faces, void *stream);
+
 /* Hand-derived backward of enslam_render_fwd (replaces autograd of the reference ops).
  *   g_depth float64 [N], g_var float64 [N] or NULL, g_rgb float32 [N,3] or NULL
  *   grad_grids[k].data : voxel-major accumulators (caller-zeroed) or NULL to skip that grid

@@ -1,5 +1,7 @@
 """The run harness on an analytic, view-consistent sequence (synthetic.BoxRoom): ATE of the full schedule against the ATE of
-poses left at their constant-speed initialisation (tracking_iters = 0).  usage: python tools/run_synthetic_slam.py [n_frames]"""
+poses left at their constant-speed initialisation (tracking_iters = 0).  usage: python tools/run_synthetic_slam.py [n_frames]
+[--mesh DIR]: also mesh the tracked run's map (SLAM.get_mesh) into DIR/mesh.ply and report accuracy, completion and completion
+ratio (eval_recon, metres) against the room's analytic surfaces seen by the keyframes."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -15,7 +17,23 @@ DEV = 'cuda:0'
 from evennicer_slam_amd.synthetic import demo_config, write_demo_sequence
 
 
-def run(n=30, verbose=True):
+def mesh_metrics(slam, path, n_gt=200000):
+    """accuracy / completion / completion ratio (5 cm) of SLAM.get_mesh's mesh against BoxRoom.sample_surface points that
+    the keyframes see (the room of synthetic.write_demo_sequence)."""
+    from evennicer_slam_amd import eval_recon as R
+    room = BoxRoom.for_bound(slam.bound, margin=0.12, seed=1)
+    got = slam.get_mesh(path)
+    if got is None:
+        return dict(accuracy=None, completion=None, completion_ratio=0.0, vertices=0, faces=0)
+    verts, faces, _ = got
+    gt = room.sample_surface(n_gt).numpy()
+    seen, _, _ = slam.mesher.point_masks(gt, slam.keyframe_dict, slam.estimate_c2w_list, slam.last_idx, slam.device)
+    gt = gt[seen]
+    return dict(accuracy=R.accuracy(gt, verts), completion=R.completion(gt, verts), completion_ratio=R.completion_ratio(gt, verts),
+                vertices=int(len(verts)), faces=int(len(faces)), gt_points_seen=int(len(gt)), timing=dict(slam.mesher.timing))
+
+
+def run(n=30, verbose=True, mesh_dir=None):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -32,10 +50,19 @@ def run(n=30, verbose=True):
             err = (ck['estimate_c2w_list'][:, :3, 3] - ck['gt_c2w_list'][:, :3, 3]).norm(dim=1)
             out[tag] = dict(ate=ate['absolute_translational_error.rmse'], raw_rmse=float((err ** 2).mean().sqrt()), raw_max=float(err.max()),
                             fps=res['fps'], prefit_loss=fit)
+            if mesh_dir is not None and tag == 'tracked':
+                os.makedirs(mesh_dir, exist_ok=True)
+                out[tag]['mesh'] = mesh_metrics(slam, os.path.join(mesh_dir, 'mesh.ply'))
             if verbose:
                 print(tag, out[tag], flush=True)
     return out
 
 
 if __name__ == '__main__':
-    run(int(sys.argv[1]) if len(sys.argv) > 1 else 30)
+    args = sys.argv[1:]
+    mesh_dir = None
+    if '--mesh' in args:
+        k = args.index('--mesh')
+        mesh_dir = args[k + 1]
+        del args[k:k + 2]
+    run(int(args[0]) if args else 30, mesh_dir=mesh_dir)
