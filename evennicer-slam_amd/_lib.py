@@ -9,6 +9,9 @@ LIB_PATH = os.environ.get("ENSLAM_LIB") or os.path.join(os.path.dirname(os.path.
 STAGE = {'coarse': 0, 'middle': 1, 'fine': 2, 'color': 3}
 MLP_COARSE, MLP_MIDDLE, MLP_FINE, MLP_COLOR = 0, 1, 2, 3
 MLP_NAMES = ('coarse_decoder', 'middle_decoder', 'fine_decoder', 'color_decoder')
+# the iMAP decoder's parameters in the order of the enslam_imap_* entries
+IMAP_PARAM_NAMES = ('embedder._B',) + tuple(f'pts_linears.{i}.{w}' for i in range(4) for w in ('weight', 'bias')) + \
+    ('output_linear.weight', 'output_linear.bias')
 MAX_SMALL_TENSORS = 72      # ENS_ADAM_MAX_TENSORS: dense tensors per adam_tensors / bucket launch
 GRID_NAMES = ('grid_coarse', 'grid_middle', 'grid_fine', 'grid_color')
 # grids / decoders read by each stage (NICE.forward, decoder.py:312-342); fine reads grid_middle twice
@@ -199,6 +202,16 @@ _SIGS = {
     "enslam_ray_points": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(c_double),
                                          c_void_p, c_void_p, c_void_p]),
     "enslam_fourier_sincos": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_imap_packed_floats": (c_size_t, []),
+    "enslam_imap_workspace_floats": (c_size_t, [c_int64]),
+    "enslam_imap_pack": (ctypes.c_int, [POINTER(c_void_p), c_void_p, c_void_p]),
+    "enslam_imap_fwd": (ctypes.c_int, [c_int64, c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
+    "enslam_imap_bwd": (ctypes.c_int, [c_int64, c_void_p, POINTER(c_void_p), c_void_p, POINTER(c_double), c_void_p, c_void_p,
+                                       c_int32, POINTER(c_void_p), c_void_p, c_void_p]),
+    "enslam_composite_density_fwd": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p]),
+    "enslam_composite_density_bwd": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

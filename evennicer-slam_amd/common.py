@@ -84,11 +84,12 @@ def normalize_3d_coordinate(p, bound):
 
 def raw2outputs_nerf_color(raw, z_vals, rays_d, occupancy=False, device='cuda:0'):
     """Alpha compositing of per-sample (r,g,b,occ) -> depth, depth variance, colour, weights
-    (reference: src/common.py:256-297).  Only the occupancy branch -- the one every shipped NICE config
-    selects (configs/nice_slam.yaml:5) -- is built; it runs as one HIP kernel (and one for its backward)."""
-    if not occupancy:
-        raise NotImplementedError("volume-density compositing (occupancy=False) is the iMAP mode, out of scope")
+    (reference: src/common.py:256-297).  Both branches run as one HIP kernel each way: occupancy (the NICE configs,
+    configs/nice_slam.yaml:5) and volume density (occupancy=False, the iMAP configs), whose intervals are scaled by
+    |rays_d| and which passes gradient to rays_d as well."""
     from . import functional as EF
+    if not occupancy:
+        return EF.composite_density(raw, z_vals, rays_d)
     return EF.composite(raw, z_vals)
 
 

@@ -38,21 +38,28 @@ class DenseLayer(nn.Linear):
 
 
 class MLP(nn.Module):
-    """middle / fine / color decoder parameters (decoder.py:110-166); fourier embedding only."""
+    """middle / fine / color decoder parameters (decoder.py:110-166); fourier embedding only.  Two shapes are built: the
+    NICE decoders (hidden 32, 5 blocks, skip at 2, c_dim 32 / 64), which only own parameters, and the iMAP decoder
+    (config.py `nice=False`: c_dim 0, hidden 256, 4 blocks, no skips, colour), which `forward` evaluates through
+    csrc/imap_mlp.hip, differentiably."""
 
     def __init__(self, name='', dim=3, c_dim=128, hidden_size=256, n_blocks=5, leaky=False, sample_mode='bilinear',
                  color=False, skips=[2], grid_len=0.16, pos_embedding_method='fourier', concat_feature=False):
         super().__init__()
         if pos_embedding_method != 'fourier' or leaky or sample_mode != 'bilinear':
-            raise NotImplementedError("only the shipped NICE configuration (fourier / relu / bilinear) is built")
-        if hidden_size != 32 or n_blocks != 5 or list(skips) != [2] or c_dim not in (32, 64):
-            raise NotImplementedError("kernels are specialised for hidden 32, 5 blocks, skip at 2, c_dim 32/64")
+            raise NotImplementedError("only the shipped configurations (fourier / relu / bilinear) are built")
+        self.imap = (c_dim == 0 and hidden_size == 256 and n_blocks == 4 and list(skips) == [] and color
+                     and dim == 3 and not concat_feature)
+        if not self.imap and (hidden_size != 32 or n_blocks != 5 or list(skips) != [2] or c_dim not in (32, 64)):
+            raise NotImplementedError("kernels are specialised for hidden 32, 5 blocks, skip at 2, c_dim 32/64 (NICE) "
+                                      "and for c_dim 0, hidden 256, 4 blocks, no skips, colour (iMAP)")
         self.name, self.color, self.c_dim, self.grid_len = name, color, c_dim, grid_len
         self.concat_feature, self.n_blocks, self.skips = concat_feature, n_blocks, skips
         self.no_grad_feature = False
         self.sample_mode = sample_mode
         embedding_size = 93
-        self.fc_c = nn.ModuleList([nn.Linear(c_dim, hidden_size) for _ in range(n_blocks)])
+        if c_dim != 0:
+            self.fc_c = nn.ModuleList([nn.Linear(c_dim, hidden_size) for _ in range(n_blocks)])
         self.embedder = GaussianFourierFeatureTransform(dim, mapping_size=embedding_size, scale=25)
         self.pts_linears = nn.ModuleList(
             [DenseLayer(embedding_size, hidden_size, activation="relu")] +
@@ -60,6 +67,14 @@ class MLP(nn.Module):
              else DenseLayer(hidden_size + embedding_size, hidden_size, activation="relu")
              for i in range(n_blocks - 1)])
         self.output_linear = DenseLayer(hidden_size, 4 if color else 1, activation="linear")
+
+    def forward(self, p, c_grid=None):
+        """iMAP decoder: raw [N,4] = (r, g, b, sigma) float32 at points p ([1,N,3] or [N,3], world coordinates), with
+        gradient to p and to the parameters (decoder.py:180-203 with c_dim 0).  No bound mask (that is
+        Renderer.eval_points).  The NICE decoders are evaluated through NICE.forward."""
+        if not self.imap:
+            raise NotImplementedError("a NICE sub-decoder is evaluated through NICE.forward(p, c_grid, stage)")
+        return EF.imap_mlp(p.reshape(-1, 3), self)
 
 
 class MLP_no_xyz(nn.Module):
@@ -108,9 +123,10 @@ class NICE(nn.Module):
 
 
 def get_model(cfg, nice=True):
-    """conv_onet/config.py:4-33 factory (NICE only; the iMAP MLP is outside the hot path)."""
+    """conv_onet/config.py:4-33 factory: NICE, or with nice=False the iMAP decoder MLP(c_dim 0, hidden 256, 4 blocks)."""
     if not nice:
-        raise NotImplementedError("iMAP decoder is not part of the accelerated path")
+        return MLP(dim=cfg['data']['dim'], c_dim=0, color=True, hidden_size=256, skips=[], n_blocks=4,
+                   pos_embedding_method=cfg['model']['pos_embedding_method'])
     gl = cfg['grid_len']
     return NICE(dim=cfg['data']['dim'], c_dim=cfg['model']['c_dim'], coarse=cfg['coarse'],
                 coarse_grid_len=gl['coarse'], middle_grid_len=gl['middle'], fine_grid_len=gl['fine'],

@@ -1844,3 +1844,133 @@ def marching_cubes(volume, level, origin, spacing):
     L.check(lib.enslam_marching_cubes_emit(_ptr(vol), nx, ny, nz, float(level), org, spc, _ptr(ws), n_verts, n_faces,
                                            _ptr(verts), _ptr(faces), _stream()), "enslam_marching_cubes_emit")
     return verts, faces
+
+
+# ------------------------------------------------------------------------------------------------
+# iMAP mode (configs/imap.yaml): the 256-wide decoder (csrc/imap_mlp.hip) and density compositing
+# ------------------------------------------------------------------------------------------------
+IMAP_WS_LIMIT_BYTES = 1 << 30     # the backward's workspace per launch; larger point sets run in chunks
+
+
+def imap_params(dec):
+    """the iMAP decoder's 11 parameter tensors in the order of the enslam_imap_* entries (_lib.IMAP_PARAM_NAMES)"""
+    named = dict(dec.named_parameters())
+    return [named[n] for n in L.IMAP_PARAM_NAMES]
+
+
+def imap_chunk_points():
+    """largest point count (a multiple of 64) whose backward workspace stays within IMAP_WS_LIMIT_BYTES"""
+    lib = L.lib()
+    per = lib.enslam_imap_workspace_floats(1 << 16) / float(1 << 16) * 4
+    return max(64, int(IMAP_WS_LIMIT_BYTES / per) // 64 * 64)
+
+
+def _imap_bound(bound, dtype):
+    if bound is None:
+        return None
+    b = bound.detach().cpu() if torch.is_tensor(bound) else torch.as_tensor(bound)
+    b = b.reshape(3, 2)
+    # Renderer.eval_points compares the points with 0-dim float64 bound entries: torch evaluates that in the points'
+    # dtype, so float32 points meet the bound rounded to float32
+    if dtype != torch.float64:
+        b = b.to(dtype)
+    return (ctypes.c_double * 6)(*[float(x) for x in b.double().reshape(-1)])
+
+
+def _imap_pack(ps):
+    lib = L.lib()
+    packed = torch.empty(lib.enslam_imap_packed_floats(), dtype=torch.float32, device=ps[0].device)
+    pv = (ctypes.c_void_p * 11)(*[p.data_ptr() for p in ps])
+    L.check(lib.enslam_imap_pack(pv, _ptr(packed), _stream()), "enslam_imap_pack")
+    return packed
+
+
+class _ImapMlpFn(torch.autograd.Function):
+    """raw [P,4] of the iMAP decoder at points [P,3]; gradient to the points and to all 11 parameters."""
+
+    @staticmethod
+    def forward(ctx, pts, bound6_, *params):
+        lib = L.lib()
+        ps = [_f32c(p) for p in params]
+        x = pts.detach().to(torch.float64).contiguous()
+        P = x.shape[0]
+        packed = _imap_pack(ps)
+        raw = torch.empty((P, 4), dtype=torch.float32, device=pts.device)
+        L.check(lib.enslam_imap_fwd(P, _ptr(x), _ptr(packed), bound6_, _ptr(raw), _stream()), "enslam_imap_fwd")
+        ctx.keep = (x, packed, ps, bound6_, pts.dtype)
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        lib = L.lib()
+        x, packed, ps, bound6_, pdtype = ctx.keep
+        P, dev = x.shape[0], x.device
+        g = g_raw.detach().float().contiguous()
+        grads = [torch.empty_like(p) for p in ps]
+        d_pts = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        chunk = min(max(P, 1), imap_chunk_points())
+        ws = torch.empty(lib.enslam_imap_workspace_floats(chunk), dtype=torch.float32, device=dev)
+        pv = (ctypes.c_void_p * 11)(*[p.data_ptr() for p in ps])
+        gv = (ctypes.c_void_p * 11)(*[t.data_ptr() for t in grads])
+        for i, c0 in enumerate(range(0, max(P, 1), chunk)):
+            n = min(chunk, P - c0)
+            L.check(lib.enslam_imap_bwd(n, _ptr(x[c0:]) if n > 0 else None, pv, _ptr(packed), bound6_,
+                                        _ptr(g[c0:]) if n > 0 else None, _ptr(ws), int(i > 0), gv,
+                                        _ptr(d_pts[c0:]) if n > 0 else None, _stream()), "enslam_imap_bwd")
+        return (d_pts.to(pdtype), None) + tuple(grads)
+
+
+def imap_mlp(p, dec, bound=None):
+    """raw [P,4] float32 of the iMAP decoder `dec` at points p [P,3] (float32 or float64; evaluated as float32 like the
+    reference's p.float()).  With `bound`, points not strictly inside get sigma = 100 (Renderer.eval_points).
+    Differentiable in p and in the decoder's parameters."""
+    _require_hip(p, "points")
+    ps = imap_params(dec)
+    for t in ps:
+        _require_hip(t, "decoder parameters")
+    return _ImapMlpFn.apply(p.reshape(-1, 3), _imap_bound(bound, p.dtype), *ps)
+
+
+class _CompositeDensityFn(torch.autograd.Function):
+    """raw2outputs_nerf_color with occupancy=False as one HIP kernel each way; gradient to `raw` and `rays_d`."""
+
+    @staticmethod
+    def forward(ctx, raw, z_vals, rays_d):
+        lib = L.lib()
+        _require_hip(raw, "raw")
+        N, S = z_vals.shape
+        if S > 64:
+            raise L.EnslamError("composite kernels handle at most 64 samples per ray")
+        r = _f32c(raw)
+        z = z_vals.detach().contiguous().double()
+        d = _f32c(rays_d)
+        dev = raw.device
+        depth = torch.empty(N, dtype=torch.float64, device=dev)
+        var = torch.empty(N, dtype=torch.float64, device=dev)
+        rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        w = torch.empty((N, S), dtype=torch.float32, device=dev)
+        L.check(lib.enslam_composite_density_fwd(N, S, _ptr(r), _ptr(z), _ptr(d), _ptr(depth), _ptr(var), _ptr(rgb), _ptr(w),
+                                                 _stream()), "enslam_composite_density_fwd")
+        ctx.keep = (r, z, d, depth, rays_d.dtype)
+        ctx.mark_non_differentiable(w)
+        return depth, var, rgb, w
+
+    @staticmethod
+    def backward(ctx, g_depth, g_var, g_rgb, _gw):
+        lib = L.lib()
+        r, z, d, depth, ddtype = ctx.keep
+        N, S = z.shape
+        gD = g_depth.detach().double().contiguous() if g_depth is not None else None
+        gV = g_var.detach().double().contiguous() if g_var is not None else None
+        gC = g_rgb.detach().float().contiguous() if g_rgb is not None else None
+        d_raw = torch.empty((N, S, 4), dtype=torch.float32, device=r.device)
+        d_rd = torch.empty((N, 3), dtype=torch.float32, device=r.device)
+        L.check(lib.enslam_composite_density_bwd(N, S, _ptr(r), _ptr(z), _ptr(d), _ptr(depth), _ptr(gD), _ptr(gV), _ptr(gC),
+                                                 _ptr(d_raw), _ptr(d_rd), _stream()), "enslam_composite_density_bwd")
+        return d_raw, None, d_rd.to(ddtype)
+
+
+def composite_density(raw, z_vals, rays_d):
+    """(depth f64 [N], var f64 [N], rgb f32 [N,3], weights f32 [N,S]) of raw [N,S,4] (sigma = volume density), z_vals
+    [N,S], rays_d [N,3]: raw2outputs_nerf_color(occupancy=False)."""
+    return _CompositeDensityFn.apply(raw, z_vals, rays_d)

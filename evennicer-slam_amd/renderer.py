@@ -23,9 +23,11 @@ class Renderer(object):
         self.nice = slam.nice
         self.bound = slam.bound
         self.H, self.W, self.fx, self.fy, self.cx, self.cy = slam.H, slam.W, slam.fx, slam.fy, slam.cx, slam.cy
-        if not self.nice or not self.occupancy:
-            raise NotImplementedError("the HIP path implements the NICE / occupancy configuration "
-                                      "(configs/nice_slam.yaml: occupancy True); iMAP mode is out of scope")
+        # two configurations are served: NICE with occupancy (configs/nice_slam.yaml) and iMAP with volume density
+        # (configs/imap.yaml: slam.nice False, occupancy False), the latter through csrc/imap_mlp.hip
+        if self.nice != self.occupancy:
+            raise NotImplementedError("the HIP path implements NICE with occupancy (configs/nice_slam.yaml) and iMAP with "
+                                      "volume density (configs/imap.yaml); this mix of slam.nice and occupancy is not built")
         self._tvals = {}
         # (PyTorch's autograd threading is left alone here: the loops of this package scope the single-thread engine around
         # their own backward calls -- functional.engine_on_calling_thread -- and a caller can do the same.)
@@ -50,7 +52,10 @@ class Renderer(object):
 
     # ------------------------------------------------------------------ API
     def eval_points(self, p, decoders, c=None, stage='color', device='cuda:0'):
-        """occupancy (and colour) of points p [N,3]; out-of-bound points get occ = 100."""
+        """occupancy (and colour) of points p [N,3]; out-of-bound points get occ = 100.  iMAP: differentiable."""
+        if not self.nice:
+            EF._require_hip(p, "points")
+            return torch.cat([EF.imap_mlp(pi, decoders, bound=self.bound) for pi in torch.split(p, self.points_batch_size)], 0)
         rets = []
         for pi in torch.split(p, self.points_batch_size):
             rets.append(EF.eval_points(pi, decoders, c, stage, self.bound, apply_mask=True,
@@ -59,7 +64,51 @@ class Renderer(object):
 
     def render_batch_ray(self, c, decoders, rays_d, rays_o, device, stage, gt_depth=None):
         """(depth f64 [N], uncertainty f64 [N], color f32 [N,3]) -- note rays_d comes before rays_o."""
+        if not self.nice:
+            return self._render_imap(decoders, rays_d, rays_o, stage, gt_depth)
         return self._render(c, decoders, rays_d, rays_o, device, stage, gt_depth, None)
+
+    def _render_imap(self, decoders, rays_d, rays_o, stage, gt_depth):
+        """`render_batch_ray` in iMAP mode (Renderer.py:83-198 with slam.nice False, occupancy False): the NICE sampler
+        (enslam_sample_rays), the points o + d z formed as the reference forms them (float64, so that autograd takes their
+        gradient to rays_o / rays_d), the decoder at every point (csrc/imap_mlp.hip, bound mask inside) and density
+        compositing (enslam_composite_density_*).  With N_importance > 0 the first pass runs without gradient, as in the
+        reference, whose new distances are detached and whose returned outputs are the second pass's."""
+        from .common import sample_pdf
+        EF._require_hip(rays_o, "rays")
+        if stage == 'coarse':
+            gt_depth = None
+        N, dev = rays_o.shape[0], rays_o.device
+        if gt_depth is not None:
+            gt_depth = gt_depth.reshape(-1)
+            if N == 0:
+                raise RuntimeError("render_batch_ray: empty ray batch with gt_depth (the reference's "
+                                   "torch.max over an empty tensor raises here too)")
+        if N == 0:
+            z = rays_o.new_zeros((0,))
+            return z.double(), z.double(), rays_o.new_zeros((0, 3))
+        n_surf = self.N_surface if gt_depth is not None else 0
+        S = self.N_samples + n_surf + self.N_importance
+        if S > 64:
+            raise NotImplementedError(f"N_samples + N_importance + N_surface = {S}: at most 64 samples per ray")
+
+        def one_pass(z):
+            pts = (rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]).reshape(-1, 3)
+            raw = self.eval_points(pts, decoders).reshape(N, z.shape[1], 4)
+            return EF.composite_density(raw, z, rays_d)
+
+        with torch.no_grad():
+            t_rand = torch.rand((N, self.N_samples), device=dev) if self.perturb > 0. else None
+            z = EF.sample_rays(rays_o, rays_d, gt_depth, self.bound, self.N_samples, n_surf, self.lindisp, t_rand,
+                               depth_max=self.depth_max_override if gt_depth is not None else None)
+        if self.N_importance > 0:
+            with torch.no_grad():
+                _, _, _, weights = one_pass(z)
+                z_mid = .5 * (z[..., 1:] + z[..., :-1])
+                z_samples = sample_pdf(z_mid, weights[..., 1:-1], self.N_importance, det=(self.perturb == 0.), device=dev)
+                z, _ = torch.sort(torch.cat([z, z_samples.to(z.dtype)], -1), -1)
+        depth, var, color, _ = one_pass(z)
+        return depth, var, color
 
     def render_batch_ray_rgbd_loss(self, c, decoders, rays_d, rays_o, device, stage, gt_depth, gt_color, w_color=0.2):
         """`render_batch_ray` and the mapper's loss on its outputs (Mapper.py:548-562:
@@ -67,6 +116,9 @@ class Renderer(object):
         into the compositing launches, forward and backward.  Returns (loss f64 scalar, depth, uncertainty, color); only
         the loss carries gradient.  Same numbers as `losses.rgbd_loss(*render_batch_ray(...))` up to the summation
         order of the loss value."""
+        if not self.nice:
+            raise NotImplementedError("render_batch_ray_rgbd_loss is not built for iMAP renderers: use render_batch_ray + "
+                                      "losses.rgbd_loss (and regulation)")
         if gt_depth is None or stage == 'coarse':
             raise ValueError("render_batch_ray_rgbd_loss needs gt_depth and a depth-guided stage (middle, fine, color)")
         gd = gt_depth.detach().contiguous().float().reshape(-1)
@@ -82,7 +134,7 @@ class Renderer(object):
     def tracker_loss_ok(self, n_rays, gt_depth):
         """whether render_batch_ray_tracker_loss serves this batch (else: render_batch_ray + losses.tracker_loss)"""
         S = self.N_samples + self.N_surface
-        return (gt_depth is not None and 0 < n_rays <= min(self.FUSED_LOSS_MAX_RAYS, L.lib().enslam_tracker_tail_max_rays())
+        return (self.nice and gt_depth is not None and 0 < n_rays <= min(self.FUSED_LOSS_MAX_RAYS, L.lib().enslam_tracker_tail_max_rays())
                 and self.N_importance == 0 and S % 16 == 0 and S <= 64)
 
     def render_batch_ray_tracker_loss(self, c, decoders, rays_d, rays_o, device, stage, gt_depth, gt_color, w_color=0.5, inside=None,
@@ -95,6 +147,9 @@ class Renderer(object):
             loss = tmp[keep & (gt_depth > 0)].sum() + w_color * |gt_color - color|[keep & (gt_depth > 0)].sum()   (use_color)
         Returns (loss f64 scalar, depth, uncertainty, color); only the loss carries gradient.  Batches of up to 4096 rays, colour
         / fine / middle stage (`tracker_loss_ok`)."""
+        if not self.nice:
+            raise NotImplementedError("render_batch_ray_tracker_loss is not built for iMAP renderers: use render_batch_ray "
+                                      "+ losses.tracker_loss")
         if stage == 'coarse' or not self.tracker_loss_ok(rays_o.shape[0], gt_depth):
             raise ValueError("render_batch_ray_tracker_loss: batch not served (see tracker_loss_ok); use render_batch_ray + losses.tracker_loss")
         gd = gt_depth.detach().contiguous().float().reshape(-1)
@@ -251,5 +306,24 @@ class Renderer(object):
         return depth.reshape(new_H, new_W), var.reshape(new_H, new_W), color.reshape(new_H, new_W, 3)
 
     def regulation(self, c, decoders, rays_d, rays_o, gt_depth, device, stage='color'):
-        raise NotImplementedError("Renderer.regulation is the iMAP (occupancy=False) free-space regulariser "
-                                  "(Renderer.py:322-360); not part of the NICE hot path")
+        """iMAP's free-space term (Renderer.py:322-360): sigma [N * N_samples] of the decoder at N_samples stratified
+        distances in [0, 0.85 gt_depth] of every ray, differentiable (Mapper.py:565-570 adds 0.0005 sum |sigma|).  The
+        stratification's torch.rand draw is on the rays' device, from the caller's generator."""
+        if self.nice:
+            raise NotImplementedError("Renderer.regulation is the iMAP (occupancy=False) free-space regulariser "
+                                      "(Renderer.py:322-360); a NICE renderer has no use for it")
+        EF._require_hip(rays_o, "rays")
+        t_rand = torch.rand((rays_o.shape[0], self.N_samples), device=rays_o.device)
+        return self._regulation(decoders, rays_d, rays_o, gt_depth, t_rand)
+
+    def _regulation(self, decoders, rays_d, rays_o, gt_depth, t_rand):
+        """`regulation` with its uniform draw given ([N, N_samples])."""
+        gt = gt_depth.reshape(-1, 1).repeat(1, self.N_samples)
+        t_vals = torch.linspace(0., 1., steps=self.N_samples, device=gt.device)
+        z = 0.0 * (1. - t_vals) + (gt * 0.85) * t_vals
+        mids = .5 * (z[..., 1:] + z[..., :-1])
+        upper = torch.cat([mids, z[..., -1:]], -1)
+        lower = torch.cat([z[..., :1], mids], -1)
+        z = lower + (upper - lower) * t_rand.to(z.dtype)
+        pts = (rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]).reshape(-1, 3)
+        return self.eval_points(pts, decoders)[:, -1]

@@ -570,6 +570,36 @@ int enslam_plan_backward(const enslam_step_plan *plan, const enslam_step_layout 
                          const float *const *grid_values, const double *g_depth, const double *g_var, const float *g_rgb,
                          const double *g_loss, void *stream);
 
+/* iMAP mode (configs/imap.yaml).  Decoder: src/conv_onet/models/decoder.py:91-203 with c_dim 0, hidden 256, 4 blocks, no
+ * skips, colour output, fourier embedding; float32 throughout (f32-input MFMA).  Its 11 parameter tensors, float32
+ * contiguous, in this order everywhere below (params / grads):
+ *   embedder._B [3,93], pts_linears.{0..3}.{weight,bias} ([256,93] [256] then [256,256] [256] x 3),
+ *   output_linear.{weight,bias} ([4,256] [4]).
+ * enslam_imap_pack writes the forward's weight image (enslam_imap_packed_floats floats) from them; repack after every
+ * parameter change.  enslam_imap_fwd: points float64 [P,3] (cast to float32 like the reference's p.float()) -> raw
+ * float32 [P,4] = (r, g, b, sigma); bound_host (host float64 [3][2]) or NULL: points not strictly inside get sigma = 100
+ * (Renderer.eval_points).  enslam_imap_bwd recomputes the forward into the workspace (enslam_imap_workspace_floats(P)
+ * floats, device) and writes d_points float32 [P,3] and the 11 parameter gradients (accumulate != 0: added to what grads
+ * hold).  The parameter gradients are per-slice partials summed in a fixed order: deterministic, no atomics. */
+size_t enslam_imap_packed_floats(void);
+size_t enslam_imap_workspace_floats(int64_t n_points);
+int enslam_imap_pack(const float *const *params, float *packed, void *stream);
+int enslam_imap_fwd(int64_t n_points, const double *points, const float *packed, const double *bound_host, float *raw,
+                    void *stream);
+int enslam_imap_bwd(int64_t n_points, const double *points, const float *const *params, const float *packed,
+                    const double *bound_host, const float *d_raw, float *workspace, int32_t accumulate, float *const *grads,
+                    float *d_points, void *stream);
+
+/* raw2outputs_nerf_color (common.py:256-297, occupancy=False: volume density): raw float32 [N,S,4], z_vals float64 [N,S],
+ * rays_d float32 [N,3] (dists are scaled by |rays_d|) -> depth/var float64 [N], rgb float32 [N,3], weights float32 [N,S]
+ * (may be NULL).  The backward also returns d_rays_d float32 [N,3] (may be NULL), the gradient through |rays_d|; g_depth /
+ * g_var / g_rgb may each be NULL.  1 <= S <= 64. */
+int enslam_composite_density_fwd(int32_t n_rays, int32_t n_samples, const float *raw, const double *z_vals,
+                                 const float *rays_d, double *depth, double *var, float *rgb, float *weights, void *stream);
+int enslam_composite_density_bwd(int32_t n_rays, int32_t n_samples, const float *raw, const double *z_vals,
+                                 const float *rays_d, const double *depth, const double *g_depth, const double *g_var,
+                                 const float *g_rgb, float *d_raw, float *d_rays_d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
