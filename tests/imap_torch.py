@@ -32,7 +32,8 @@ def eval_points(p, params, bound):
 def composite_density(raw, z, rays_d):
     """(depth, var, rgb, weights) with volume density (raw[..., 3] = sigma)."""
     dists = (z[..., 1:] - z[..., :-1]).float()
-    dists = torch.cat([dists, torch.full_like(dists[..., :1], 1e10)], -1)
+    # the last interval is 1e10 (the reference expands 1e10 to dists[..., :1].shape, which is empty for one sample)
+    dists = torch.cat([dists, dists.new_full(dists.shape[:-1] + (1,), 1e10)], -1)
     dists = dists * torch.norm(rays_d[..., None, :], dim=-1)
     alpha = 1. - torch.exp(-F.relu(raw[..., 3]) * dists)
     T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1. - alpha + 1e-10], -1), -1)[:, :-1]
@@ -73,3 +74,87 @@ def fixture_grad(fx, name, grad):
     if name.startswith('pts_linears.') and name.endswith('weight'):
         return grad[torch.as_tensor(fx['grad_rows']).to(grad.device)]
     return grad
+
+
+# ------------------------------------------------------------------------------------------------ float64 yardstick
+def im_arg(p, B):
+    """the Fourier argument p . B as the kernel forms it (csrc/imap_mlp.hip im_arg): float32, the three products summed
+    left to right, no fused multiply-add.  p [P,3], B [3,93]; returns float32 [P,93]."""
+    p, B = p.float(), B.float()
+    return (p[:, 0:1] * B[0] + p[:, 1:2] * B[1]) + p[:, 2:3] * B[2]
+
+
+def _outside(p, bound):
+    """points that Renderer.eval_points / eval_points above give sigma = 100 (compared in the points' precision)"""
+    b = bound.to(p.device)
+    inside = torch.ones(p.shape[0], dtype=torch.bool, device=p.device)
+    for a in range(3):
+        inside &= (p[:, a] < b[a, 1]) & (p[:, a] > b[a, 0])
+    return ~inside
+
+
+def _forward64(p, params):
+    arg = im_arg(p, params[0]).double()
+    h = torch.sin(arg)
+    ins, dens, zs = [], [h.abs()], []
+    margin = torch.full((p.shape[0],), float('inf'), dtype=torch.float64, device=p.device)
+    for i in range(4):
+        W, b = params[1 + 2 * i].double(), params[2 + 2 * i].double()
+        z = h @ W.T + b
+        den = h.abs() @ W.abs().T + b.abs()
+        rel = torch.where(den > 0, z.abs() / den.clamp_min(1e-300), torch.full_like(z, float('inf')))
+        margin = torch.minimum(margin, rel.min(1).values)
+        ins.append(h)
+        zs.append(z)
+        h = torch.relu(z)
+        dens.append(den * (z > 0))
+    raw = h @ params[9].double().T + params[10].double()
+    raw_scale = h.abs() @ params[9].double().abs().T + params[10].double().abs()
+    return raw, margin, arg, ins, dens, zs, h, raw_scale
+
+
+def mlp64(p, params):
+    """(raw float64 [P,4], margin float64 [P]) of the iMAP decoder.  The argument p . B is formed in float32 exactly as
+    the kernel forms it (im_arg); sin, the four ReLU linears and the output linear run in float64.  margin is the
+    relative ReLU margin per point: the minimum over all 1024 pre-activations z = W h + b of |z| / (|W||h| + |b|).
+    Where it is well above float32 rounding (~1e-6), a float32 evaluation of the point takes relu's branches as this
+    one does."""
+    raw, margin = _forward64(p, params)[:2]
+    return raw, margin
+
+
+def grads64(p, params, cot, bound=None):
+    """An explicit float64 backward of eval_points (bound given) or mlp (bound None) at cotangent cot [P,4]; the argument
+    is im_arg's float32 value, its gradient flows to p and B as in float64 (dB = p32^T dz, dp = dz B^T).
+
+    Returns (raw, d_pts, grads, scales, d_pts_scale, raw_scale): raw [P,4] (sigma = 100 outside the bound), d_pts [P,3],
+    the 11 parameter gradients in NAMES order, and for each one the scale of a float32 evaluation's rounding error: the
+    same sum taken over the absolute values of its terms, where each factor is itself replaced by the abs-sum of the sum
+    that formed it (|h_l| by [z_l > 0] (|W_l||h_{l-1}| + |b_l|), dPre_l by [z_l > 0] |dPre_{l+1}||W_{l+1}|, dz by
+    |dPre_0||W_0||cos|).  So: Gd_l^T Hd_l for W_l, sum Gd_l for b_l, |p|^T Gz for B, Gz |B|^T for d_pts, |Wo||h_4| +
+    |bo| for raw.  A plain |dPre_l|^T |in_l| does not bound the error: a ReLU output a little above its margin is the
+    small difference of large terms and carries a few percent of error of its own."""
+    raw, _, arg, ins, dens, zs, h4, raw_scale = _forward64(p, params)
+    g = cot.double().clone()
+    if bound is not None:
+        out = _outside(p, bound)
+        raw, raw_scale = raw.clone(), raw_scale.clone()
+        raw[out, 3] = 100.
+        raw_scale[out, 3] = 100.
+        g[out, 3] = 0.
+    W = [params[1 + 2 * i].double() for i in range(4)]
+    Wo, B = params[9].double(), params[0].double()
+    grads, scales = [None] * 11, [None] * 11
+    grads[9], scales[9] = g.T @ h4, g.abs().T @ dens[4]
+    grads[10], scales[10] = g.sum(0), g.abs().sum(0)
+    dpre, gd = (g @ Wo) * (zs[3] > 0), (g.abs() @ Wo.abs()) * (zs[3] > 0)
+    for i in range(3, -1, -1):
+        grads[1 + 2 * i], scales[1 + 2 * i] = dpre.T @ ins[i], gd.T @ dens[i]
+        grads[2 + 2 * i], scales[2 + 2 * i] = dpre.sum(0), gd.sum(0)
+        d_in, a_in = dpre @ W[i], dpre.abs() @ W[i].abs()
+        dpre, gd = (d_in * (zs[i - 1] > 0), a_in * (zs[i - 1] > 0)) if i > 0 else (d_in, a_in)
+    c = torch.cos(arg)
+    dz, gz = dpre * c, gd * c.abs()
+    p32 = p.float().double()
+    grads[0], scales[0] = p32.T @ dz, p32.abs().T @ gz
+    return raw, dz @ B.T, grads, scales, gz @ B.abs().T, raw_scale

@@ -96,3 +96,58 @@ def test_imap_renderer_configuration_and_cpu_refusal():
     # iMAP decoder with occupancy compositing is not a configuration of the reference
     with pytest.raises(NotImplementedError):
         E.Renderer(dict(cfg, occupancy=True), None, slam)
+
+
+def _fixture_params():
+    from tests.imap_torch import NAMES, fixture_decoder
+    named = dict(fixture_decoder(load("tiny_imap")).named_parameters())
+    return [named[n].detach() for n in NAMES]
+
+
+def test_float64_yardstick_reproduces_the_fixture():
+    """mlp64 (the argument p . B in float32 in the kernel's order, the rest in float64) against the reference's float32
+    eval_points: 7.5e-7 of the largest |raw|, so the fixture's own float32 rounding is all that separates them."""
+    from tests.imap_torch import mlp64
+    fx = load("tiny_imap")
+    raw, margin = mlp64(torch.from_numpy(fx['ep_pts']), _fixture_params())
+    ref = fx['ep_raw'].astype(np.float64)
+    out = ref[:, 3] == 100
+    assert out.sum() > 20 and (~out).sum() > 20
+    got = raw.numpy()
+    scale = np.abs(ref).max()
+    assert np.abs(got[:, :3] - ref[:, :3]).max() <= 2e-6 * scale
+    assert np.abs(got[~out, 3] - ref[~out, 3]).max() <= 2e-6 * scale
+    assert margin.shape == (700,) and (margin >= 0).all() and np.median(margin.numpy()) > 1e-5
+
+
+def test_float64_backward_equals_autograd():
+    """grads64's explicit backward against float64 autograd of the restatement (mlp, with eval_points' bound mask) at the
+    same float32 argument: the argument enters autograd as im_arg's value plus (p B - (p B).detach()), and mlp runs on it
+    with an identity B, so the values are im_arg's and the gradient to p and B is float64's.  The points are float32
+    values, so p32 = p there.  Scales are non-negative and bound every gradient."""
+    from tests.imap_torch import NAMES, _outside, grads64, im_arg, mlp
+    fx = load("tiny_imap")
+    ps = _fixture_params()
+    bound = torch.from_numpy(fx['bound'])
+    g = torch.Generator().manual_seed(5)
+    p = torch.cat([torch.from_numpy(fx['ep_pts']), (torch.rand(300, 3, generator=g, dtype=torch.float64) * 2 - 1) * 3])
+    p = p.float().double()
+    cot = torch.randn(p.shape[0], 4, generator=g, dtype=torch.float64)
+    raw, d_pts, grads, scales, d_scale, raw_scale = grads64(p, ps, cot, bound)
+
+    pa = p.clone().requires_grad_(True)
+    pa64 = [q.double().clone().requires_grad_(True) for q in ps]
+    lin = pa @ pa64[0]
+    arg = im_arg(p, ps[0]).double() + (lin - lin.detach())
+    r = mlp(arg, [torch.eye(93, dtype=torch.float64)] + pa64[1:])
+    out = _outside(p, bound)
+    assert out.any() and (~out).any()
+    r = torch.cat([r[:, :3], torch.where(out, torch.full_like(r[:, 3], 100.), r[:, 3])[:, None]], 1)
+    (r * cot).sum().backward()
+    assert (r.detach() - raw).abs().max() <= 1e-12 * raw.abs().max()
+    assert (d_pts - pa.grad).abs().max() <= 1e-12 * pa.grad.abs().max()
+    for name, got, ref, s in zip(NAMES, grads, pa64, scales):
+        assert got.shape == ref.shape and s.shape == ref.shape, name
+        assert (got - ref.grad).abs().max() <= 1e-12 * ref.grad.abs().max(), name
+        assert (s >= 0).all() and (got.abs() <= s * (1 + 1e-12)).all(), name
+    assert (d_pts.abs() <= d_scale * (1 + 1e-12)).all() and (raw.abs() <= raw_scale * (1 + 1e-12)).all()
