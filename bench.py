@@ -5,7 +5,11 @@ One "step" = Renderer.render_batch_ray (sampling, gather, decoders, compositing)
 (Mapper.py:553-562) + backward producing gradients for the three feature grids, EVERY decoder parameter
 (the reference never freezes any, so its autograd computes them all) and the rays -- on synthetic data.
 
-  python bench.py --gpus N --steps K --warmup W [--config 2|4|5]
+  python bench.py --gpus N --steps K --warmup W [--config 2|4|5] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints the result line.
+Everything else the bench measures -- the kernel-event roofline, the reference-API and eager-step rates, the CPU baseline,
+the per-phase times of a multi-rank step and the extra configurations under "also" -- runs only with --full.
 
   --config 2 (default)  BASELINE configs[1]: Replica room0, full 4-level grid, stage `color`, 1000 rays x 48 samples
                         PER GPU (weak scaling: every rank renders its own 1000-ray block of an N x 1000 batch)
@@ -17,12 +21,12 @@ One "step" = Renderer.render_batch_ray (sampling, gather, decoders, compositing)
   N > 1: one rank per GPU under torch.distributed.run.  Started WITHOUT it (`python bench.py --gpus N`, no WORLD_SIZE in the
   environment) the script starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself as a child process
   -- before this process has touched the GPU -- and exits with the child's code; rank 0 of the child prints the JSON line.
-  Leaf gradients are summed with one bucketed RCCL all-reduce (touched 64-voxel blocks only).  The default run (config 2) also measures config 4 on the same ranks
+  Leaf gradients are summed with one bucketed RCCL all-reduce (touched 64-voxel blocks only).  With --full, config 2 also measures config 4 on the same ranks
   and reports it inside the SAME JSON line under "also" (disable with --no-secondary), so that a 1/2/4/8-GPU sweep
   records both the weak (room0) and the strong (office0, 5000 rays) curve.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the `roofline` and `cpu_baseline` objects).  At N = 1 the default
-run adds, under "also": config 4 on this GPU, config 3 (the tracker's camera iteration with the event term: path only, path +
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the `roofline` and `cpu_baseline` objects of --full).  At N = 1 --full
+adds, under "also": config 4 on this GPU, config 3 (the tracker's camera iteration with the event term: path only, path +
 U-Net, one hipGraph per iteration), the 200-ray tracker iteration, and the headline step on a map with real surfaces (an
 analytic room fitted by the path's own mapper) next to the random-init scene; `api_rays_per_s` is the Python-driven step through
 the reference API only (render_batch_ray + torch loss + backward), no graph capture and no fused-loss entry point.
@@ -350,7 +354,7 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
                  dump_dir=None):
     """Measure one configuration.  scaling 'weak': `rays` per rank (batch = world x rays); 'strong': `rays` per
     iteration, split over the ranks in contiguous blocks (parallel.shard_range).  dump_dir: rank 0 writes what the last timed
-    step computed there (dump_outputs)."""
+    step computed there (dump_outputs).  Without args.full only the warm-up and the timed steps run on the GPU."""
     import evennicer_slam_amd as E
     import evennicer_slam_amd.functional as EF
     from evennicer_slam_amd import parallel as PAR
@@ -553,7 +557,7 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
     # What an UNCHANGED caller gets: the reference API only (render_batch_ray -> the caller's torch loss -> loss.backward()),
     # Python-driven, no graph capture, no fused-loss entry point (Mapper.py:548-575 around this Renderer).
     api = None
-    if world == 1 and stage != 'coarse' and not args.no_api:
+    if args.full and world == 1 and stage != 'coarse' and not args.no_api:
         def api_step():
             torch._C._increment_version(leaves)         # (an optimiser step happened: values changed in place)
             for t in leaves:
@@ -596,13 +600,15 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
     gstep = None
     phases = None
     graph_outputs = None
+    eager_elapsed = None
     if args.eager:
         elapsed, loss = env.timed(step, steps)
         eager_elapsed, eager_steps = elapsed, steps
     else:
-        eager_steps = min(steps, 50)
-        eager_elapsed, _ = env.timed(step, eager_steps)
-        del _
+        if args.full:               # the Python-driven step's own rate (`eager_rays_per_s`)
+            eager_steps = min(steps, 50)
+            eager_elapsed, _ = env.timed(step, eager_steps)
+            del _
         from evennicer_slam_amd.graph import GraphedStep
         for t in leaves:
             t.grad = None
@@ -664,7 +670,7 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
     # where a multi-rank step spends its time (HIP events around the three parts of 20 extra steps, this rank's stream;
     # outside the timed region): what precedes the local step, the local step, the gradient collective with its glue
     comm_ms = None
-    if comm_on:
+    if comm_on and args.full:
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(20)]
         local = (lambda: gstep.replay()) if (mode == 'hipgraph' and gstep is not None) else local_step
         torch.cuda.synchronize()
@@ -699,7 +705,7 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
                                                             f"(touched 64-voxel blocks only)"},
         "loss": float(loss.item()), "mode": mode, "loss_impl": "torch" if args.torch_loss else ("fused HIP (losses.rgbd_loss)" if args.separate_loss or stage == 'coarse'
                                                                   else "fused into the compositing launches (render_batch_ray_rgbd_loss)"),
-        "eager_rays_per_s": total_rays * eager_steps / eager_elapsed,
+        "eager_rays_per_s": total_rays * eager_steps / eager_elapsed if eager_elapsed is not None else None,
         "autograd_engine": ("headline (hipGraph replay): no autograd at replay time; eager_rays_per_s and the capture: backward inside "
                             "`with functional.engine_on_calling_thread()` (scoped, restored on exit); api_rays_per_s: PyTorch's "
                             "default threading; api_calling_thread_rays_per_s: the scoped form"),
@@ -714,7 +720,7 @@ def run_workload(env, args, scene, rays, scaling, steps, warmup, want_events, wa
     if fit is not None:
         out["fit"] = fit
     if comm_on:
-        out["comm"] = dict(comm_ms, bucket_bytes=int(comm['bytes']), mode=mode,
+        out["comm"] = dict(comm_ms or {}, bucket_bytes=int(comm['bytes']), mode=mode,
                            flags="marked locally from the whole batch" if whole_batch else "MAX all-reduce of per-rank flags",
                            pre_step="side stream, under the previous iteration's collective" if overlap_pre else "in line",
                            bucket_block_voxels=BUCKET_BLOCK if whole_batch else 64)
@@ -1050,7 +1056,7 @@ def run_slam_fps(dev, frames=10):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
@@ -1060,10 +1066,13 @@ def main():
     ap.add_argument('--scene', default=None, help='override the configuration\'s scene (room0, office0, recording4)')
     ap.add_argument('--scaling', default=None, choices=('weak', 'strong'))
     ap.add_argument('--stage', default='color')
-    ap.add_argument('--no-secondary', action='store_true', help='default run: skip the extra config-4 measurement reported under "also"')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-events', action='store_true')
-    ap.add_argument('--no-api', action='store_true', help='skip the reference-API-only (Python-driven) timing `api_rays_per_s`')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, run every other measurement: kernel-event roofline, reference-API and eager-step '
+                         'rates, CPU baseline, per-phase times of a multi-rank step, the extra configurations under "also"')
+    ap.add_argument('--no-secondary', action='store_true', help='--full, config 2: skip the extra measurements reported under "also"')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-kernel-events', action='store_true', help='--full: skip the kernel-event timing behind `roofline`')
+    ap.add_argument('--no-api', action='store_true', help='--full: skip the reference-API-only (Python-driven) timing `api_rays_per_s`')
     ap.add_argument('--variant', default=None, choices=('surfaces', 'mapper_grads'), help="primary workload on a map fitted to an analytic room | with the reference mapper's gradient set")
     ap.add_argument('--grid-layout', default='channels_last_3d', choices=('channels_last_3d', 'contiguous'),
                     help='memory format of the feature-grid tensors (same shape and values either way)')
@@ -1074,8 +1083,11 @@ def main():
                     help='after the timed steps, write what the last one computed (loss, depth, var, color, the gradients of '
                          'every leaf) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed, seeded sample of '
                          'the rows of the largest arrays when the whole set is larger)')
-    args = ap.parse_args()
+    return ap.parse_args(argv)
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and os.environ.get('ENSLAM_BENCH_FORCE_COMM') != '1':
         sys.exit(spawn_ranks(args.gpus))        # (nothing in this process has touched the GPU yet)
     env = Env(args)
@@ -1085,11 +1097,11 @@ def main():
     rays = args.rays if args.rays is not None else spec['rays']
     scaling = args.scaling or spec['scaling']
     primary = run_workload(env, args, scene, rays, scaling, args.steps, args.warmup,
-                           want_events=not args.no_kernel_events,
-                           want_cpu_baseline=env.rank == 0 and env.world == 1 and not args.no_cpu_baseline, variant=args.variant,
-                           dump_dir=args.dump_outputs)
+                           want_events=args.full and not args.no_kernel_events,
+                           want_cpu_baseline=args.full and env.rank == 0 and env.world == 1 and not args.no_cpu_baseline,
+                           variant=args.variant, dump_dir=args.dump_outputs)
     primary["config"]["baseline_config"] = spec['name'] if not customised else "custom"
-    if args.config == 2 and not customised and not args.no_secondary and args.stage == 'color':
+    if args.full and args.config == 2 and not customised and not args.no_secondary and args.stage == 'color':
         s4 = CONFIGS[4]
         sec = run_workload(env, args, s4['scene'], s4['rays'], s4['scaling'], max(20, args.steps // 2), max(5, args.warmup // 2),
                            want_events=False, want_cpu_baseline=False)
@@ -1139,7 +1151,8 @@ def main():
                 try:
                     import subprocess
                     cmd = [sys.executable, os.path.abspath(__file__), '--variant', 'mapper_grads', '--steps', str(max(50, args.steps // 2)),
-                           '--warmup', str(max(5, args.warmup // 2)), '--no-secondary', '--no-cpu-baseline', '--no-api', '--no-kernel-events']
+                           '--warmup', str(max(5, args.warmup // 2)), '--full', '--no-secondary', '--no-cpu-baseline', '--no-api',
+                           '--no-kernel-events']
                     cp = subprocess.run(cmd, env=dict(os.environ, ENSLAM_DEFER_SCATTER='2'), capture_output=True, text=True, timeout=300)
                     line = [ln for ln in cp.stdout.splitlines() if ln.startswith('{')][-1]
                     c = json.loads(line)

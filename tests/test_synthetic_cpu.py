@@ -91,6 +91,14 @@ def test_bench_starts_its_own_ranks(monkeypatch):
     assert seen['env'].get('HSA_ENABLE_IPC_MODE_LEGACY') == '0'
 
 
+def test_bench_full_is_opt_in():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs only the headline; every other measurement needs --full."""
+    import bench
+    plain = bench.parse_args(['--gpus', '1', '--steps', '5', '--warmup', '2'])
+    assert not plain.full and (plain.gpus, plain.steps, plain.warmup) == (1, 5, 2)
+    assert bench.parse_args(['--full']).full
+
+
 def test_bench_physical_core_query():
     import bench
     cores, model = bench.physical_cores()

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/shard_times.txt; : > $O
 cd $R
 one() {  # scene rays extra-env...
   scene=$1; rays=$2; shift 2
-  env "$@" python bench.py --scene $scene --rays $rays --scaling weak --steps 100 --warmup 10 --no-secondary --no-cpu-baseline --no-kernel-events --no-api 2>/dev/null \
+  env "$@" python bench.py --scene $scene --rays $rays --scaling weak --steps 100 --warmup 10 --full --no-secondary --no-cpu-baseline --no-kernel-events --no-api 2>/dev/null \
     | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d.get('comm') or {}; print('$scene', $rays, '%.4f ms/step' % d['ms_per_step'], '%.3f Mrays/s' % (d['value']/1e6), 'mode', d['mode'], 'bucket_bytes', c.get('bucket_bytes'), 'pre_ms', c.get('pre_ms'), 'allreduce_ms', c.get('gradient_allreduce_ms'))" >> $O
 }
 for n in 1000 500 250 125; do one room0 $n A=1; done
