@@ -1846,6 +1846,83 @@ def marching_cubes(volume, level, origin, spacing):
     return verts, faces
 
 
+def world_to_camera(c2w_list):
+    """float64 numpy [K,3,4]: the upper rows of the inverses of the camera-to-world matrices, inverted on the host in float64 as
+    the reference does (np.linalg.inv of the pose's numpy form)."""
+    import numpy as np
+    out = np.zeros((len(c2w_list), 3, 4), np.float64)
+    for k, c2w in enumerate(c2w_list):
+        m = c2w.detach().cpu().numpy() if torch.is_tensor(c2w) else np.asarray(c2w)
+        out[k] = np.linalg.inv(m.astype(np.float64))[:3]
+    return out
+
+
+def visibility(points, w2c, cam, edge_seen=0, edge_forecast=-1000, z_eps=1e-8, limit=None, depth=None, lattice=None,
+               first=0, count=None, want_classes=True, want_counts=False, dtype=torch.float32):
+    """Classes and per-camera counts of points against K cameras (enslam_visibility, enslam_hip.h; Mesher.py:88-190 and
+    Mapper.py:218-241).
+      points    float32 [P,3] on a HIP device, or None with lattice=(ax, ay, az) float32 device axes: the `count` points from
+                linear index `first` of the lattice in Mesher.lattice_volume's order
+      w2c       world-to-camera matrices [K,3,4] or [K,4,4] (numpy or tensor, see world_to_camera); they are rounded to `dtype`
+      cam       dict with H, W, fx, fy, cx, cy
+      limit     float32 [K] per-camera bound on the projected depth, or None
+      depth     float32 [K,H,W] depth images for the depth test, or None
+      dtype     torch.float32 (the Mesher's arithmetic) or torch.float64 (the overlap selection's)
+    Returns (classes uint8 [P] or None, counts int32 [K] or None); classes: 0 unseen, 1 seen, 2 forecast.  The largest depth
+    sample the forecast test uses is taken over the points of THIS call, so chunk as the reference chunks."""
+    lib = L.lib()
+    if dtype not in (torch.float32, torch.float64):
+        raise L.EnslamError(f"visibility computes in float32 or float64 (got {dtype})")
+    if (points is None) == (lattice is None):
+        raise L.EnslamError("visibility wants either explicit points or a lattice")
+    if points is not None:
+        _require_hip(points, "points")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise L.EnslamError(f"points must be [P,3] (got shape {tuple(points.shape)})")
+        pts, axes, dims, first = _f32c(points), (None, None, None), (0, 0, 0), 0
+        P, dev = int(pts.shape[0]), pts.device
+    else:
+        for a in lattice:
+            _require_hip(a, "lattice axes")
+            if a.dim() != 1 or a.shape[0] < 1:
+                raise L.EnslamError("lattice axes must be non-empty 1-D tensors")
+        pts, axes = None, tuple(_f32c(a) for a in lattice)
+        dims = tuple(int(a.shape[0]) for a in axes)
+        total = dims[0] * dims[1] * dims[2]
+        P, dev = (total - int(first)) if count is None else int(count), axes[0].device
+        if first < 0 or P < 0 or first + P > total:
+            raise L.EnslamError(f"lattice range [{first}, {first + P}) leaves the {total} lattice points")
+    w = torch.as_tensor(w2c)
+    if w.dim() != 3 or tuple(w.shape[1:]) not in ((3, 4), (4, 4)):
+        raise L.EnslamError(f"w2c must be [K,3,4] or [K,4,4] (got shape {tuple(w.shape)})")
+    K = int(w.shape[0])
+    w = w[:, :3].to(dtype).contiguous().to(dev)
+    H, W = int(cam['H']), int(cam['W'])
+    lim = dep = ws = None
+    if limit is not None:
+        _require_hip(limit, "limit")
+        lim = _f32c(limit).reshape(-1)
+        if lim.shape[0] != K:
+            raise L.EnslamError(f"limit has {lim.shape[0]} entries for {K} cameras")
+    if depth is not None:
+        _require_hip(depth, "depth")
+        dep = _f32c(depth)
+        if tuple(dep.shape) != (K, H, W):
+            raise L.EnslamError(f"depth must be [{K},{H},{W}] (got shape {tuple(dep.shape)})")
+        nbytes = ctypes.c_int64()
+        L.check(lib.enslam_visibility_workspace(K, ctypes.byref(nbytes)), "enslam_visibility_workspace")
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    classes = torch.empty(P, dtype=torch.uint8, device=dev) if want_classes else None
+    counts = torch.empty(K, dtype=torch.int32, device=dev) if want_counts else None
+    with torch.cuda.device(dev):
+        L.check(lib.enslam_visibility(1 if dtype is torch.float64 else 0, P, _ptr(pts), _ptr(axes[0]), _ptr(axes[1]), _ptr(axes[2]),
+                                      dims[0], dims[1], dims[2], int(first), K, _ptr(w) if K else None, float(cam['fx']),
+                                      float(cam['fy']), float(cam['cx']), float(cam['cy']), H, W, int(edge_seen),
+                                      int(edge_forecast), float(z_eps), _ptr(lim), _ptr(dep), _ptr(ws), _ptr(classes),
+                                      _ptr(counts), _stream()), "enslam_visibility")
+    return classes, counts
+
+
 # ------------------------------------------------------------------------------------------------
 # iMAP mode (configs/imap.yaml): the 256-wide decoder (csrc/imap_mlp.hip) and density compositing
 # ------------------------------------------------------------------------------------------------

@@ -22,6 +22,52 @@ from .functional import (VoxelMajorGrid, _native_vm, _ptr, _require_hip, _stream
 GRID_KEYS = ('grid_coarse', 'grid_middle', 'grid_fine', 'grid_color')
 
 
+def overlap_points(gt_color, gt_depth, c2w, cam, N_samples=16, pixels=100, device='cuda:0'):
+    """float32 [pixels * N_samples, 3]: the points keyframe_selection_overlap tests (Mapper.py:206-217): `pixels` random
+    pixels of the current frame (common.get_samples, torch's global generator) and N_samples points per ray between 0.8 x and
+    0.5 m behind the measured depth."""
+    from .common import get_samples
+    H, W = cam['H'], cam['W']
+    rays_o, rays_d, d, _ = get_samples(0, H, 0, W, pixels, H, W, cam['fx'], cam['fy'], cam['cx'], cam['cy'], c2w, gt_depth,
+                                       gt_color, device)
+    return ray_sample_points(rays_o, rays_d, d, N_samples)
+
+
+def ray_sample_points(rays_o, rays_d, d, N_samples=16):
+    """float32 [N * N_samples, 3]: per ray N_samples points between 0.8 x its depth and 0.5 m behind it (Mapper.py:209-217)"""
+    t = torch.linspace(0., 1., steps=N_samples).to(rays_o.device)       # formed on the host, as the reference forms it
+    d = d.reshape(-1, 1)
+    z_vals = (d * 0.8) * (1. - t) + (d + 0.5) * t                       # [N, N_samples]
+    return (rays_o[:, None, :] + rays_d[:, None, :] * z_vals[:, :, None]).reshape(-1, 3)
+
+
+def overlap_counts(points, keyframe_dict, cam, edge=20, z_eps=1e-5):
+    """int32 [K] (host numpy): per keyframe the points that project at least `edge` pixels inside its image, in front of
+    it, in float64 with the pixel coordinates compared as float32 (Mapper.py:220-238) -- one enslam_visibility launch."""
+    import numpy as np
+    from . import functional as EF
+    if len(keyframe_dict) == 0:
+        return np.zeros(0, np.int32)
+    w2c = EF.world_to_camera([kf['est_c2w'] for kf in keyframe_dict])
+    _, counts = EF.visibility(points, w2c, cam, edge_seen=edge, edge_forecast=edge, z_eps=z_eps, want_classes=False,
+                              want_counts=True, dtype=torch.float64)
+    return counts.cpu().numpy()
+
+
+def keyframe_selection_overlap(gt_color, gt_depth, c2w, keyframe_dict, k, cam, N_samples=16, pixels=100, device='cuda:0'):
+    """Mapper.keyframe_selection_overlap (Mapper.py:188-250): ids of up to k keyframes that see some of the current frame's
+    sampled points, in the order of numpy's global RNG (np.random.permutation over the ids sorted by share, as the reference
+    draws it, so a seeded caller gets the reference's list)."""
+    import numpy as np
+    pts = overlap_points(gt_color, gt_depth, c2w, cam, N_samples, pixels, device)
+    counts = overlap_counts(pts, keyframe_dict, cam)
+    share = counts / max(int(pts.shape[0]), 1)
+    # sorted(..., reverse=True) is stable: equal shares keep their keyframe order
+    order = sorted(range(len(keyframe_dict)), key=lambda i: share[i], reverse=True)
+    selected = [i for i in order if share[i] > 0.00]
+    return list(np.random.permutation(np.array(selected))[:k])
+
+
 class MaskedGridOptimizer:
     """Adam over the masked voxels of feature grids, state and parameters in voxel-major layout.
 

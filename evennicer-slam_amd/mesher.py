@@ -12,8 +12,10 @@ Numerical differences from the reference:
     table, so face sets may differ in ambiguous cells; the vertex set does not;
   * order: after cleaning, the kept faces keep their marching-cubes order and the vertices their order, where trimesh
     regroups both per connected component.  The geometry is the same.
-Not implemented (NotImplementedError): show_forecast (mesh_coarse_level; every shipped config has it False), depth_test
-(the shipped default is False) and the iMAP colour method render_ray_along_normal."""
+On a HIP device the seen / forecast / unseen classification (point_masks, with and without depth_test, and the lattice of
+show_forecast) is one enslam_visibility launch per chunk of points (csrc/visibility.hip).  On device='cpu' point_masks keeps
+its torch form for depth_test False; depth_test True and show_forecast need the HIP device there (NotImplementedError).
+Not implemented anywhere: the iMAP colour method render_ray_along_normal."""
 import numpy as np
 import torch
 
@@ -55,12 +57,56 @@ class Mesher(object):
         self.timing = {}            # seconds of the last get_mesh, per phase (tools/bench_mesher.py)
 
     # ------------------------------------------------------------------ masks
-    def point_masks(self, input_points, keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames=False):
-        """(seen, forecast, unseen) bool numpy masks of the points (Mesher.py:53-211, depth_test False): a point is seen
-        when it projects strictly inside the image of a keyframe (or of every frame up to idx), in front of the camera and
-        closer than 1.1 x that frame's largest depth; forecast: the same with the image enlarged by 1000 pixels."""
+    def _views(self, keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames):
+        """(w2c float64 numpy [K,3,4], limit float32 [K] or None, depth float32 [K,H,W] or None) of the cameras point_masks
+        tests: every frame up to idx (no depth limit, no depth test: Mesher.py:88-122) or the keyframes, each with
+        1.1 x its largest depth as limit, or with its depth image when depth_test is set (Mesher.py:124-186)."""
+        if get_mask_use_all_frames:
+            return EF.world_to_camera([estimate_c2w_list[i] for i in range(0, idx + 1)]), None, None
+        w2c = EF.world_to_camera([kf['est_c2w'] for kf in keyframe_dict])
+        if len(keyframe_dict) == 0:
+            return w2c, None, None
         if self.depth_test:
-            raise NotImplementedError("point_masks with depth_test=True (the shipped configs have it False)")
+            return w2c, None, torch.stack([kf['depth'].to(device).float().reshape(self.H, self.W) for kf in keyframe_dict])
+        return w2c, torch.stack([torch.max(kf['depth']).to(device).float() * 1.1 for kf in keyframe_dict]), None
+
+    def point_classes(self, views, device, points=None, lattice=None):
+        """uint8 device tensor [P] (0 unseen, 1 seen, 2 forecast) of explicit points [P,3] or of a lattice (three float32
+        device axes, Mesher.lattice_volume's order), one enslam_visibility call per points_batch_size chunk: with depth_test
+        the forecast test uses the largest depth sample of the chunk, as the reference's per-chunk torch.max does."""
+        w2c, limit, depth = views
+        w2c = torch.from_numpy(w2c).float().to(device)          # rounded and uploaded once for all chunks
+        cam = dict(H=self.H, W=self.W, fx=self.fx, fy=self.fy, cx=self.cx, cy=self.cy)
+        P = points.shape[0] if points is not None else lattice[0].shape[0] * lattice[1].shape[0] * lattice[2].shape[0]
+        out = torch.empty(P, dtype=torch.uint8, device=device)
+        for lo in range(0, P, self.points_batch_size):
+            n = min(self.points_batch_size, P - lo)
+            if points is not None:
+                cls, _ = EF.visibility(points[lo:lo + n].to(device).float(), w2c, cam, limit=limit, depth=depth)
+            else:
+                cls, _ = EF.visibility(None, w2c, cam, limit=limit, depth=depth, lattice=lattice, first=lo, count=n)
+            out[lo:lo + n] = cls
+        return out
+
+    def point_masks(self, input_points, keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames=False):
+        """(seen, forecast, unseen) bool numpy masks of the points (Mesher.py:53-211): a point is seen when it projects
+        strictly inside the image of a keyframe (or of every frame up to idx), in front of the camera and closer than
+        1.1 x that frame's largest depth -- with depth_test, within 2.4 of the keyframe's depth sampled at its pixel instead;
+        forecast: the same with the image enlarged by 1000 pixels (with depth_test: closer than the largest depth sample of
+        the chunk), and not seen.  HIP device: csrc/visibility.hip; cpu: the torch form below, depth_test False only."""
+        if torch.device(device).type == 'cuda':
+            if not isinstance(input_points, torch.Tensor):
+                input_points = torch.from_numpy(np.asarray(input_points))
+            views = self._views(keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames)
+            cls = self.point_classes(views, device, points=input_points.reshape(-1, 3)).cpu().numpy()
+            return cls == 1, cls == 2, cls == 0
+        return self.point_masks_torch(input_points, keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames)
+
+    def point_masks_torch(self, input_points, keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames=False):
+        """point_masks as a loop of torch operations over the cameras (depth_test False only): what device='cpu' runs, and the
+        baseline tools/bench_visibility.py times the kernel against on the GPU."""
+        if self.depth_test:
+            raise NotImplementedError("point_masks with depth_test=True needs a HIP device (csrc/visibility.hip)")
         H, W, fx, fy, cx, cy = self.H, self.W, self.fx, self.fy, self.cx, self.cy
         if not isinstance(input_points, torch.Tensor):
             input_points = torch.from_numpy(np.asarray(input_points))
@@ -133,6 +179,24 @@ class Mesher(object):
                 z.masked_fill_(~inside_halfspaces(pts, hs), 100.0)
         return vol
 
+    def forecast_volume(self, c, decoders, xyz, views, device):
+        """(float32 [nx, ny, nz] volume, uint8 [nx*ny*nz] classes) of show_forecast (Mesher.py:389-425): stage-`fine` occupancy
+        where the lattice point is seen, stage-`coarse` occupancy + 0.2 where it is forecast, -100 where unseen.  Only the
+        points of a class are evaluated (compact, evaluate, scatter back)."""
+        ax = [torch.from_numpy(a.astype(np.float32)).to(device) for a in xyz]
+        nx, ny, nz = (len(a) for a in xyz)
+        classes = self.point_classes(views, device, lattice=ax)
+        flat = torch.full((nx * ny * nz,), -100.0, dtype=torch.float32, device=device)
+        coarse_bound = self.renderer._coarse_bound(decoders)
+        for cls, stage, offset in ((1, 'fine', None), (2, 'coarse', 0.2)):
+            for lin in torch.split(torch.nonzero(classes == cls).reshape(-1), self.points_batch_size):
+                if lin.numel() == 0:
+                    continue
+                pts = torch.stack([ax[0][lin // (ny * nz)], ax[1][(lin // nz) % ny], ax[2][lin % nz]], 1)
+                occ = EF.eval_points(pts, decoders, c, stage, self.bound, apply_mask=True, coarse_bound=coarse_bound)[:, 3]
+                flat[lin] = occ if offset is None else occ + offset
+        return flat.view(nx, ny, nz), classes
+
     # ------------------------------------------------------------------ the mesh
     def get_mesh(self, mesh_out_file, c, decoders, keyframe_dict, estimate_c2w_list, idx, device='cuda:0', show_forecast=False,
                  color=True, clean_mesh=True, get_mask_use_all_frames=False):
@@ -140,8 +204,8 @@ class Mesher(object):
         (vertices float64 [V,3], faces int32 [F,3], colours uint8 [V,3] or None); None when no surface is found (the
         reference prints a message and returns there as well)."""
         import time
-        if show_forecast:
-            raise NotImplementedError("show_forecast (mesh_coarse_level) is not implemented; every shipped config has it False")
+        if show_forecast and torch.device(device).type != 'cuda':
+            raise NotImplementedError("show_forecast (mesh_coarse_level) needs a HIP device (csrc/visibility.hip)")
         if color and self.color_mesh_extraction_method != 'direct_point_query':
             raise NotImplementedError(f"color_mesh_extraction_method {self.color_mesh_extraction_method!r} belongs to iMAP; "
                                       "the HIP path implements direct_point_query")
@@ -156,9 +220,13 @@ class Mesher(object):
         with torch.no_grad():
             t0 = time.perf_counter()
             xyz = self.get_grid_uniform(self.resolution)['xyz']
-            halfspaces = self.get_bound_from_frames(keyframe_dict, self.scale)
+            views = self._views(keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames) if show_forecast else None
+            halfspaces = self.get_bound_from_frames(keyframe_dict, self.scale) if clean_mesh or not show_forecast else None
             t0 = lap('hull', t0)
-            vol = self.lattice_volume(c, decoders, xyz, halfspaces, device)
+            if show_forecast:
+                vol, _ = self.forecast_volume(c, decoders, xyz, views, device)
+            else:
+                vol = self.lattice_volume(c, decoders, xyz, halfspaces, device)
             t0 = lap('lattice', t0)
             verts, faces = EF.marching_cubes(vol, self.level_set, [a[0] for a in xyz],
                                              [a[2] - a[1] for a in xyz])
@@ -170,9 +238,17 @@ class Mesher(object):
             vertices, faces = verts.cpu().numpy(), faces.cpu().numpy()
 
             if clean_mesh:
-                seen, _, _ = self.point_masks(vertices, keyframe_dict, estimate_c2w_list, idx, device=device,
-                                              get_mask_use_all_frames=get_mask_use_all_frames)
-                faces = faces[~(~seen)[faces].all(axis=1)]
+                t1 = time.perf_counter()
+                if show_forecast:                       # Mesher.py:472-486: faces with a vertex inside the keyframes' hull stay
+                    hs = torch.from_numpy(halfspaces).to(device)
+                    keep = torch.cat([inside_halfspaces(p, hs) for p in torch.split(verts, self.points_batch_size)]).cpu().numpy()
+                else:
+                    keep, _, _ = self.point_masks(vertices, keyframe_dict, estimate_c2w_list, idx, device=device,
+                                                  get_mask_use_all_frames=get_mask_use_all_frames)
+                faces = faces[~(~keep)[faces].all(axis=1)]
+                if torch.device(device).type == 'cuda':
+                    torch.cuda.synchronize(device)
+                timing['clean_masks'] = time.perf_counter() - t1
                 faces = filter_components(vertices, faces, self.remove_small_geometry_threshold * self.scale * self.scale,
                                           self.get_largest_components)
                 vertices, faces = drop_unreferenced(vertices, faces)
@@ -186,6 +262,10 @@ class Mesher(object):
                     z = torch.cat([EF.eval_points(p, decoders, c, 'color', self.bound, apply_mask=True)[:, :3]
                                    for p in torch.split(pts, self.points_batch_size)]).cpu().numpy()
                 vertex_colors = (np.clip(z, 0, 1) * 255).astype(np.uint8)
+                if show_forecast:                       # Mesher.py:556-563: cyan for the forecast region
+                    _, forecast, _ = self.point_masks(vertices, keyframe_dict, estimate_c2w_list, idx, device=device,
+                                                      get_mask_use_all_frames=get_mask_use_all_frames)
+                    vertex_colors[forecast] = (0, 255, 255)
             t0 = lap('color', t0)
 
             vertices = vertices / self.scale

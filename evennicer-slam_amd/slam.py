@@ -8,7 +8,9 @@ the same per-frame schedule runs in one process on one GPU, tracker and mapper a
                   is given), the candidate with the smallest loss is kept (:321-330)
   every `mapping.every_frame`-th frame: `mapping.iters` joint iterations (`mapper.MapperIteration`: frustum-masked grids,
                   colour decoder, local BA over the window of keyframes -- the reference's `global` selection: random
-                  keyframes + the latest one + the current frame, Mapper.py:280-303) and `update_para_from_mapping`
+                  keyframes + the latest one + the current frame, Mapper.py:280-303; with
+                  `mapping.keyframe_selection_method: 'overlap'` the keyframes that see the current frame's points,
+                  `mapper.keyframe_selection_overlap`) and `update_para_from_mapping`
                   then -- `cfg['coarse']` -- the COARSE mapper's round on the same frame (the reference's third process,
                   EvenNICER_SLAM.py:303-311: `Mapper(..., coarse_mapper=True)` runs the same schedule with stage `coarse`
                   only, every voxel of `grid_coarse` optimisable, no depth guidance, no BA; Mapper.py:133-136,326-328,
@@ -34,7 +36,7 @@ from . import functional as EF
 from .common import get_camera_from_tensor, get_tensor_from_camera
 from .decoder import get_model
 from .eval_ate import Logger, evaluate_checkpoint
-from .mapper import FusedAdam, MapperIteration
+from .mapper import FusedAdam, MapperIteration, keyframe_selection_overlap
 from .renderer import Renderer
 from .scene import GRID_KEYS, grid_init, scene_bound
 from .tracker import TrackerIteration
@@ -197,9 +199,16 @@ class SLAM:
         m = self.cfg['mapping']
         window = m.get('mapping_window_size', 5)
         frames = []
-        if self.keyframe_dict:                                               # 'global' selection, Mapper.py:280-303
+        if self.keyframe_dict:                                               # keyframe selection, Mapper.py:280-303
             n_old = len(self.keyframe_dict) - 1
-            pick = list(np.random.permutation(n_old)[:max(window - 2, 0)]) if n_old > 0 else []
+            method = m.get('keyframe_selection_method', 'global')
+            if method == 'overlap':                                          # Mapper.py:290-293
+                pick = keyframe_selection_overlap(gt_color, gt_depth, cur_c2w, self.keyframe_dict[:-1], max(window - 2, 0),
+                                                  self.cam, device=self.device)
+            elif method == 'global':
+                pick = list(np.random.permutation(n_old)[:max(window - 2, 0)]) if n_old > 0 else []
+            else:
+                raise ValueError(f"mapping.keyframe_selection_method {method!r}: 'global' or 'overlap'")
             pick = sorted(set(int(p) for p in pick) | {len(self.keyframe_dict) - 1})
             oldest = min(pick)
             for k in pick:
@@ -340,8 +349,8 @@ class SLAM:
         mesher = self.mesher = Mesher(cfg, None, self)
         idx = getattr(self, 'last_idx', 0) if idx is None else idx
         return mesher.get_mesh(path, self.shared_c, self.shared_decoders, self.keyframe_dict, self.estimate_c2w_list, idx,
-                               device=self.device, color=color, clean_mesh=clean_mesh,
-                               get_mask_use_all_frames=get_mask_use_all_frames)
+                               device=self.device, show_forecast=bool(cfg['meshing']['mesh_coarse_level']), color=color,
+                               clean_mesh=clean_mesh, get_mask_use_all_frames=get_mask_use_all_frames)
 
     def evaluate(self, ckpt):
         return evaluate_checkpoint(ckpt, scale=self.scale)

@@ -398,6 +398,31 @@ int enslam_marching_cubes_emit(const float *volume, int32_t nx, int32_t ny, int3
                                const double *origin_host, const double *spacing_host, void *workspace, int32_t n_verts,
                                int32_t n_faces, double *verts, int32_t *faces, void *stream);
 
+/* Visibility of points in K cameras: the projection loop of Mesher.point_masks (src/utils/Mesher.py:88-190) and of
+ * Mapper.keyframe_selection_overlap (src/Mapper.py:218-241).  One thread per point; the cameras are wave-uniform data.
+ * Per camera k, in float32 (real64 = 0, the Mesher's points.float() path) or float64 (real64 = 1, the Mapper's numpy path):
+ *   cam = w2c[k][:3,:3] p + w2c[k][:3,3]; cam.x *= -1; uvz = K cam; z = uvz.z + z_eps; (u, v) = float32(uvz.xy / z)
+ *   inside(edge) = edge < u < W - edge  and  edge < v < H - edge  and  z < 0                      (all strict)
+ *   seen_k     = inside(edge_seen)     [and -cam.z < limit[k]]  [and  sample - 2.4 < -cam.z < sample + 2.4]
+ *   forecast_k = inside(edge_forecast) [and -cam.z < limit[k]]  [and  -cam.z < max_sample[k]]
+ * where sample is the bilinear sample of depth[k] at (u, v) with zero padding (F.grid_sample, align_corners=True) and
+ * max_sample[k] the largest sample of camera k over ALL points of the call, in view or not (the reference's
+ * torch.max(depth_sample) per chunk of points: chunk in the caller to match it chunk for chunk).
+ *   points   float32 [P,3], or NULL for a lattice: point i is (ax[ix], ay[iy], az[iz]) of the linear index
+ *            lattice_first + i = (ix * ny + iy) * nz + iz  (Mesher.lattice_volume's order); ax/ay/az float32 [nx]/[ny]/[nz]
+ *   w2c      float32 (real64 = 0) or float64 (real64 = 1) [K,12]: the upper three rows of each world-to-camera matrix
+ *   limit    float32 [K] or NULL;  depth float32 [K,H,W] or NULL (needs workspace, H and W >= 2)
+ *   classes  uint8 [P] or NULL: 0 unseen, 1 seen by some camera, 2 forecast by some camera and seen by none
+ *   counts   int32 [K] or NULL: points that pass seen_k (zeroed by the call).  With counts NULL a wave leaves the camera
+ *            loop once all its points are seen.
+ * Integer adds and a maximum: the outputs do not depend on the launch order.  P = 0 and K = 0 are valid. */
+int enslam_visibility_workspace(int32_t n_cams, int64_t *bytes_host);
+int enslam_visibility(int32_t real64, int64_t n_points, const float *points, const float *ax, const float *ay,
+                      const float *az, int32_t nx, int32_t ny, int32_t nz, int64_t lattice_first, int32_t n_cams,
+                      const void *w2c, double fx, double fy, double cx, double cy, int32_t H, int32_t W, int32_t edge_seen,
+                      int32_t edge_forecast, double z_eps, const float *limit, const float *depth, void *workspace,
+                      uint8_t *classes, int32_t *counts, void *stream);
+
 /* Hand-derived backward of enslam_render_fwd (replaces autograd of the reference ops).
  *   g_depth float64 [N], g_var float64 [N] or NULL, g_rgb float32 [N,3] or NULL
  *   grad_grids[k].data : voxel-major accumulators (caller-zeroed) or NULL to skip that grid

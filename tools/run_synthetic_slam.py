@@ -1,7 +1,8 @@
 """The run harness on an analytic, view-consistent sequence (synthetic.BoxRoom): ATE of the full schedule against the ATE of
 poses left at their constant-speed initialisation (tracking_iters = 0).  usage: python tools/run_synthetic_slam.py [n_frames]
-[--mesh DIR]: also mesh the tracked run's map (SLAM.get_mesh) into DIR/mesh.ply and report accuracy, completion and completion
-ratio (eval_recon, metres) against the room's analytic surfaces seen by the keyframes."""
+[--mesh DIR] [--overlap]: --mesh also meshes the tracked run's map (SLAM.get_mesh) into DIR/mesh.ply and reports accuracy,
+completion and completion ratio (eval_recon, metres) against the room's analytic surfaces seen by the keyframes; --overlap selects
+the mapping window with mapping.keyframe_selection_method 'overlap' (mapper.keyframe_selection_overlap) instead of 'global'."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -33,12 +34,14 @@ def mesh_metrics(slam, path, n_gt=200000):
                 vertices=int(len(verts)), faces=int(len(faces)), gt_points_seen=int(len(gt)), timing=dict(slam.mesher.timing))
 
 
-def run(n=30, verbose=True, mesh_dir=None):
+def run(n=30, verbose=True, mesh_dir=None, overlap=False):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         (inp, evf), poses = write_demo_sequence(os.path.join(tmp, 'data'), n, cam, step=float(os.environ.get('STEP', 0.012)), yaw_deg=float(os.environ.get('YAW', 0.5)))
         cfg = demo_config(inp, evf, cam, device=DEV, env=os.environ)
+        if overlap:
+            cfg['mapping'] = dict(cfg['mapping'], keyframe_selection_method='overlap')
         ds = D.get_dataset(cfg, types.SimpleNamespace(input_folder=None, event_folder=None), 1, device=DEV)
         for tag, iters in ((('tracked', None),) if os.environ.get('SKIP_BASE') == '1' else (('tracked', None), ('const_speed_init', 0))):
             torch.manual_seed(0); np.random.seed(0)
@@ -65,4 +68,7 @@ if __name__ == '__main__':
         k = args.index('--mesh')
         mesh_dir = args[k + 1]
         del args[k:k + 2]
-    run(int(args[0]) if args else 30, mesh_dir=mesh_dir)
+    overlap = '--overlap' in args
+    if overlap:
+        args.remove('--overlap')
+    run(int(args[0]) if args else 30, mesh_dir=mesh_dir, overlap=overlap)
