@@ -142,6 +142,12 @@ _SIGS = {
     "enslam_visibility": (ctypes.c_int, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64,
                                          c_int32, c_void_p, c_double, c_double, c_double, c_double, c_int32, c_int32, c_int32,
                                          c_int32, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_mesh_clean_workspace": (ctypes.c_int, [c_int32, c_int32, POINTER(c_int64)]),
+    "enslam_mesh_components": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "enslam_mesh_clean_count": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_double, c_int32, c_void_p,
+                                               c_void_p, c_void_p]),
+    "enslam_mesh_clean_emit": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                                              c_void_p, c_void_p, c_void_p]),
     "enslam_render_bwd": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(Scene),
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(Grid),
                                          POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,

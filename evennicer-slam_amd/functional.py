@@ -1923,6 +1923,82 @@ def visibility(points, w2c, cam, edge_seen=0, edge_forecast=-1000, z_eps=1e-8, l
     return classes, counts
 
 
+def _mesh_faces(faces, n_verts):
+    _require_hip(faces, "faces")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype is not torch.int32:
+        raise L.EnslamError(f"faces must be int32 [F,3] (got {faces.dtype} {tuple(faces.shape)})")
+    if int(n_verts) < 0:
+        raise L.EnslamError(f"n_verts must not be negative (got {n_verts})")
+    return faces.detach().contiguous()
+
+
+def _mesh_workspace(lib, n_verts, n_faces, dev):
+    nbytes = ctypes.c_int64()
+    L.check(lib.enslam_mesh_clean_workspace(n_verts, n_faces, ctypes.byref(nbytes)), "enslam_mesh_clean_workspace")
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+
+
+def mesh_components(faces, n_verts):
+    """int32 [F] labels of the edge-connected components of a triangle mesh (faces int32 [F,3] on a HIP device, indices in
+    [0, n_verts)): the label of a face is the smallest face index of its component; faces sharing an edge (the same unordered
+    vertex pair) are connected, faces sharing only a vertex are not (enslam_hip.h; mesher.face_components is the host form)."""
+    lib = L.lib()
+    f = _mesh_faces(faces, n_verts)
+    F, dev = int(f.shape[0]), f.device
+    labels = torch.empty(F, dtype=torch.int32, device=dev)
+    if F == 0:
+        return labels
+    with torch.cuda.device(dev):
+        ws = _mesh_workspace(lib, int(n_verts), F, dev)
+        L.check(lib.enslam_mesh_components(_ptr(f), F, int(n_verts), _ptr(ws), _ptr(labels), _stream()), "enslam_mesh_components")
+    return labels
+
+
+def mesh_clean(vertices, faces, vertex_keep=None, min_area=0.0, largest_only=False, stats=None):
+    """(vertices float64 [V',3], faces int32 [F',3], vertex_index int32 [V']) of a triangle mesh (vertices float64 [V,3], faces
+    int32 [F,3], HIP device) after the cleaning of Mesher.get_mesh: faces none of whose vertices is kept by vertex_keep (bool /
+    uint8 [V], None: keep all) go, then every edge-connected component whose area is not above min_area (or, with largest_only,
+    every component but the largest), then the vertices no face uses.  Faces and vertices keep their order; vertex_index is the
+    original index of each kept vertex.  Bit-equal to mesher.drop_unreferenced(v, mesher.filter_components(v, f_masked, ...))
+    unless a component's area is within rounding of the threshold (enslam_hip.h).  One host synchronisation: the counts.
+    `stats`, a dict, receives the number of components after the mask drop."""
+    lib = L.lib()
+    _require_hip(vertices, "vertices")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype is not torch.float64:
+        raise L.EnslamError(f"vertices must be float64 [V,3] (got {vertices.dtype} {tuple(vertices.shape)})")
+    v = vertices.detach().contiguous()
+    V, dev = int(v.shape[0]), v.device
+    f = _mesh_faces(faces, V)
+    F = int(f.shape[0])
+    keep = None
+    if vertex_keep is not None:
+        _require_hip(vertex_keep, "vertex_keep")
+        if vertex_keep.dtype not in (torch.bool, torch.uint8) or tuple(vertex_keep.shape) != (V,):
+            raise L.EnslamError(f"vertex_keep must be bool or uint8 [{V}] (got {vertex_keep.dtype} {tuple(vertex_keep.shape)})")
+        keep = vertex_keep.detach().contiguous()
+        keep = keep.view(torch.uint8) if keep.dtype is torch.bool else keep
+    if f.device != dev or (keep is not None and keep.device != dev):
+        raise L.EnslamError("vertices, faces and vertex_keep must live on one device")
+    if F == 0:
+        if stats is not None:
+            stats['components'] = 0
+        return v.new_empty((0, 3)), f.new_empty((0, 3)), torch.empty(0, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _mesh_workspace(lib, V, F, dev)
+        counts = torch.empty(3, dtype=torch.int32, device=dev)
+        L.check(lib.enslam_mesh_clean_count(_ptr(v), V, _ptr(f), F, _ptr(keep), float(min_area), 1 if largest_only else 0,
+                                            _ptr(ws), _ptr(counts), _stream()), "enslam_mesh_clean_count")
+        n_v, n_f, n_comp = counts.tolist()
+        v_out = torch.empty((n_v, 3), dtype=torch.float64, device=dev)
+        f_out = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
+        index = torch.empty(n_v, dtype=torch.int32, device=dev)
+        L.check(lib.enslam_mesh_clean_emit(_ptr(v), V, _ptr(f), F, _ptr(ws), n_v, n_f, _ptr(v_out), _ptr(f_out), _ptr(index),
+                                           _stream()), "enslam_mesh_clean_emit")
+    if stats is not None:
+        stats['components'] = n_comp
+    return v_out, f_out, index
+
+
 # ------------------------------------------------------------------------------------------------
 # iMAP mode (configs/imap.yaml): the 256-wide decoder (csrc/imap_mlp.hip) and density compositing
 # ------------------------------------------------------------------------------------------------

@@ -12,6 +12,12 @@ Numerical differences from the reference:
     table, so face sets may differ in ambiguous cells; the vertex set does not;
   * order: after cleaning, the kept faces keep their marching-cubes order and the vertices their order, where trimesh
     regroups both per connected component.  The geometry is the same.
+With clean_mesh on a HIP device the mesh stays on the device from the lattice to the download before the file is written: the
+vertex mask, the connected-component filter and the compaction are functional.mesh_clean (csrc/mesh_clean.hip), the colour
+query and the forecast classes read the device vertices.  The host helpers at the end of this file (face_components,
+filter_components, drop_unreferenced) are what device='cpu' runs, what `mesher.clean_on_host = True` (an attribute, set after
+construction) selects on a HIP device, and what the tests compare the kernels with; both routes give bit-identical arrays and
+files.
 On a HIP device the seen / forecast / unseen classification (point_masks, with and without depth_test, and the lattice of
 show_forecast) is one enslam_visibility launch per chunk of points (csrc/visibility.hip).  On device='cpu' point_masks keeps
 its torch form for depth_test False; depth_test True and show_forecast need the HIP device there (NotImplementedError).
@@ -55,6 +61,10 @@ class Mesher(object):
 
         self.H, self.W, self.fx, self.fy, self.cx, self.cy = slam.H, slam.W, slam.fx, slam.fy, slam.cx, slam.cy
         self.timing = {}            # seconds of the last get_mesh, per phase (tools/bench_mesher.py)
+        # set after construction (the constructor keeps the reference's signature): True runs the cleaning of get_mesh through
+        # the host helpers below on a HIP device as well -- what device='cpu' always does, and what the device route is tested against
+        self.clean_on_host = False
+        self.clean_stats = {}       # components / vertices / faces of the last device-route cleaning
 
     # ------------------------------------------------------------------ masks
     def _views(self, keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames):
@@ -235,6 +245,10 @@ class Mesher(object):
             if faces.shape[0] == 0:
                 print('marching_cubes error. Possibly no surface extracted from the level set.')
                 return None
+            on_device = clean_mesh and torch.device(device).type == 'cuda' and not self.clean_on_host
+            if on_device:
+                return self._finish_on_device(mesh_out_file, verts, faces, halfspaces, c, decoders, keyframe_dict, estimate_c2w_list,
+                                              idx, device, show_forecast, color, get_mask_use_all_frames, lap, t0)
             vertices, faces = verts.cpu().numpy(), faces.cpu().numpy()
 
             if clean_mesh:
@@ -249,9 +263,11 @@ class Mesher(object):
                 if torch.device(device).type == 'cuda':
                     torch.cuda.synchronize(device)
                 timing['clean_masks'] = time.perf_counter() - t1
+                t1 = time.perf_counter()
                 faces = filter_components(vertices, faces, self.remove_small_geometry_threshold * self.scale * self.scale,
                                           self.get_largest_components)
                 vertices, faces = drop_unreferenced(vertices, faces)
+                timing['clean_components'] = time.perf_counter() - t1
             t0 = lap('clean', t0)
 
             vertex_colors = None
@@ -274,6 +290,58 @@ class Mesher(object):
             if self.verbose:
                 print('Saved mesh at', mesh_out_file)
             return vertices, faces, vertex_colors
+
+    def _finish_on_device(self, mesh_out_file, verts, faces, halfspaces, c, decoders, keyframe_dict, estimate_c2w_list, idx, device,
+                          show_forecast, color, get_mask_use_all_frames, lap, t0):
+        """get_mesh from the marching-cubes output on, with clean_mesh, on a HIP device: the vertex mask, the component filter
+        and the compaction (functional.mesh_clean), the colour query and the forecast classes stay on the device; vertices,
+        faces, colours and the forecast mask are downloaded once, before the file is written.  Every array and the file are
+        bit-identical to the host route's (clean_on_host = True): the same float32 roundings of the same float64 vertices,
+        the same chunks, the same kept faces and vertices in the same order."""
+        import time
+        timing = self.timing
+        t1 = time.perf_counter()
+        if show_forecast:                               # Mesher.py:472-486: faces with a vertex inside the keyframes' hull stay
+            hs = torch.from_numpy(halfspaces).to(device)
+            keep = torch.cat([inside_halfspaces(p, hs) for p in torch.split(verts, self.points_batch_size)])
+        else:
+            views = self._views(keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames)
+            keep = self.point_classes(views, device, points=verts) == 1
+        torch.cuda.synchronize(device)
+        timing['clean_masks'] = time.perf_counter() - t1
+        t1 = time.perf_counter()
+        stats = {}
+        verts, faces, _ = EF.mesh_clean(verts, faces, keep, self.remove_small_geometry_threshold * self.scale * self.scale,
+                                        self.get_largest_components, stats=stats)
+        torch.cuda.synchronize(device)
+        timing['clean_components'] = time.perf_counter() - t1
+        self.clean_stats = dict(components=stats['components'], vertices=int(verts.shape[0]), faces=int(faces.shape[0]))
+        t0 = lap('clean', t0)
+
+        z = forecast = None
+        if color:
+            pts = verts.float()
+            z = torch.zeros((0, 3), dtype=torch.float32, device=device)
+            if pts.shape[0]:
+                z = torch.cat([EF.eval_points(p, decoders, c, 'color', self.bound, apply_mask=True)[:, :3]
+                               for p in torch.split(pts, self.points_batch_size)])
+            if show_forecast:                           # Mesher.py:556-563: cyan for the forecast region
+                views = self._views(keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames)
+                forecast = self.point_classes(views, device, points=verts) == 2
+        vertices, faces = verts.cpu().numpy(), faces.cpu().numpy()
+        vertex_colors = None
+        if color:
+            vertex_colors = (np.clip(z.cpu().numpy(), 0, 1) * 255).astype(np.uint8)
+            if forecast is not None:
+                vertex_colors[forecast.cpu().numpy()] = (0, 255, 255)
+        t0 = lap('color', t0)
+
+        vertices = vertices / self.scale
+        write_ply(mesh_out_file, vertices, faces, vertex_colors)
+        lap('write', t0)
+        if self.verbose:
+            print('Saved mesh at', mesh_out_file)
+        return vertices, faces, vertex_colors
 
 
 # ---------------------------------------------------------------------------------------------------------------------

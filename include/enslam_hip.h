@@ -423,6 +423,37 @@ int enslam_visibility(int32_t real64, int64_t n_points, const float *points, con
                       int32_t edge_forecast, double z_eps, const float *limit, const float *depth, void *workspace,
                       uint8_t *classes, int32_t *counts, void *stream);
 
+/* Mesh cleaning: the tail of Mesher.get_mesh (src/utils/Mesher.py:469-510) on a triangle mesh, vertices float64 [V,3] and
+ * faces int32 [F,3] with indices in [0, V) -- any such mesh, boundary edges and edges of three or more faces included.
+ *   adjacency  two faces are adjacent iff they share an undirected edge (the same unordered pair of vertex indices); faces
+ *              that share only a vertex are not
+ *   labels     int32 [F]: the smallest face index of the face's edge-connected component (canonical: it does not depend on
+ *              scheduling, and it numbers the components in the order of their first faces)
+ *   mask drop  vertex_keep uint8 [V] or NULL (keep all): a face goes iff none of its three vertices is kept
+ *   areas      0.5 * |(v1 - v0) x (v2 - v0)| per face in float64, unfused; summed per component in 80-bit fixed point scaled
+ *              by the mesh's largest face area (integer adds: the same bits in every run; a sum is below the exact sum of
+ *              its float64 areas by less than 2^-56 of the largest face area).  Non-finite areas count as zero.
+ *   keep rule  largest_only = 0: the components with area > min_area (strict); else the one with the largest area, ties to
+ *              the smallest label
+ *   output     kept faces in their original order, the vertices a kept face references in their original order, face
+ *              indices remapped; vertex_index_out int32 [V_out] or NULL: the original index of each kept vertex.  Output
+ *              positions are prefix sums: no order depends on scheduling.
+ * Two calls on one stream with the same workspace, as for marching cubes: the count call leaves {kept vertices, kept faces,
+ * components after the mask drop} in counts (device int32 [3]); the caller reads them back, allocates exactly and passes
+ * them to the emit call with the same vertices and faces.  The components call is the labelling alone (no mask, indices are
+ * only compared, never used as addresses).  Limits: n_faces <= 2^24, n_verts <= 2^26 (ENSLAM_EUNSUPPORTED beyond); negative
+ * counts, NULL where data is required and a NaN min_area: ENSLAM_EINVAL.  A vertex index outside [0, V) is the caller's error:
+ * the cleaning calls drop such a face, nothing reports it.  Zero faces or vertices are valid (empty result). */
+int enslam_mesh_clean_workspace(int32_t n_verts, int32_t n_faces, int64_t *bytes_host);
+int enslam_mesh_components(const int32_t *faces, int32_t n_faces, int32_t n_verts, void *workspace, int32_t *labels_out,
+                           void *stream);
+int enslam_mesh_clean_count(const double *vertices, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                            const uint8_t *vertex_keep, double min_area, int32_t largest_only, void *workspace,
+                            int32_t *counts, void *stream);
+int enslam_mesh_clean_emit(const double *vertices, int32_t n_verts, const int32_t *faces, int32_t n_faces, void *workspace,
+                           int32_t n_verts_out, int32_t n_faces_out, double *vertices_out, int32_t *faces_out,
+                           int32_t *vertex_index_out, void *stream);
+
 /* Hand-derived backward of enslam_render_fwd (replaces autograd of the reference ops).
  *   g_depth float64 [N], g_var float64 [N] or NULL, g_rgb float32 [N,3] or NULL
  *   grad_grids[k].data : voxel-major accumulators (caller-zeroed) or NULL to skip that grid

@@ -1,6 +1,8 @@
 """Mesh extraction timings on one GPU: mesher.Mesher.get_mesh at 256^3 on the room0 scene (bench.py's seeded random-init map,
 one keyframe at the bench camera), by phase, and the HIP marching cubes split into its count and emit calls against the
-numpy restatement (tests/mc_numpy.py) on the same volume.  Prints one JSON line.
+numpy restatement (tests/mc_numpy.py) on the same volume; then the `clean` phase of get_mesh through the device route
+(csrc/mesh_clean.hip) and the host route (scipy / numpy), alternating in this process, and the device cleaning split into its
+calls by device events.  Prints one JSON line.
 
     python tools/bench_mesher.py [--resolution 256] [--repeat 5]"""
 import argparse
@@ -89,12 +91,77 @@ def main():
         t_np = time.perf_counter() - t0
         same = bool(np.array_equal(nf, f.cpu().numpy()) and np.abs(nv - v.cpu().numpy()).max(initial=0) <= 1e-12)
 
+        # the cleaning of get_mesh through both routes, alternating (the first pair warms up)
+        clean = {'device': [], 'host': []}
+        comps = {'device': [], 'host': []}
+        for r in range(args.repeat + 1):
+            for route in ('device', 'host'):
+                mesher.clean_on_host = route == 'host'
+                mesher.get_mesh(os.path.join(tmp, 'm.ply'), grids, model, [kf], None, 0, device=dev)
+                if r:
+                    clean[route].append(mesher.timing['clean'])
+                    comps[route].append(mesher.timing['clean_components'])
+        mesher.clean_on_host = False
+        clean_stats = dict(mesher.clean_stats)
+
+        # the device cleaning alone on the marching-cubes output, by call (device events): labelling only, count, emit
+        keep = (mesher.point_classes(mesher._views([kf], None, 0, dev, False), dev, points=v) == 1).view(torch.uint8)
+        Vn, Fn = int(v.shape[0]), int(f.shape[0])
+        E._lib.check(lib.enslam_mesh_clean_workspace(Vn, Fn, ctypes.byref(nb)), "workspace")
+        cws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        clean_ws_bytes = nb.value
+        lab = torch.empty(Fn, dtype=torch.int32, device=dev)
+        cnt3 = torch.empty(3, dtype=torch.int32, device=dev)
+        min_area = mesher.remove_small_geometry_threshold * mesher.scale * mesher.scale
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        t_lab, t_cnt, t_emt = [], [], []
+        for r in range(args.repeat + 1):
+            torch.cuda.synchronize()
+            ev[0].record()
+            E._lib.check(lib.enslam_mesh_components(f.data_ptr(), Fn, Vn, cws.data_ptr(), lab.data_ptr(), s), "components")
+            ev[1].record()
+            E._lib.check(lib.enslam_mesh_clean_count(v.data_ptr(), Vn, f.data_ptr(), Fn, keep.data_ptr(), min_area, 0, cws.data_ptr(),
+                                                     cnt3.data_ptr(), s), "clean_count")
+            Vo, Fo, Nc = cnt3.tolist()
+            vo = torch.empty((Vo, 3), dtype=torch.float64, device=dev)
+            fo = torch.empty((Fo, 3), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            ev[2].record()
+            E._lib.check(lib.enslam_mesh_clean_emit(v.data_ptr(), Vn, f.data_ptr(), Fn, cws.data_ptr(), Vo, Fo, vo.data_ptr(),
+                                                    fo.data_ptr(), None, s), "clean_emit")
+            ev[3].record()
+            torch.cuda.synchronize()
+            if r:
+                t_lab.append(ev[0].elapsed_time(ev[1]))
+                t_emt.append(ev[2].elapsed_time(ev[3]))
+            if r == 0:
+                first_cnt = (Vo, Fo, Nc)
+        for r in range(args.repeat):                     # the count call on its own (above, the read-back of the counts follows it)
+            torch.cuda.synchronize()
+            ev[0].record()
+            E._lib.check(lib.enslam_mesh_clean_count(v.data_ptr(), Vn, f.data_ptr(), Fn, keep.data_ptr(), min_area, 0, cws.data_ptr(),
+                                                     cnt3.data_ptr(), s), "clean_count")
+            ev[1].record()
+            torch.cuda.synchronize()
+            t_cnt.append(ev[0].elapsed_time(ev[1]))
+        assert tuple(cnt3.tolist()) == first_cnt
+
     med = lambda xs: float(np.median(xs)) * 1e3        # noqa: E731
+    span = lambda xs: [float(np.min(xs)) * 1e3, float(np.median(xs)) * 1e3, float(np.max(xs)) * 1e3]     # noqa: E731
     res = dict(resolution=args.resolution, scene='room0 (seeded random-init map, one keyframe)',
                vertices=counts[0], faces=counts[1], mc_vertices_unclean=int(V), mc_faces_unclean=int(F),
                get_mesh_ms={k: med([p[k] for p in phases]) for k in phases[0]},
                mc_count_ms=med(t_count), mc_emit_ms=med(t_emit), mc_binding_call_ms=med(t_call),
                mc_numpy_ms=t_np * 1e3, mc_equal_to_numpy=same,
+               clean_device_ms_min_med_max=span(clean['device']), clean_host_ms_min_med_max=span(clean['host']),
+               clean_components_device_ms_min_med_max=span(comps['device']),
+               clean_components_host_ms_min_med_max=span(comps['host']),
+               clean_device_faster_in_every_repeat=bool(max(clean['device']) < min(clean['host'])),
+               clean_host_over_device=float(np.median(clean['host']) / np.median(clean['device'])),
+               clean_components_after_mask=clean_stats.get('components'), clean_vertices=clean_stats.get('vertices'),
+               clean_faces=clean_stats.get('faces'),
+               mesh_components_call_ms=float(np.median(t_lab)), mesh_clean_count_call_ms=float(np.median(t_cnt)),
+               mesh_clean_emit_call_ms=float(np.median(t_emt)), mesh_clean_workspace_mib=clean_ws_bytes / 2**20,
                device=torch.cuda.get_device_name(0))
     print(json.dumps(res))
 
