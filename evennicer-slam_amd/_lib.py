@@ -148,6 +148,13 @@ _SIGS = {
                                                c_void_p, c_void_p]),
     "enslam_mesh_clean_emit": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
                                               c_void_p, c_void_p, c_void_p]),
+    "enslam_nn_workspace": (ctypes.c_int, [c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
+    "enslam_nn_build": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "enslam_nn_query": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_int32, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "enslam_mesh_depth_workspace": (ctypes.c_int, [c_int32, c_int32, POINTER(c_int64)]),
+    "enslam_mesh_depth": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_double,
+                                         c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "enslam_render_bwd": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(Scene),
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(Grid),
                                          POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,

@@ -1999,6 +1999,115 @@ def mesh_clean(vertices, faces, vertex_keep=None, min_area=0.0, largest_only=Fal
     return v_out, f_out, index
 
 
+NN_DEFAULT_MAX_RINGS = 4     # Chebyshev shells a query walks before the brute-force kernel takes it over
+
+
+def _points64(t, what):
+    _require_hip(t, what)
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype is not torch.float64:
+        raise L.EnslamError(f"{what} must be float64 [N,3] (got {t.dtype} {tuple(t.shape)})")
+    t = t.detach().contiguous()
+    if not bool(torch.isfinite(t).all()):
+        raise L.EnslamError(f"{what} holds non-finite coordinates")
+    return t
+
+
+class NearestIndex:
+    """The cell grid of enslam_nn_build over a reference point set (float64 [N,3], HIP device), for any number of queries --
+    the ICP of eval_recon.align_icp builds it once for its 30 iterations."""
+
+    def __init__(self, ref):
+        self.lib = L.lib()
+        self.ref = _points64(ref, "ref")
+        self.N, self.device = int(self.ref.shape[0]), self.ref.device
+        if self.N == 0:
+            raise L.EnslamError("nearest needs at least one reference point")
+        self.ws = None
+
+    def _grid(self):
+        if self.ws is None:
+            nbytes = ctypes.c_int64()
+            L.check(self.lib.enslam_nn_workspace(self.N, 0, ctypes.byref(nbytes), None), "enslam_nn_workspace")
+            self.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            L.check(self.lib.enslam_nn_build(_ptr(self.ref), self.N, _ptr(self.ws), _stream()), "enslam_nn_build")
+        return self.ws
+
+    def query(self, query, max_dist=None, max_rings=None, stats=None):
+        """(dist float64 [M], idx int32 [M]); `stats`, a dict, receives 'tail': the number of queries the brute-force kernel
+        finished (one host synchronisation, only when asked for)."""
+        q = _points64(query, "query")
+        if q.device != self.device:
+            raise L.EnslamError("query and ref must live on one device")
+        rings = NN_DEFAULT_MAX_RINGS if max_rings is None else int(max_rings)
+        md = float('inf') if max_dist is None else float(max_dist)
+        if rings < 0 or md != md:
+            raise L.EnslamError(f"nearest: max_rings must not be negative and max_dist not NaN (got {max_rings}, {max_dist})")
+        M = int(q.shape[0])
+        dist = torch.empty(M, dtype=torch.float64, device=self.device)
+        idx = torch.empty(M, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            grid = qws = None
+            if rings > 0 and M > 0:
+                grid = self._grid()
+                nbytes = ctypes.c_int64()
+                L.check(self.lib.enslam_nn_workspace(self.N, M, None, ctypes.byref(nbytes)), "enslam_nn_workspace")
+                qws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            tail = torch.zeros(1, dtype=torch.int32, device=self.device) if stats is not None else None
+            L.check(self.lib.enslam_nn_query(_ptr(self.ref), self.N, _ptr(q), M, md, rings, _ptr(grid), _ptr(qws), _ptr(dist),
+                                             _ptr(idx), _ptr(tail), _stream()), "enslam_nn_query")
+        if stats is not None:
+            stats['tail'] = int(tail.item())
+        return dist, idx
+
+
+def nearest(query, ref, max_dist=None, max_rings=None, stats=None):
+    """(dist float64 [M], idx int32 [M]): for every query point (float64 [M,3]) the nearest of the reference points (float64
+    [N,3], both on one HIP device), exactly: dist is sqrt((dx*dx + dy*dy) + dz*dz) in float64 in this order -- the bits of
+    numpy's np.sqrt(((q - r) ** 2).sum(-1)) -- and among reference points at the same distance the smallest index wins
+    (enslam_nn_query, enslam_hip.h).  max_dist: a query with no reference point closer than max_dist gets idx -1 and dist inf.
+    max_rings: shells of the cell grid a query walks before the brute-force kernel finishes it (default 4; 0: brute force
+    alone); the result does not depend on it.  Non-finite coordinates raise."""
+    return NearestIndex(ref).query(query, max_dist=max_dist, max_rings=max_rings, stats=stats)
+
+
+def mesh_depth(vertices, faces, w2c, cam, z_near=0.0, z_far=20.0):
+    """float32 [K,H,W] depth images of a triangle mesh (vertices float64 [V,3], faces int32 [F,3], HIP device) from the K
+    cameras w2c ([K,3,4] or [K,4,4], numpy or tensor, the convention of `visibility` / `world_to_camera`: the camera looks
+    down -z); cam is a dict with H, W, fx, fy, cx, cy.  Pixel (row j, column i) holds the smallest depth t, z_near < t <=
+    z_far, at which the ray through ((i - cx) / fx, -(j - cy) / fy, -1) -- the rays of get_rays and BoxRoom.render -- meets a
+    triangle, 0.0 where none does (enslam_mesh_depth, enslam_hip.h): both sides count, edges are inclusive, float64 up to the
+    rounding of t.  z_far = 20 is the reference's far plane; z_near = 0 is a difference: the reference's renderer derives
+    its near plane from the scene's bounding box."""
+    if not vertices.is_cuda:
+        raise NotImplementedError("mesh_depth needs a HIP device")
+    lib = L.lib()
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype is not torch.float64:
+        raise L.EnslamError(f"vertices must be float64 [V,3] (got {vertices.dtype} {tuple(vertices.shape)})")
+    v = vertices.detach().contiguous()
+    V, dev = int(v.shape[0]), v.device
+    f = _mesh_faces(faces, V)
+    if f.device != dev:
+        raise L.EnslamError("vertices and faces must live on one device")
+    F = int(f.shape[0])
+    w = torch.as_tensor(w2c)
+    if w.dim() != 3 or tuple(w.shape[1:]) not in ((3, 4), (4, 4)):
+        raise L.EnslamError(f"w2c must be [K,3,4] or [K,4,4] (got shape {tuple(w.shape)})")
+    K = int(w.shape[0])
+    w = w[:, :3].to(torch.float64).contiguous().to(dev)
+    H, W = int(cam['H']), int(cam['W'])
+    depth = torch.empty((K, H, W), dtype=torch.float32, device=dev)
+    if K == 0:
+        return depth
+    with torch.cuda.device(dev):
+        nbytes = ctypes.c_int64()
+        L.check(lib.enslam_mesh_depth_workspace(F, K, ctypes.byref(nbytes)), "enslam_mesh_depth_workspace")
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        L.check(lib.enslam_mesh_depth(_ptr(v) if V else None, V, _ptr(f) if F else None, F, _ptr(w), K, H, W, float(cam['fx']),
+                                      float(cam['fy']), float(cam['cx']), float(cam['cy']), float(z_near), float(z_far),
+                                      _ptr(ws), _ptr(depth), _stream()), "enslam_mesh_depth")
+    return depth
+
+
 # ------------------------------------------------------------------------------------------------
 # iMAP mode (configs/imap.yaml): the 256-wide decoder (csrc/imap_mlp.hip) and density compositing
 # ------------------------------------------------------------------------------------------------

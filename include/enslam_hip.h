@@ -454,6 +454,42 @@ int enslam_mesh_clean_emit(const double *vertices, int32_t n_verts, const int32_
                            int32_t n_verts_out, int32_t n_faces_out, double *vertices_out, int32_t *faces_out,
                            int32_t *vertex_index_out, void *stream);
 
+/* Exact nearest neighbour in float64 (the cKDTree queries of src/tools/eval_recon.py:24-43 and the correspondence search of
+ * its ICP alignment).  ref float64 [N,3], query float64 [M,3]; outputs dist float64 [M], idx int32 [M]:
+ *   dist[m] = sqrt((dx*dx + dy*dy) + dz*dz) of the nearest reference point, float64 in this order, unfused -- the bits of
+ *             numpy's np.sqrt(((q - r) ** 2).sum(-1)); among reference points at bit-equal distance the smallest index wins
+ *   max_dist  a query with no reference point at distance < max_dist gets idx = -1 and dist = +inf (pass +inf for none)
+ *   max_rings the query walks this many Chebyshev shells of a uniform cell grid over the reference (about 2 N cells, at
+ *             most 2^24, counting-sorted on the device by the build call); queries still open after that are finished by a
+ *             brute-force kernel (the reference through LDS, a workgroup per 256 queries).  0: brute force alone, the
+ *             build call and both workspaces are not needed.  The result does not depend on max_rings.
+ *   n_tail    device int32 [1] or NULL: the number of queries the brute-force kernel finished
+ * The build call sorts `ref` into grid_workspace; any number of query calls with the same ref and n_ref may follow on the
+ * same stream.  query_workspace is scratch of one query call.  Every call enqueues a fixed set of launches, whatever the
+ * data, and never waits for the device.  Limits: N, M <= 2^26; beyond them, N = 0, a negative max_rings or a NaN max_dist:
+ * ENSLAM_EINVAL.  M = 0 is valid (nothing is written but n_tail).  Coordinates must be finite (the caller checks). */
+int enslam_nn_workspace(int64_t n_ref, int64_t n_query, int64_t *grid_bytes_host, int64_t *query_bytes_host);
+int enslam_nn_build(const double *ref, int64_t n_ref, void *grid_workspace, void *stream);
+int enslam_nn_query(const double *ref, int64_t n_ref, const double *query, int64_t n_query, double max_dist,
+                    int32_t max_rings, void *grid_workspace, void *query_workspace, double *dist, int32_t *idx,
+                    int32_t *n_tail, void *stream);
+
+/* Depth images of a triangle mesh from K cameras (the off-screen depth renders of src/tools/eval_recon.py:131-210).
+ * vertices float64 [V,3], faces int32 [F,3], w2c float64 [K,12] (the upper three rows of each world-to-camera matrix, the
+ * convention of the visibility entry: the camera looks down -z); depth_out float32 [K,H,W].
+ *   pixel (row j, column i) = the smallest camera-space depth t, z_near < t <= z_far, at which the ray through
+ *   ((i - cx) / fx, -(j - cy) / fy, -1) meets a triangle; 0.0 where none does.  Both sides of a triangle count, edges are
+ *   inclusive, degenerate triangles and triangles whose plane holds the camera centre hit nothing, a face with a vertex
+ *   index outside [0, V) is dropped.  Float64 up to the rounding of t to float32.
+ * The depths are combined by an integer minimum: the images are the same bits in every run and do not depend on how the
+ * views are split over calls.  A fixed set of launches per call.  Limits: K*H*W <= 2^31 and F*K < 2^31
+ * (ENSLAM_EUNSUPPORTED beyond); 0 <= z_near < z_far, finite intrinsics with fx, fy != 0 (ENSLAM_EINVAL otherwise).
+ * F = 0 gives zero images, K = 0 is valid. */
+int enslam_mesh_depth_workspace(int32_t n_faces, int32_t n_views, int64_t *bytes_host);
+int enslam_mesh_depth(const double *vertices, int32_t n_verts, const int32_t *faces, int32_t n_faces, const double *w2c,
+                      int32_t n_views, int32_t H, int32_t W, double fx, double fy, double cx, double cy, double z_near,
+                      double z_far, void *workspace, float *depth_out, void *stream);
+
 /* Hand-derived backward of enslam_render_fwd (replaces autograd of the reference ops).
  *   g_depth float64 [N], g_var float64 [N] or NULL, g_rgb float32 [N,3] or NULL
  *   grad_grids[k].data : voxel-major accumulators (caller-zeroed) or NULL to skip that grid

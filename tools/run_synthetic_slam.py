@@ -1,7 +1,8 @@
 """The run harness on an analytic, view-consistent sequence (synthetic.BoxRoom): ATE of the full schedule against the ATE of
 poses left at their constant-speed initialisation (tracking_iters = 0).  usage: python tools/run_synthetic_slam.py [n_frames]
 [--mesh DIR] [--overlap]: --mesh also meshes the tracked run's map (SLAM.get_mesh) into DIR/mesh.ply and reports accuracy,
-completion and completion ratio (eval_recon, metres) against the room's analytic surfaces seen by the keyframes; --overlap selects
+completion and completion ratio (eval_recon, metres) against the room's analytic surfaces seen by the keyframes, of the mesh
+vertices and, under 'surface_samples', of area-weighted samples of the mesh (eval_recon.sample_surface); --overlap selects
 the mapping window with mapping.keyframe_selection_method 'overlap' (mapper.keyframe_selection_overlap) instead of 'global'."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -30,8 +31,17 @@ def mesh_metrics(slam, path, n_gt=200000):
     gt = room.sample_surface(n_gt).numpy()
     seen, _, _ = slam.mesher.point_masks(gt, slam.keyframe_dict, slam.estimate_c2w_list, slam.last_idx, slam.device)
     gt = gt[seen]
-    return dict(accuracy=R.accuracy(gt, verts), completion=R.completion(gt, verts), completion_ratio=R.completion_ratio(gt, verts),
-                vertices=int(len(verts)), faces=int(len(faces)), gt_points_seen=int(len(gt)), timing=dict(slam.mesher.timing))
+    out = dict(accuracy=R.accuracy(gt, verts), completion=R.completion(gt, verts), completion_ratio=R.completion_ratio(gt, verts),
+               vertices=int(len(verts)), faces=int(len(faces)), gt_points_seen=int(len(gt)), timing=dict(slam.mesher.timing))
+    # the same three numbers on surface samples of the mesh (what the reference's tool measures), on the device
+    dev = torch.device(slam.device)
+    if len(faces) and len(gt) and dev.type == 'cuda':
+        pts = R.sample_surface(torch.as_tensor(np.asarray(verts, np.float64)), torch.as_tensor(np.asarray(faces)), n_gt, seed=0,
+                               device=dev)[0]
+        g = torch.from_numpy(gt).to(dev)
+        out['surface_samples'] = dict(accuracy=R.accuracy(g, pts), completion=R.completion(g, pts),
+                                      completion_ratio=R.completion_ratio(g, pts), samples=int(n_gt))
+    return out
 
 
 def run(n=30, verbose=True, mesh_dir=None, overlap=False):
