@@ -51,6 +51,14 @@ class StepLayout(ctypes.Structure):           # enslam_step_layout
                 ("n_samples", c_int32), ("finish_needed", c_int32), ("inline_rays", c_int32), ("merged", c_int32)]
 
 
+class FramePlan(ctypes.Structure):            # enslam_frame_plan
+    _fields_ = [("h0", c_int32), ("w0", c_int32), ("channels", c_int32), ("he", c_int32), ("we", c_int32), ("H", c_int32),
+                ("W", c_int32), ("depth_int32", c_int32), ("has_dist", c_int32), ("undistort_events", c_int32),
+                ("crop_h", c_int32), ("crop_w", c_int32), ("crop_edge", c_int32), ("ev_neg", c_int32), ("ev_pos", c_int32),
+                ("reserved", c_int32), ("fx", c_double), ("fy", c_double), ("cx", c_double), ("cy", c_double),
+                ("dist", c_double * 8), ("png_depth_scale", c_double), ("scale", c_double)]
+
+
 class EnslamError(RuntimeError):
     pass
 
@@ -155,6 +163,9 @@ _SIGS = {
     "enslam_mesh_depth_workspace": (ctypes.c_int, [c_int32, c_int32, POINTER(c_int64)]),
     "enslam_mesh_depth": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_double,
                                          c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "enslam_frame_plan_bytes": (c_int64, []),
+    "enslam_frame_prepare": (ctypes.c_int, [POINTER(FramePlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
     "enslam_render_bwd": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(Scene),
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(Grid),
                                          POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
@@ -255,6 +266,8 @@ def lib():
         if hasattr(handle, "enslam_plan_struct_bytes") and (handle.enslam_plan_struct_bytes(0) != ctypes.sizeof(StepPlan) or
                                                            handle.enslam_plan_struct_bytes(1) != ctypes.sizeof(StepLayout)):
             raise EnslamError("libenslam_hip.so: enslam_step_plan / enslam_step_layout do not have the sizes this binding declares")
+        if hasattr(handle, "enslam_frame_plan_bytes") and handle.enslam_frame_plan_bytes() != ctypes.sizeof(FramePlan):
+            raise EnslamError("libenslam_hip.so: enslam_frame_plan does not have the size this binding declares")
         _lib = handle
     return _lib
 

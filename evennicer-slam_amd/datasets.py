@@ -19,7 +19,16 @@ numpy: the inverse map of OpenCV's pinhole + rational-radial + tangential model 
 sampling with a zero border.  cv2 interpolates 8-bit images in fixed point (1/32 pixel, 15-bit weights); this version
 interpolates in float64 and rounds once, so single pixels may differ from cv2's by one grey level.  cv2 is absent from the
 image, so that last level is "parity unpinned"; the geometry is pinned by a distort -> undistort round trip
-(tests/test_harness_cpu.py)."""
+(tests/test_harness_cpu.py).
+
+Further layouts of the reference's `dataset_dict` (src/utils/datasets.py:321-606): `RPG_event_dense` (`data.density` event
+frames per image interval, poses from traj_density{d}.txt), `TUM_RGBD` (rgb.txt / depth.txt / groundtruth.txt associated by
+nearest time stamp), `ScanNet` (frames/{color,depth,pose}, numeric file order) and `Azure` (scene/trajectory.log).  `CoFusion`
+is not built: its depth is OpenEXR and no EXR decoder is installed.
+
+`data.prepare` (attribute `prepare`): 'host' (default) prepares a frame with numpy / torch on the CPU as described above and
+uploads the result; 'device' uploads the RAW decoded arrays and prepares them in one launch of csrc/frame_prep.hip
+(functional.frame_prepare) -- the same stages in the same order and precision, an eighth of the upload."""
 import glob
 import os
 
@@ -66,9 +75,27 @@ class BaseDataset(torch.utils.data.Dataset):
         self.crop_size = cam.get('crop_size')
         self.input_folder = cfg['data']['input_folder'] if getattr(args, 'input_folder', None) is None else args.input_folder
         self.crop_edge = cam['crop_edge']
+        self.prepare = cfg['data'].get('prepare', 'host')
 
     def __len__(self):
         return self.n_img
+
+    def _on_device(self):
+        """True for prepare == 'device'; that route exists on a HIP device only."""
+        if self.prepare not in ('host', 'device'):
+            raise ValueError(f"data.prepare must be 'host' or 'device' (got {self.prepare!r})")
+        if self.prepare == 'device' and torch.device(self.device).type != 'cuda':
+            from ._lib import EnslamError
+            raise EnslamError(f"data.prepare = 'device' prepares frames with the HIP kernel and needs a HIP device (the dataset's "
+                              f"device is {self.device!r}); use prepare = 'host' there")
+        return self.prepare == 'device'
+
+    def _prepare_device(self, color, depth, event=None, events=False, event_order='replica', undistort_events=False):
+        from . import functional as EF
+        return EF.frame_prepare(color, depth, event, events=events, K=(self.fx, self.fy, self.cx, self.cy),
+                                distortion=self.distortion, png_depth_scale=self.png_depth_scale, scale=self.scale,
+                                crop_size=self.crop_size, crop_edge=self.crop_edge, event_order=event_order,
+                                undistort_events=undistort_events, device=self.device)
 
     def _color_depth(self, index):
         color = _imread_rgb(self.color_paths[index])
@@ -102,6 +129,9 @@ class BaseDataset(torch.utils.data.Dataset):
         return pose
 
     def __getitem__(self, index):
+        if self._on_device():
+            color, depth = self._prepare_device(_imread_rgb(self.color_paths[index]), _imread_depth(self.depth_paths[index]))
+            return index, color, depth, self._pose(index).to(self.device)
         color, depth = self._color_depth(index)
         color, depth, _ = self._crop(color, depth)
         return index, color.to(self.device), depth.to(self.device), self._pose(index).to(self.device)
@@ -135,6 +165,11 @@ class Replica_event(Replica):
         assert self.n_event == self.n_img - 1, "Number of GT events does not match that of GT images!"
 
     def __getitem__(self, index):
+        if self._on_device():                                       # the event image keeps its lens model here (as below)
+            event = _imread_rgb(self.event_paths[index - 1]) if index >= 1 else None
+            color, depth, event, mask = self._prepare_device(_imread_rgb(self.color_paths[index]),
+                                                             _imread_depth(self.depth_paths[index]), event, events=True)
+            return index, color, depth, event, mask, self._pose(index).to(self.device)
         color, depth = self._color_depth(index)
         H, W = depth.shape
         if index >= 1:
@@ -209,11 +244,20 @@ class RPG_event(RPG):
         assert self.n_event == self.n_img - 1, "Number of GT events does not match that of GT images!"
 
     def __getitem__(self, index):
+        return self._frame(index, index)
+
+    def _frame(self, index, image):
+        """Item `index`: events of interval index - 1, colour and depth of image number `image`."""
         from PIL import Image
-        with Image.open(self.color_paths[index]) as im:
+        with Image.open(self.color_paths[image]) as im:
             grey = np.array(im.convert('L'))                        # cv2.IMREAD_GRAYSCALE, then GRAY2BGR (:252-253)
+        if self._on_device():
+            event = _imread_rgb(self.event_paths[index - 1]) if index >= 1 else None
+            color, depth, event, mask = self._prepare_device(grey, _imread_depth(self.depth_paths[image]), event, events=True,
+                                                             event_order='rpg', undistort_events=True)
+            return index, color, depth, event, mask, self._pose(index).to(self.device)
         color = np.repeat(grey[:, :, None], 3, axis=2)
-        depth = _imread_depth(self.depth_paths[index]).astype(np.float32) / self.png_depth_scale
+        depth = _imread_depth(self.depth_paths[image]).astype(np.float32) / self.png_depth_scale
         event = _imread_rgb(self.event_paths[index - 1]) if index >= 1 else np.zeros_like(color)    # RGB = (+, -, 0)
         if self.distortion is not None:                             # colour and events, not the depth (:262-266)
             K = (self.fx, self.fy, self.cx, self.cy)
@@ -230,7 +274,169 @@ class RPG_event(RPG):
                 self._pose(index).to(self.device))
 
 
-dataset_dict = {"replica": Replica, "replica_event": Replica_event, "rpg": RPG, "rpg_event": RPG_event}
+class RPG_event_dense(RPG):
+    """src/utils/datasets.py:321-423: `RPG_event` with `data.density` event frames per image interval.  Item i carries the
+    events of interval i - 1 and the pose of line i of traj_density{density}.txt; its colour and depth are those of image
+    i // density (meant to be used where i % density == 0, a placeholder in between)."""
+
+    def __init__(self, cfg, args, scale, device='cuda:0'):
+        super().__init__(cfg, args, scale, device)
+        self.event_folder = cfg['data']['event_folder'] if getattr(args, 'event_folder', None) is None else args.event_folder
+        self.event_paths = sorted(glob.glob(f'{self.event_folder}/*.png'))
+        self.density = int(cfg['data']['density'])
+        self.n_event = len(self.event_paths)
+        assert self.n_event == (self.n_img - 1) * self.density, "Number of GT events does not match that of GT images!"
+        with open(f'{self.input_folder}/traj_density{self.density}.txt', "r") as f:
+            lines = f.readlines()
+        assert len(lines) == self.n_event + 1, "Number of GT events does not match that of GT poses!"
+        self.poses = []                                             # one per event frame, in place of traj.txt's
+        for line in lines:
+            c2w = np.array(line.split(), dtype=np.float64).reshape(4, 4)
+            c2w[:3, 1] *= -1
+            c2w[:3, 2] *= -1
+            self.poses.append(torch.from_numpy(c2w).float())
+
+    _frame = RPG_event._frame
+
+    def __len__(self):
+        return self.n_event + 1
+
+    def __getitem__(self, index):
+        return self._frame(index, index // self.density)
+
+
+class Azure(BaseDataset):
+    """src/utils/datasets.py:425-463: color/*.jpg, depth/*.png and scene/trajectory.log -- records of five lines, a header
+    (source, target, fitness) and the four rows of a camera-to-world matrix; identity poses when the file is absent."""
+
+    def __init__(self, cfg, args, scale, device='cuda:0'):
+        super().__init__(cfg, args, scale, device)
+        self.color_paths = sorted(glob.glob(os.path.join(self.input_folder, 'color', '*.jpg')))
+        self.depth_paths = sorted(glob.glob(os.path.join(self.input_folder, 'depth', '*.png')))
+        self.n_img = len(self.color_paths)
+        self.load_poses(os.path.join(self.input_folder, 'scene', 'trajectory.log'))
+
+    def load_poses(self, path):
+        self.poses = []
+        if not os.path.exists(path):
+            self.poses = [torch.eye(4) for _ in range(self.n_img)]
+            return
+        with open(path) as f:
+            lines = f.readlines()
+        for i in range(0, len(lines) - 4, 5):
+            c2w = np.array(' '.join(lines[i + 1:i + 5]).split(), dtype=np.float64).reshape(4, 4)
+            c2w[:3, 1] *= -1
+            c2w[:3, 2] *= -1
+            self.poses.append(torch.from_numpy(c2w).float())
+
+
+def _numbered(pattern):
+    """files matching `pattern` in the order of the integer their name starts with (2.jpg before 10.jpg)"""
+    return sorted(glob.glob(pattern), key=lambda x: int(os.path.splitext(os.path.basename(x))[0]))
+
+
+class ScanNet(BaseDataset):
+    """src/utils/datasets.py:466-493: frames/color/<n>.jpg, frames/depth/<n>.png, frames/pose/<n>.txt (a 4x4 per file)."""
+
+    def __init__(self, cfg, args, scale, device='cuda:0'):
+        super().__init__(cfg, args, scale, device)
+        self.input_folder = os.path.join(self.input_folder, 'frames')
+        self.color_paths = _numbered(os.path.join(self.input_folder, 'color', '*.jpg'))
+        self.depth_paths = _numbered(os.path.join(self.input_folder, 'depth', '*.png'))
+        self.n_img = len(self.color_paths)
+        self.poses = []
+        for path in _numbered(os.path.join(self.input_folder, 'pose', '*.txt')):
+            with open(path, "r") as f:
+                c2w = np.array(f.read().split(), dtype=np.float64).reshape(4, 4)
+            c2w[:3, 1] *= -1
+            c2w[:3, 2] *= -1
+            self.poses.append(torch.from_numpy(c2w).float())
+
+
+def quaternion_matrix(q):
+    """3x3 rotation of the quaternion (x, y, z, w), normalised first (scipy's Rotation.from_quat(q).as_matrix())."""
+    x, y, z, w = np.asarray(q, dtype=np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def matrix_quaternion(R):
+    """(x, y, z, w), w >= 0, of a 3x3 rotation: the inverse of `quaternion_matrix` (the sequence writers)."""
+    R = np.asarray(R, dtype=np.float64)
+    d = np.array([R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2], R[2, 2] - R[0, 0] - R[1, 1],
+                  R[0, 0] + R[1, 1] + R[2, 2]])                     # 4 q_i^2 - 1
+    k = int(np.argmax(d))                                           # the largest component: safe to divide by
+    q = np.zeros(4)
+    q[k] = np.sqrt(1 + d[k]) / 2
+    prod = {(0, 1): R[0, 1] + R[1, 0], (0, 2): R[0, 2] + R[2, 0], (1, 2): R[1, 2] + R[2, 1],
+            (0, 3): R[2, 1] - R[1, 2], (1, 3): R[0, 2] - R[2, 0], (2, 3): R[1, 0] - R[0, 1]}      # 4 q_i q_j
+    for i in range(4):
+        if i != k:
+            q[i] = prod[(min(i, k), max(i, k))] / (4 * q[k])
+    return q if q[3] >= 0 else -q
+
+
+class TUM_RGBD(BaseDataset):
+    """src/utils/datasets.py:519-606: rgb.txt and depth.txt (time stamp, file), groundtruth.txt or pose.txt (time stamp, t,
+    q_xyzw; its first line is skipped as in the reference).  Every colour stamp takes the depth and the pose nearest in time
+    and is dropped unless both lie within max_dt = 0.08 s; the survivors are thinned so that consecutive frames are more than
+    1 / frame_rate = 1 / 32 s apart; poses are relative to the first kept frame."""
+
+    def __init__(self, cfg, args, scale, device='cuda:0'):
+        super().__init__(cfg, args, scale, device)
+        self.color_paths, self.depth_paths, self.poses = self.loadtum(self.input_folder, frame_rate=32)
+        self.n_img = len(self.color_paths)
+
+    @staticmethod
+    def parse_list(path, skiprows=0):
+        """rows of a space-separated list as strings; '#' starts a comment (np.loadtxt(dtype=str) of the reference)"""
+        with open(path) as f:
+            lines = f.readlines()[skiprows:]
+        rows = [ln.split('#', 1)[0].split() for ln in lines]
+        return np.array([r for r in rows if r], dtype=str)
+
+    @staticmethod
+    def associate_frames(t_image, t_depth, t_pose, max_dt=0.08):
+        out = []
+        for i, t in enumerate(t_image):
+            j, k = int(np.argmin(np.abs(t_depth - t))), int(np.argmin(np.abs(t_pose - t)))
+            if np.abs(t_depth[j] - t) < max_dt and np.abs(t_pose[k] - t) < max_dt:
+                out.append((i, j, k))
+        return out
+
+    def loadtum(self, root, frame_rate=-1):
+        pose_list = os.path.join(root, 'groundtruth.txt')
+        if not os.path.isfile(pose_list):
+            pose_list = os.path.join(root, 'pose.txt')
+        images, depths = self.parse_list(os.path.join(root, 'rgb.txt')), self.parse_list(os.path.join(root, 'depth.txt'))
+        pose_rows = self.parse_list(pose_list, skiprows=1)
+        t_image, t_depth = images[:, 0].astype(np.float64), depths[:, 0].astype(np.float64)
+        t_pose, vecs = pose_rows[:, 0].astype(np.float64), pose_rows[:, 1:].astype(np.float64)
+        assoc = self.associate_frames(t_image, t_depth, t_pose)
+        keep = [0]
+        for a in range(1, len(assoc)):
+            if t_image[assoc[a][0]] - t_image[assoc[keep[-1]][0]] > 1.0 / frame_rate:
+                keep.append(a)
+        color_paths, depth_paths, poses, first_inv = [], [], [], None
+        for a in keep:
+            i, j, k = assoc[a]
+            color_paths.append(os.path.join(root, images[i, 1]))
+            depth_paths.append(os.path.join(root, depths[j, 1]))
+            c2w = np.eye(4)
+            c2w[:3, :3], c2w[:3, 3] = quaternion_matrix(vecs[k, 3:]), vecs[k, :3]
+            if first_inv is None:
+                first_inv, c2w = np.linalg.inv(c2w), np.eye(4)
+            else:
+                c2w = first_inv @ c2w
+            c2w[:3, 1] *= -1
+            c2w[:3, 2] *= -1
+            poses.append(torch.from_numpy(c2w).float())
+        return color_paths, depth_paths, poses
+
+
+dataset_dict = {"replica": Replica, "replica_event": Replica_event, "rpg": RPG, "rpg_event": RPG_event,
+                "rpg_event_dense": RPG_event_dense, "tumrgbd": TUM_RGBD, "scannet": ScanNet, "azure": Azure}
 
 
 def write_rpg_event_sequence(root, frames, poses, png_depth_scale, events):
@@ -281,3 +487,110 @@ def write_replica_event_sequence(root, frames, poses, png_depth_scale, events=No
             rgb[..., 1:] = ev
             Image.fromarray(rgb, 'RGB').save(os.path.join(evf, f'event_frame{i + 1:06d}.png'))
     return inp, evf
+
+
+def _color_u8(color):
+    a = np.asarray(color)
+    return a if a.dtype == np.uint8 else np.clip(np.rint(a.astype(np.float64) * 255.), 0, 255).astype(np.uint8)
+
+
+def _depth_u16(depth, png_depth_scale):
+    return np.clip(np.rint(np.asarray(depth, dtype=np.float64) * png_depth_scale), 0, 65535).astype(np.uint16)
+
+
+def _opencv_pose(pose):
+    """a camera-to-world in the readers' convention -> the file's (the y / z column flip undone)"""
+    p = np.array(pose, dtype=np.float64).reshape(4, 4).copy()
+    p[:3, 1] *= -1
+    p[:3, 2] *= -1
+    return p
+
+
+def _save_color(c8, path):
+    from PIL import Image
+    im = Image.fromarray(c8, 'RGB') if c8.ndim == 3 else Image.fromarray(c8, 'L')
+    if path.endswith('.jpg'):
+        im.save(path, quality=100, subsampling=0)
+    else:
+        im.save(path)
+
+
+def write_rpg_event_dense_sequence(root, frames, poses, png_depth_scale, events, density):
+    """The RPG_event_dense layout: `write_rpg_event_sequence` with len(events) = (len(frames) - 1) * density event pngs and
+    len(events) + 1 poses (one per event frame, the readers' convention) in traj_density{density}.txt.  traj.txt holds the
+    poses of the images (every density-th).  Returns (input_folder, event_folder)."""
+    assert len(events) == (len(frames) - 1) * density and len(poses) == len(events) + 1
+    inp, evf = write_rpg_event_sequence(root, frames, poses[::density], png_depth_scale, events)
+    with open(os.path.join(inp, f'traj_density{density}.txt'), 'w') as f:
+        for pose in poses:
+            f.write(' '.join(repr(float(v)) for v in _opencv_pose(pose).reshape(-1)) + '\n')
+    return inp, evf
+
+
+def write_tum_sequence(root, frames, poses, png_depth_scale, stamps=None, depth_stamps=None, pose_stamps=None,
+                       pose_file='groundtruth.txt'):
+    """The TUM RGB-D layout: rgb/<stamp>.png, depth/<stamp>.png, rgb.txt, depth.txt and `pose_file` (stamp tx ty tz qx qy qz
+    qw), each list under the three comment lines of the original files.  frames: list of (colour, depth metres); poses:
+    camera-to-world in the readers' convention, one per entry of pose_stamps (default: one per frame at the colour stamps;
+    TUM_RGBD hands them out relative to the first kept frame).  stamps / depth_stamps: seconds, default 0.1 s apart /
+    the colour stamps; an entry of None in depth_stamps leaves that depth image out.  Returns the input folder."""
+    from PIL import Image
+    inp = os.path.join(root, 'seq')
+    os.makedirs(os.path.join(inp, 'rgb'), exist_ok=True)
+    os.makedirs(os.path.join(inp, 'depth'), exist_ok=True)
+    stamps = [1.0 + 0.1 * i for i in range(len(frames))] if stamps is None else list(stamps)
+    depth_stamps = stamps if depth_stamps is None else list(depth_stamps)
+    pose_stamps = stamps if pose_stamps is None else list(pose_stamps)
+    head = '# {}\n# file: synthetic\n# {}\n'
+    with open(os.path.join(inp, 'rgb.txt'), 'w') as fc, open(os.path.join(inp, 'depth.txt'), 'w') as fd:
+        fc.write(head.format('color images', 'timestamp filename'))
+        fd.write(head.format('depth maps', 'timestamp filename'))
+        for (color, depth), tc, td in zip(frames, stamps, depth_stamps):
+            _save_color(_color_u8(color), os.path.join(inp, 'rgb', f'{tc:.6f}.png'))
+            fc.write(f'{tc:.6f} rgb/{tc:.6f}.png\n')
+            if td is not None:
+                Image.fromarray(_depth_u16(depth, png_depth_scale)).save(os.path.join(inp, 'depth', f'{td:.6f}.png'))
+                fd.write(f'{td:.6f} depth/{td:.6f}.png\n')
+    with open(os.path.join(inp, pose_file), 'w') as f:
+        f.write(head.format('ground truth trajectory', 'timestamp tx ty tz qx qy qz qw'))
+        for pose, t in zip(poses, pose_stamps):
+            p = _opencv_pose(pose)
+            f.write(f'{t:.6f} ' + ' '.join(repr(float(v)) for v in list(p[:3, 3]) + list(matrix_quaternion(p[:3, :3]))) + '\n')
+    return inp
+
+
+def write_scannet_sequence(root, frames, poses, png_depth_scale, numbers=None):
+    """The ScanNet layout: frames/color/<n>.jpg, frames/depth/<n>.png, frames/pose/<n>.txt with n = numbers[i] (default i, no
+    zero padding: the reader orders by the integer).  The colour may be larger than the depth.  Returns the input folder."""
+    from PIL import Image
+    inp = os.path.join(root, 'seq')
+    for sub in ('color', 'depth', 'pose'):
+        os.makedirs(os.path.join(inp, 'frames', sub), exist_ok=True)
+    numbers = list(range(len(frames))) if numbers is None else list(numbers)
+    for n, (color, depth), pose in zip(numbers, frames, poses):
+        _save_color(_color_u8(color), os.path.join(inp, 'frames', 'color', f'{n}.jpg'))
+        Image.fromarray(_depth_u16(depth, png_depth_scale)).save(os.path.join(inp, 'frames', 'depth', f'{n}.png'))
+        with open(os.path.join(inp, 'frames', 'pose', f'{n}.txt'), 'w') as f:
+            for row in _opencv_pose(pose):
+                f.write(' '.join(repr(float(v)) for v in row) + '\n')
+    return inp
+
+
+def write_azure_sequence(root, frames, poses, png_depth_scale):
+    """The Azure layout: color/<i>.jpg, depth/<i>.png and, unless poses is None, scene/trajectory.log in five-line records.
+    Returns the input folder."""
+    from PIL import Image
+    inp = os.path.join(root, 'seq')
+    for sub in ('color', 'depth'):
+        os.makedirs(os.path.join(inp, sub), exist_ok=True)
+    for i, (color, depth) in enumerate(frames):
+        _save_color(_color_u8(color), os.path.join(inp, 'color', f'{i:06d}.jpg'))
+        Image.fromarray(_depth_u16(depth, png_depth_scale)).save(os.path.join(inp, 'depth', f'{i:06d}.png'))
+    if poses is not None:
+        os.makedirs(os.path.join(inp, 'scene'), exist_ok=True)
+        with open(os.path.join(inp, 'scene', 'trajectory.log'), 'w') as f:
+            for i, pose in enumerate(poses):
+                f.write(f'{i} {i} {i + 1}\n')
+                for row in _opencv_pose(pose):
+                    f.write(' '.join(repr(float(v)) for v in row) + '\n')
+    return inp

@@ -2109,6 +2109,104 @@ def mesh_depth(vertices, faces, w2c, cam, z_near=0.0, z_far=20.0):
 
 
 # ------------------------------------------------------------------------------------------------
+# Frame preparation (csrc/frame_prep.hip): raw decoded images -> the tensors of the dataset readers
+# ------------------------------------------------------------------------------------------------
+EVENT_ORDERS = {'replica': (1, 2), 'rpg': (1, 0)}     # (channel of -, channel of +) in the event png: (0,-,+) / (+,-,0)
+
+
+def frame_plan(color_shape, depth_shape, depth_int32, event_shape=None, K=None, distortion=None, png_depth_scale=1.0, scale=1.0,
+               crop_size=None, crop_edge=0, event_order='replica', undistort_events=True):
+    """The enslam_frame_plan of one frame layout (host arithmetic only; `frame_prepare` documents the arguments)."""
+    if len(color_shape) == 2:
+        color_shape = tuple(color_shape) + (1,)
+    if len(color_shape) != 3 or len(depth_shape) != 2 or (event_shape is not None and (len(event_shape) != 3 or event_shape[2] != 3)):
+        raise L.EnslamError(f"frame_prepare: colour must be [h,w] or [h,w,C], depth [H,W], events [h,w,3] (got {tuple(color_shape)}, "
+                            f"{tuple(depth_shape)}, {None if event_shape is None else tuple(event_shape)})")
+    if event_order not in EVENT_ORDERS:
+        raise L.EnslamError(f"frame_prepare: event_order must be one of {sorted(EVENT_ORDERS)} (got {event_order!r})")
+    p = L.FramePlan()
+    p.h0, p.w0, p.channels = (int(v) for v in color_shape)
+    p.he, p.we = (int(event_shape[0]), int(event_shape[1])) if event_shape is not None else (0, 0)
+    p.H, p.W = int(depth_shape[0]), int(depth_shape[1])
+    p.depth_int32 = int(bool(depth_int32))
+    p.has_dist = int(distortion is not None)
+    p.undistort_events = int(bool(undistort_events))
+    if distortion is not None:
+        if K is None:
+            raise L.EnslamError("frame_prepare: a lens model needs the intrinsics K = (fx, fy, cx, cy)")
+        p.fx, p.fy, p.cx, p.cy = (float(v) for v in K)
+        d = [float(v) for v in distortion][:8]
+        for i, v in enumerate(d):
+            p.dist[i] = v
+    p.crop_h, p.crop_w = (int(crop_size[0]), int(crop_size[1])) if crop_size is not None else (0, 0)
+    p.crop_edge = int(crop_edge)
+    p.ev_neg, p.ev_pos = EVENT_ORDERS[event_order]
+    p.png_depth_scale, p.scale = float(png_depth_scale), float(scale)
+    return p
+
+
+def _raw_image(a, device, what, dtypes):
+    """numpy array or tensor -> contiguous tensor on `device` (a numpy array is uploaded as it is: the raw bytes)."""
+    if not torch.is_tensor(a):
+        import numpy as np
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.uint16:                      # torch has no arithmetic on uint16: the bits travel as int16
+            a = a.view(np.int16)
+        a = torch.from_numpy(a)
+    if a.dtype not in dtypes:
+        raise L.EnslamError(f"frame_prepare: {what} must be one of {[str(d) for d in dtypes]} (got {a.dtype})")
+    return a.to(device).contiguous()
+
+
+def frame_prepare(color, depth, event=None, events=False, K=None, distortion=None, png_depth_scale=1.0, scale=1.0, crop_size=None,
+                  crop_edge=0, event_order='replica', undistort_events=True, device=None):
+    """One frame from raw decoded images to what the dataset readers hand out, in one launch (enslam_frame_prepare,
+    enslam_hip.h): the device route of `datasets.BaseDataset` / `Replica_event` / `RPG_event`.
+
+      color   uint8 [h0,w0,3], or grey [h0,w0] / [h0,w0,1] (replicated to three channels)
+      depth   uint16 or int32 [H,W] (a tensor carries uint16 as the bits of an int16)
+      event   uint8 [he,we,3] or None; `events=True` (implied by an event image) asks for the event outputs: without an
+              image they are all zero (frame 0)
+    numpy arrays are uploaded to `device` (default: the current HIP device), tensors must already live on a HIP device.
+    K = (fx, fy, cx, cy) and distortion (k1, k2, p1, p2[, k3[, k4, k5, k6]]) remove the lens model from the colour image
+    and, with undistort_events, from the event image -- never from the depth.  event_order: 'replica' for pngs with
+    channels (0, -, +), 'rpg' for (+, -, 0).
+
+    Returns (color float64 [H',W',3], depth float32 [H',W']) or, with events, (color, depth, event [H',W',2] = (-, +) --
+    uint8 without crop_size, float32 with it --, mask int64 [H',W'])."""
+    lib = L.lib()
+    tensors = [t for t in (color, depth, event) if torch.is_tensor(t)]
+    if device is None:
+        device = tensors[0].device if tensors else torch.device('cuda', torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise L.EnslamError(f"frame_prepare runs on a HIP device (got {device}); the host route is datasets.BaseDataset with "
+                            f"prepare='host'")
+    for t in tensors:
+        _require_hip(t, "frame_prepare: a raw image tensor")
+    c = _raw_image(color, device, "colour", (torch.uint8,))
+    d = _raw_image(depth, device, "depth", (torch.int16, torch.int32) + ((torch.uint16,) if hasattr(torch, 'uint16') else ()))
+    e = _raw_image(event, device, "events", (torch.uint8,)) if event is not None else None
+    plan = frame_plan(tuple(c.shape), tuple(d.shape), d.dtype is torch.int32, None if e is None else tuple(e.shape), K, distortion,
+                      png_depth_scale, scale, crop_size, crop_edge, event_order, undistort_events)
+    Hs, Ws = (plan.crop_h, plan.crop_w) if plan.crop_h > 0 else (plan.H, plan.W)
+    Ho, Wo = max(Hs - 2 * plan.crop_edge, 0), max(Ws - 2 * plan.crop_edge, 0)
+    want_events = events or e is not None
+    with torch.cuda.device(device):
+        color_out = torch.empty((Ho, Wo, 3), dtype=torch.float64, device=device)
+        depth_out = torch.empty((Ho, Wo), dtype=torch.float32, device=device)
+        event_out = mask_out = None
+        if want_events:
+            event_out = torch.empty((Ho, Wo, 2), dtype=torch.float32 if plan.crop_h > 0 else torch.uint8, device=device)
+            mask_out = torch.empty((Ho, Wo), dtype=torch.int64, device=device)
+        L.check(lib.enslam_frame_prepare(ctypes.byref(plan), _ptr(c), _ptr(d), _ptr(e), _ptr(color_out), _ptr(depth_out),
+                                         _ptr(event_out), _ptr(mask_out), _stream()), "enslam_frame_prepare")
+    if want_events:
+        return color_out, depth_out, event_out, mask_out
+    return color_out, depth_out
+
+
+# ------------------------------------------------------------------------------------------------
 # iMAP mode (configs/imap.yaml): the 256-wide decoder (csrc/imap_mlp.hip) and density compositing
 # ------------------------------------------------------------------------------------------------
 IMAP_WS_LIMIT_BYTES = 1 << 30     # the backward's workspace per launch; larger point sets run in chunks

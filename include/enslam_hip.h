@@ -490,6 +490,48 @@ int enslam_mesh_depth(const double *vertices, int32_t n_verts, const int32_t *fa
                       int32_t n_views, int32_t H, int32_t W, double fx, double fy, double cx, double cy, double z_near,
                       double z_far, void *workspace, float *depth_out, void *stream);
 
+/* Frame preparation (the per-frame work of src/utils/datasets.py between the image decoders and the tracker): one launch
+ * turns the raw decoded images of one frame into the tensors the readers hand out.
+ *   color_raw  uint8 [h0,w0,C], C = 3 or C = 1 (grey, replicated to three channels)
+ *   depth_raw  uint16 (depth_int32 = 0) or int32 (depth_int32 = 1) [H,W]
+ *   event_raw  uint8 [he,we,3] or NULL (frame 0: all-zero events and mask)
+ *   color_out  float64 [H',W',3]; depth_out float32 [H',W']; mask_out int64 [H',W'];
+ *   event_out  [H',W',2] = (-, +): uint8 without crop_size, float32 with it; NULL (with mask_out NULL): no event outputs
+ *   (H',W') = (crop_h, crop_w) when crop_h > 0, else (H, W), less crop_edge on every side.
+ * Stages, in the order and precision of the host route (datasets.py):
+ *   1 undistort (has_dist: colour; undistort_events: the event image too; never the depth): per destination pixel the
+ *     inverse map of OpenCV's rational-radial + tangential model in float64, bilinear taps with a zero border in float64,
+ *     one round-half-to-even to uint8
+ *   2 colour / 255., then a half-pixel-centre bilinear resize to (H,W) in float64 when (h0,w0) differs
+ *   3 events: the same resize from (he,we), rounded half-to-even to uint8
+ *   4 crop_size: colour bilinear align_corners in float64, events the same in float32, depth torch's `nearest`
+ *   5 the crop_edge cut
+ *   6 depth = float32(raw) / float32(png_depth_scale) * float32(scale), two float32 operations
+ *   7 mask = any event channel != 0
+ * ev_neg / ev_pos: the channels of event_raw that hold the negative / positive events (1, 2 for Replica's (0,-,+) pngs,
+ * 1, 0 for RPG's (+,-,0)).  ENSLAM_EINVAL without a launch: a NULL plan / colour / depth pointer, event_out without
+ * mask_out (or the reverse), C not 1 or 3, a size < 1, an event channel outside 0..2, a crop_edge that leaves no pixel,
+ * non-finite or zero intrinsics with has_dist, a png_depth_scale of 0.  More than 2^28 pixels in any image:
+ * ENSLAM_EUNSUPPORTED. */
+typedef struct enslam_frame_plan {
+    int32_t h0, w0, channels;       /* raw colour image */
+    int32_t he, we;                 /* raw event image (ignored when event_raw is NULL) */
+    int32_t H, W;                   /* raw depth image */
+    int32_t depth_int32;
+    int32_t has_dist, undistort_events;
+    int32_t crop_h, crop_w;         /* cam.crop_size, 0 0 for none */
+    int32_t crop_edge;
+    int32_t ev_neg, ev_pos;
+    int32_t reserved;
+    double fx, fy, cx, cy;
+    double dist[8];                 /* k1 k2 p1 p2 k3 k4 k5 k6 */
+    double png_depth_scale, scale;
+} enslam_frame_plan;
+int64_t enslam_frame_plan_bytes(void);               /* sizeof(enslam_frame_plan): binding self-check */
+int enslam_frame_prepare(const enslam_frame_plan *plan, const uint8_t *color_raw, const void *depth_raw,
+                         const uint8_t *event_raw, double *color_out, float *depth_out, void *event_out,
+                         int64_t *mask_out, void *stream);
+
 /* Hand-derived backward of enslam_render_fwd (replaces autograd of the reference ops).
  *   g_depth float64 [N], g_var float64 [N] or NULL, g_rgb float32 [N,3] or NULL
  *   grad_grids[k].data : voxel-major accumulators (caller-zeroed) or NULL to skip that grid
