@@ -166,6 +166,17 @@ _SIGS = {
     "enslam_frame_plan_bytes": (c_int64, []),
     "enslam_frame_prepare": (ctypes.c_int, [POINTER(FramePlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),
+    "enslam_tsdf_touch": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_double), POINTER(c_double), c_double,
+                                         c_double, POINTER(c_int32), POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p]),
+    "enslam_tsdf_integrate": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_double), POINTER(c_double),
+                                             c_double, c_double, POINTER(c_int32), POINTER(c_int32), c_int32, c_void_p, c_void_p,
+                                             c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_tsdf_mesh_workspace": (ctypes.c_int, [c_int32, POINTER(c_int64)]),
+    "enslam_tsdf_mesh_count": (ctypes.c_int, [c_void_p, POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p]),
+    "enslam_tsdf_mesh_emit": (ctypes.c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_double, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
     "enslam_render_bwd": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(Scene),
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(Grid),
                                          POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,

@@ -2109,6 +2109,79 @@ def mesh_depth(vertices, faces, w2c, cam, z_near=0.0, z_far=20.0):
 
 
 # ------------------------------------------------------------------------------------------------
+# Block-sparse TSDF volume (csrc/tsdf.hip): the raw calls; tsdf.TSDFVolume holds the arrays and allocates
+# ------------------------------------------------------------------------------------------------
+def _i32x3(v):
+    return (ctypes.c_int32 * 3)(*[int(x) for x in v])
+
+
+def _pose12(m):
+    """host float64 [12]: the upper three rows of a [3|4,4] matrix (numpy)."""
+    return (ctypes.c_double * 12)(*[float(x) for x in m[:3].reshape(-1)])
+
+
+def _cam4(cam):
+    return (ctypes.c_double * 4)(float(cam['fx']), float(cam['fy']), float(cam['cx']), float(cam['cy']))
+
+
+def tsdf_touch(depth, c2w, cam, stride, sdf_trunc, voxel_length, unit_lo, nu, stamp, stamps):
+    """Stamp the units within sdf_trunc of the frame's sampled depth pixels (enslam_tsdf_touch).  depth float32 [H,W] on the
+    HIP device, c2w float64 numpy [3|4,4], stamps int32 [nu0*nu1*nu2].  Returns the per-workgroup counts (int32 device
+    tensor) of pixels that reached outside the table."""
+    lib = L.lib()
+    H, W = int(cam['H']), int(cam['W'])
+    if depth.dtype is not torch.float32 or tuple(depth.shape) != (H, W) or not depth.is_contiguous():
+        raise L.EnslamError(f"depth must be contiguous float32 [{H},{W}] (got {depth.dtype} {tuple(depth.shape)})")
+    ns = -(-H // int(stride)) * -(-W // int(stride))
+    outside = torch.empty(-(-ns // 256), dtype=torch.int32, device=depth.device)
+    with torch.cuda.device(depth.device):
+        L.check(lib.enslam_tsdf_touch(_ptr(depth), H, W, int(stride), _cam4(cam), _pose12(c2w), float(sdf_trunc),
+                                      float(voxel_length), _i32x3(unit_lo), _i32x3(nu), int(stamp), _ptr(stamps), _ptr(outside),
+                                      _stream()), "enslam_tsdf_touch")
+    return outside
+
+
+def tsdf_integrate(depth, color, mult, w2c, cam, voxel_length, sdf_trunc, unit_lo, nu, touched_block, touched_index, n_blocks,
+                   tsdf, weight, vcolor):
+    """Fuse one frame into the touched blocks (enslam_tsdf_integrate); returns the per-(block, slab) counts of updated voxels
+    (int32 device tensor [n_touched * 16])."""
+    lib = L.lib()
+    H, W = int(cam['H']), int(cam['W'])
+    n = int(touched_block.shape[0])
+    counts = torch.empty(n * 16, dtype=torch.int32, device=depth.device)
+    with torch.cuda.device(depth.device):
+        L.check(lib.enslam_tsdf_integrate(_ptr(depth), _ptr(color), _ptr(mult), H, W, _cam4(cam), _pose12(w2c), float(voxel_length),
+                                          float(sdf_trunc), _i32x3(unit_lo), _i32x3(nu), n, _ptr(touched_block), _ptr(touched_index),
+                                          int(n_blocks), _ptr(tsdf), _ptr(weight), _ptr(vcolor), _ptr(counts), _stream()),
+                "enslam_tsdf_integrate")
+    return counts
+
+
+def tsdf_mesh(table, unit_lo, nu, n_blocks, sorted_block, sorted_index, tsdf, weight, vcolor, voxel_length):
+    """(vertices float64 [V,3], faces int32 [F,3], colors uint8 [V,3] or None) of the zero level of a block-sparse TSDF volume
+    (enslam_tsdf_mesh_count / _emit; conventions: enslam_hip.h).  One host synchronisation: the counts."""
+    lib = L.lib()
+    dev = table.device
+    with torch.cuda.device(dev):
+        nbytes = ctypes.c_int64()
+        L.check(lib.enslam_tsdf_mesh_workspace(int(n_blocks), ctypes.byref(nbytes)), "enslam_tsdf_mesh_workspace")
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        L.check(lib.enslam_tsdf_mesh_count(_ptr(table), _i32x3(nu), int(n_blocks), _ptr(sorted_block), _ptr(sorted_index),
+                                           _ptr(tsdf), _ptr(weight), _ptr(ws), _ptr(counts), _stream()), "enslam_tsdf_mesh_count")
+        n_verts, n_faces = counts.tolist()
+        verts = torch.empty((n_verts, 3), dtype=torch.float64, device=dev)
+        faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+        colors = torch.empty((n_verts, 3), dtype=torch.uint8, device=dev) if vcolor is not None else None
+        L.check(lib.enslam_tsdf_mesh_emit(_ptr(table), _i32x3(unit_lo), _i32x3(nu), int(n_blocks), _ptr(sorted_block),
+                                          _ptr(sorted_index), _ptr(tsdf), _ptr(weight), _ptr(vcolor), float(voxel_length), _ptr(ws),
+                                          n_verts, n_faces, _ptr(verts) if n_verts else None, _ptr(faces) if n_faces else None,
+                                          _ptr(colors) if colors is not None and n_verts else None, _stream()),
+                "enslam_tsdf_mesh_emit")
+    return verts, faces, colors
+
+
+# ------------------------------------------------------------------------------------------------
 # Frame preparation (csrc/frame_prep.hip): raw decoded images -> the tensors of the dataset readers
 # ------------------------------------------------------------------------------------------------
 EVENT_ORDERS = {'replica': (1, 2), 'rpg': (1, 0)}     # (channel of -, channel of +) in the event png: (0,-,+) / (+,-,0)

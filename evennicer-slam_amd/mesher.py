@@ -5,9 +5,14 @@ open3d are not needed.
 
 Numerical differences from the reference:
   * inside mask: the reference fuses the keyframes into a TSDF (open3d) and keeps the lattice points inside the convex hull
-    of that mesh and the camera centres, scaled by `clean_mesh_bound_scale`.  Here the hull is taken of the keyframes'
-    back-projected valid depth pixels and the camera centres (scipy.spatial.ConvexHull), scaled the same way about the
-    mean of its vertices, and tested against the lattice by its half-spaces on the GPU;
+    of that mesh and the camera centres, scaled by `clean_mesh_bound_scale`.  `bound_method` selects how the hull's points
+    are made.  'depth_points' (the default): the keyframes' back-projected valid depth pixels and the camera centres.
+    'tsdf' (HIP device only): the reference's way -- the keyframes fused into a block-sparse TSDF volume with its
+    voxel_length 4 * scale / 512 and sdf_trunc 0.04 * scale (tsdf.TSDFVolume, csrc/tsdf.hip), the vertices of that volume's
+    mesh and the camera centres, thinned by `hull_candidates` before scipy sees them.  What still differs from Open3D
+    there: float64 per-voxel geometry, a deterministic output order, a table-bounded volume sized from the frames.  Either
+    way the hull (scipy.spatial.ConvexHull) is scaled about the mean of its vertices and tested against the lattice by
+    its half-spaces on the GPU;
   * faces: the case table resolves ambiguous cube faces by one fixed rule (csrc/mc_tables.hpp), skimage by the Lewiner
     table, so face sets may differ in ambiguous cells; the vertex set does not;
   * order: after cleaning, the kept faces keep their marching-cubes order and the vertices their order, where trimesh
@@ -30,7 +35,9 @@ from . import functional as EF
 # configs/nice_slam.yaml `meshing` (the reference's defaults), for callers whose config has no such section
 MESHING_DEFAULTS = dict(level_set=0, resolution=256, eval_rec=False, clean_mesh=True, depth_test=False, mesh_coarse_level=False,
                         clean_mesh_bound_scale=1.02, get_largest_components=False,
-                        color_mesh_extraction_method='direct_point_query', remove_small_geometry_threshold=0.2)
+                        color_mesh_extraction_method='direct_point_query', remove_small_geometry_threshold=0.2,
+                        bound_method='depth_points')
+BOUND_METHODS = ('depth_points', 'tsdf')
 
 
 class Mesher(object):
@@ -50,6 +57,11 @@ class Mesher(object):
         self.color_mesh_extraction_method = cfg['meshing']['color_mesh_extraction_method']
         self.get_largest_components = cfg['meshing']['get_largest_components']
         self.depth_test = cfg['meshing']['depth_test']
+        # how get_bound_from_frames makes the points of the hull (the header comment); settable after construction
+        self.bound_method = cfg['meshing'].get('bound_method', 'depth_points')
+        if self.bound_method not in BOUND_METHODS:
+            raise ValueError(f"meshing.bound_method must be one of {BOUND_METHODS} (got {self.bound_method!r})")
+        self.tsdf_stats = {}        # blocks / bytes / per-frame counts of the last 'tsdf' bound
 
         self.bound = slam.bound
         self.nice = slam.nice
@@ -155,12 +167,51 @@ class Mesher(object):
         forecast = np.concatenate(forecast_l) if forecast_l else np.zeros(0, bool)
         return seen, forecast, ~(seen | forecast)
 
-    def get_bound_from_frames(self, keyframe_dict, scale=1):
+    def get_bound_from_frames(self, keyframe_dict, scale=1, device=None):
         """Half-spaces [K,4] float64 (n . x + d <= 0 inside) of the convex hull of the keyframes' back-projected valid depth
         pixels and camera centres, scaled by clean_mesh_bound_scale about the mean of its vertices (Mesher.py:213-262
-        with the TSDF replaced by the depth points themselves)."""
+        with the TSDF replaced by the depth points themselves).  With bound_method 'tsdf' the points are the vertices of the
+        keyframes' fused TSDF mesh and the camera centres, as in the reference; `device` defaults to the keyframes'."""
+        if self.bound_method not in BOUND_METHODS:
+            raise ValueError(f"bound_method must be one of {BOUND_METHODS} (got {self.bound_method!r})")
+        if self.bound_method == 'tsdf':
+            import time
+            points = self.tsdf_bound_points(keyframe_dict, scale, device)
+            t0 = time.perf_counter()
+            halfspaces = hull_halfspaces(points, self.clean_mesh_bound_scale)
+            self.timing['hull_scipy'] = time.perf_counter() - t0
+            return halfspaces
         return hull_halfspaces(backprojected_points(keyframe_dict, self.H, self.W, self.fx, self.fy, self.cx, self.cy),
                                self.clean_mesh_bound_scale)
+
+    def tsdf_bound_points(self, keyframe_dict, scale=1, device=None):
+        """float64 numpy [P,3]: the candidates for the hull of Mesher.py:214-279 -- the keyframes' depth fused with est_c2w into a
+        TSDF volume of voxel_length 4 * scale / 512 and sdf_trunc 0.04 * scale (stride 4, no colour: the reference integrates
+        colour and never reads it), the vertices of its mesh and the camera centres, passed through hull_candidates."""
+        from .tsdf import TSDFVolume
+        if device is None:
+            device = keyframe_dict[0]['depth'].device if len(keyframe_dict) else 'cpu'
+        if torch.device(device).type != 'cuda':
+            raise NotImplementedError("bound_method 'tsdf' needs a HIP device (csrc/tsdf.hip)")
+        import time
+        cam = dict(H=self.H, W=self.W, fx=self.fx, fy=self.fy, cx=self.cx, cy=self.cy)
+        frames = [dict(depth=kf['depth'].reshape(self.H, self.W), est_c2w=kf['est_c2w']) for kf in keyframe_dict]
+        t0 = time.perf_counter()
+
+        def lap(name):                  # seconds per step of the bound, beside timing['hull'] (tools/bench_tsdf.py)
+            nonlocal t0
+            torch.cuda.synchronize(device)
+            self.timing[name] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+        vol = TSDFVolume.for_frames(frames, cam, 4.0 * scale / 512.0, 0.04 * scale, color=False, depth_sampling_stride=4, device=device)
+        lap('hull_fuse')
+        verts, _, _ = vol.extract_mesh()
+        lap('hull_extract')
+        centres = torch.stack([kf['est_c2w'].detach().double()[:3, 3] for kf in keyframe_dict]).to(verts.device)
+        points = hull_candidates(torch.cat([verts, centres])).cpu().numpy()
+        lap('hull_candidates')
+        self.tsdf_stats = dict(vol.stats, points=int(verts.shape[0]) + len(keyframe_dict), candidates=int(points.shape[0]))
+        return points
 
     # ------------------------------------------------------------------ lattice
     def get_grid_uniform(self, resolution):
@@ -231,7 +282,7 @@ class Mesher(object):
             t0 = time.perf_counter()
             xyz = self.get_grid_uniform(self.resolution)['xyz']
             views = self._views(keyframe_dict, estimate_c2w_list, idx, device, get_mask_use_all_frames) if show_forecast else None
-            halfspaces = self.get_bound_from_frames(keyframe_dict, self.scale) if clean_mesh or not show_forecast else None
+            halfspaces = self.get_bound_from_frames(keyframe_dict, self.scale, device) if clean_mesh or not show_forecast else None
             t0 = lap('hull', t0)
             if show_forecast:
                 vol, _ = self.forecast_volume(c, decoders, xyz, views, device)
@@ -375,6 +426,39 @@ def hull_halfspaces(points, scale):
     v = points[ConvexHull(points).vertices]
     center = v.mean(axis=0)
     return ConvexHull((v - center) * scale + center).equations.astype(np.float64)
+
+
+_HULL_DIRECTIONS = []
+
+
+def hull_directions():
+    """float64 numpy [70,3]: the fixed unit directions of hull_candidates -- 64 seeded Gaussian directions and +- the axes."""
+    if not _HULL_DIRECTIONS:
+        d = np.random.default_rng(0).standard_normal((64, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        _HULL_DIRECTIONS.append(np.concatenate([d, np.eye(3), -np.eye(3)]))
+    return _HULL_DIRECTIONS[0]
+
+
+def hull_candidates(points):
+    """The points (float64 [P,3], tensor on either device, or numpy) that can be vertices of their convex hull, as a tensor on the
+    points' device: the extreme points along 70 fixed directions span an inner hull (scipy, on <= 70 points); every point
+    deeper than a relative 1e-9 inside all of its half-spaces (inside_halfspaces' arithmetic) is dropped.  A vertex of the hull
+    of all points is never strictly inside the hull of some of them, so ConvexHull(survivors) has the vertex set of
+    ConvexHull(points) at a fraction of its cost.  A degenerate extreme set (scipy raises) returns all points."""
+    from scipy.spatial import ConvexHull
+    p = (torch.from_numpy(np.asarray(points)) if not torch.is_tensor(points) else points).double()
+    if p.shape[0] < 5:
+        return p
+    dirs = torch.from_numpy(hull_directions()).to(p.device)
+    extreme = torch.unique(torch.argmax(p @ dirs.T, dim=0))
+    try:
+        hs = ConvexHull(p[extreme].cpu().numpy()).equations.astype(np.float64)
+    except Exception:               # degenerate (planar) set: keep the points
+        return p
+    eps = 1e-9 * float((p.max(0).values - p.min(0).values).max())
+    hs[:, 3] += eps                 # n . x + d + eps <= 0: deeper than eps inside this half-space
+    return p[~inside_halfspaces(p, torch.from_numpy(hs).to(p.device))]
 
 
 def inside_halfspaces(points, halfspaces, block=32):

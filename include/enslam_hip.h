@@ -532,6 +532,55 @@ int enslam_frame_prepare(const enslam_frame_plan *plan, const uint8_t *color_raw
                          const uint8_t *event_raw, double *color_out, float *depth_out, void *event_out,
                          int64_t *mask_out, void *stream);
 
+/* Block-sparse TSDF volume (Mesher.get_bound_from_frames, Mesher.py:214-279: Open3D's ScalableTSDFVolume.integrate and
+ * extract_triangle_mesh; tsdf.py holds the arrays and does the allocation).
+ *   units   16^3 voxels, anchored at the world origin: unit = floor(p / (16 * voxel_length)) per axis.  The block table
+ *           (device int32 [nu0 * nu1 * nu2], z fastest, -1 = absent, otherwise a block id < n_blocks) covers the integer unit
+ *           box [unit_lo, unit_lo + nu) (host int32 [3] each); at most 2^27 entries (ENSLAM_EUNSUPPORTED beyond).
+ *   blocks  tsdf / weight float32 [n_blocks,4096], vcolor float32 [n_blocks,4096,3] or NULL, voxel (lx, ly, lz) of a block at
+ *           (lx * 16 + ly) * 16 + lz.  0 < sdf_trunc <= 16 * voxel_length (ENSLAM_EINVAL otherwise).
+ *   cam_host host float64 [4] = fx, fy, cx, cy; poses host float64 [12] = the rows of a [3,4] matrix, in the reference's camera
+ *           axes (x right, y up, looking along -z).
+ * enslam_tsdf_touch: for every pixel on rows / columns 0, stride, 2 stride, ... with depth > 0 (depth float32 [H,W]) the world
+ *   point P = c2w . (depth * [(i - cx) / fx, -(j - cy) / fy, -1]) in float64, products summed left to right and the translation
+ *   added last; stamps[unit] = stamp for every unit from floor((P - sdf_trunc) / L) to floor((P + sdf_trunc) / L) per axis,
+ *   L = 16 * voxel_length (plain stores of one value).  Units outside the table are ignored; outside_partials (int32
+ *   [ceil(ceil(H / stride) * ceil(W / stride) / 256)]) receives per workgroup the number of pixels that had one.
+ * enslam_tsdf_integrate: Open3D's UniformTSDFVolume integration with the depth-to-distance multiplier, over the voxels of the
+ *   n_touched blocks touched_block (ids) / touched_index (their table indices), every voxel evaluated on its own in float64
+ *   (Open3D steps the camera point incrementally in float32):
+ *     centre = (g + 0.5) * voxel_length, g the global integer voxel index; (x, y, z) = w2c . centre; zc = -z > 0 required;
+ *     u_f = x * fx / zc + cx + 0.5, v_f = (-y) * fy / zc + cy + 0.5; inside iff 1e-4 <= u_f < W - 1e-4 (v likewise);
+ *     (u, v) = trunc(u_f, v_f); d = depth[v,u] > 0 required; sdf = (d - zc) * mult[v,u] (mult float64 [H,W], the length of
+ *     the pixel's un-normalised ray, made by the host); skipped if sdf <= -sdf_trunc; t = (float) min(1, sdf / sdf_trunc);
+ *     float32: tsdf = (tsdf * w + t) / (w + 1), vcolor likewise from color[v,u] (float32 [H,W,3]; color and vcolor are both
+ *     given or both NULL), w += 1.
+ *   voxel_counts (int32 [n_touched * 16]) receives the number of voxels updated per (block, x slab).
+ * Extraction (the pattern of enslam_marching_cubes_*): sorted_block / sorted_index int32 [n_blocks] are the block ids and
+ *   their table indices in ascending table index.  A cell is the 8 voxels g + {0,1}^3, valid iff all lie in allocated blocks
+ *   with weight > 0; a corner is "occupied" iff tsdf < 0 (zero level, normals towards positive tsdf).  A voxel owns its +x / +y /
+ *   +z edges; an edge carries a vertex iff both ends have weight > 0 and different signs and one of the up to four cells sharing
+ *   it is valid.  Vertex: centre(a) + t_a / (t_a - t_b) * voxel_length along the axis (float64); colour: the same interpolation
+ *   of the two voxels' colours, clipped to [0, 1], floor(255 c + 0.5).  Order: blocks by table index, voxels in lattice order,
+ *   edges x, y, z; faces by cell, then case-table order.  counts: device int32 [2] = vertices, triangles.  At most 100000
+ *   blocks (ENSLAM_EUNSUPPORTED beyond).  colors uint8 [V,3] may be NULL. */
+int enslam_tsdf_touch(const float *depth, int32_t H, int32_t W, int32_t stride, const double *cam_host, const double *c2w_host,
+                      double sdf_trunc, double voxel_length, const int32_t *unit_lo_host, const int32_t *nu_host,
+                      int32_t stamp, int32_t *stamps, int32_t *outside_partials, void *stream);
+int enslam_tsdf_integrate(const float *depth, const float *color, const double *mult, int32_t H, int32_t W,
+                          const double *cam_host, const double *w2c_host, double voxel_length, double sdf_trunc,
+                          const int32_t *unit_lo_host, const int32_t *nu_host, int32_t n_touched, const int32_t *touched_block,
+                          const int32_t *touched_index, int32_t n_blocks, float *tsdf, float *weight, float *vcolor,
+                          int32_t *voxel_counts, void *stream);
+int enslam_tsdf_mesh_workspace(int32_t n_blocks, int64_t *bytes_host);
+int enslam_tsdf_mesh_count(const int32_t *table, const int32_t *nu_host, int32_t n_blocks, const int32_t *sorted_block,
+                           const int32_t *sorted_index, const float *tsdf, const float *weight, void *workspace,
+                           int32_t *counts, void *stream);
+int enslam_tsdf_mesh_emit(const int32_t *table, const int32_t *unit_lo_host, const int32_t *nu_host, int32_t n_blocks,
+                          const int32_t *sorted_block, const int32_t *sorted_index, const float *tsdf, const float *weight,
+                          const float *vcolor, double voxel_length, void *workspace, int32_t n_verts, int32_t n_faces,
+                          double *verts, int32_t *faces, uint8_t *colors, void *stream);
+
 /* Hand-derived backward of enslam_render_fwd (replaces autograd of the reference ops).
  *   g_depth float64 [N], g_var float64 [N] or NULL, g_rgb float32 [N,3] or NULL
  *   grad_grids[k].data : voxel-major accumulators (caller-zeroed) or NULL to skip that grid

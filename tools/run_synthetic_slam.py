@@ -1,8 +1,10 @@
 """The run harness on an analytic, view-consistent sequence (synthetic.BoxRoom): ATE of the full schedule against the ATE of
 poses left at their constant-speed initialisation (tracking_iters = 0).  usage: python tools/run_synthetic_slam.py [n_frames]
-[--mesh DIR] [--overlap]: --mesh also meshes the tracked run's map (SLAM.get_mesh) into DIR/mesh.ply and reports accuracy,
+[--mesh DIR] [--tsdf] [--overlap]: --mesh also meshes the tracked run's map (SLAM.get_mesh) into DIR/mesh.ply and reports accuracy,
 completion and completion ratio (eval_recon, metres) against the room's analytic surfaces seen by the keyframes, of the mesh
-vertices and, under 'surface_samples', of area-weighted samples of the mesh (eval_recon.sample_surface); --overlap selects
+vertices and, under 'surface_samples', of area-weighted samples of the mesh (eval_recon.sample_surface); with --tsdf the
+keyframes' depth fused under the estimated poses (tsdf.TSDFVolume, the reference's voxel size) is written to DIR/tsdf.ply and
+evaluated beside the neural mesh, under 'tsdf'; --overlap selects
 the mapping window with mapping.keyframe_selection_method 'overlap' (mapper.keyframe_selection_overlap) instead of 'global'."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,7 +21,23 @@ DEV = 'cuda:0'
 from evennicer_slam_amd.synthetic import demo_config, write_demo_sequence
 
 
-def mesh_metrics(slam, path, n_gt=200000):
+def tsdf_metrics(slam, path, gt):
+    """The same three numbers for the TSDF-fused mesh of the run's keyframes under their estimated poses (written to path)."""
+    from evennicer_slam_amd import eval_recon as R
+    from evennicer_slam_amd import mesher as MS
+    from evennicer_slam_amd.tsdf import TSDFVolume
+    cam = dict(H=slam.H, W=slam.W, fx=slam.fx, fy=slam.fy, cx=slam.cx, cy=slam.cy)
+    vol = TSDFVolume.for_frames(slam.keyframe_dict, cam, 4.0 * slam.scale / 512.0, 0.04 * slam.scale, color=True, device=slam.device)
+    verts, faces, colors = (t.cpu().numpy() for t in vol.extract_mesh())
+    verts = verts / slam.scale
+    MS.write_ply(path, verts, faces, colors)
+    if not len(verts) or not len(gt):
+        return dict(accuracy=None, completion=None, completion_ratio=0.0, vertices=0, faces=0)
+    return dict(accuracy=R.accuracy(gt, verts), completion=R.completion(gt, verts), completion_ratio=R.completion_ratio(gt, verts),
+                vertices=int(len(verts)), faces=int(len(faces)), blocks=vol.stats['blocks'], bytes=vol.stats['bytes'])
+
+
+def mesh_metrics(slam, path, n_gt=200000, tsdf=False):
     """accuracy / completion / completion ratio (5 cm) of SLAM.get_mesh's mesh against BoxRoom.sample_surface points that
     the keyframes see (the room of synthetic.write_demo_sequence)."""
     from evennicer_slam_amd import eval_recon as R
@@ -41,10 +59,12 @@ def mesh_metrics(slam, path, n_gt=200000):
         g = torch.from_numpy(gt).to(dev)
         out['surface_samples'] = dict(accuracy=R.accuracy(g, pts), completion=R.completion(g, pts),
                                       completion_ratio=R.completion_ratio(g, pts), samples=int(n_gt))
+    if tsdf:
+        out['tsdf'] = tsdf_metrics(slam, os.path.join(os.path.dirname(path), 'tsdf.ply'), gt)
     return out
 
 
-def run(n=30, verbose=True, mesh_dir=None, overlap=False):
+def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -65,7 +85,7 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False):
                             fps=res['fps'], prefit_loss=fit)
             if mesh_dir is not None and tag == 'tracked':
                 os.makedirs(mesh_dir, exist_ok=True)
-                out[tag]['mesh'] = mesh_metrics(slam, os.path.join(mesh_dir, 'mesh.ply'))
+                out[tag]['mesh'] = mesh_metrics(slam, os.path.join(mesh_dir, 'mesh.ply'), tsdf=tsdf)
             if verbose:
                 print(tag, out[tag], flush=True)
     return out
@@ -81,4 +101,7 @@ if __name__ == '__main__':
     overlap = '--overlap' in args
     if overlap:
         args.remove('--overlap')
-    run(int(args[0]) if args else 30, mesh_dir=mesh_dir, overlap=overlap)
+    tsdf = '--tsdf' in args
+    if tsdf:
+        args.remove('--tsdf')
+    run(int(args[0]) if args else 30, mesh_dir=mesh_dir, overlap=overlap, tsdf=tsdf)
