@@ -251,6 +251,15 @@ _SIGS = {
                                                     c_void_p, c_void_p, c_void_p]),
     "enslam_composite_density_bwd": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_eventnet_pack_floats": (c_size_t, []),
+    "enslam_eventnet_workspace_floats": (c_size_t, [c_int32, c_int32]),
+    "enslam_eventnet_forward": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_eventnet_backward": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "enslam_eventnet_conv3x3": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                               c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                               c_void_p, c_int64, c_void_p]),
+    "enslam_eventnet_pool2": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "enslam_eventnet_up2": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

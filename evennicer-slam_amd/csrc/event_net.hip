@@ -1,0 +1,574 @@
+// Event network on the device: UNet_2heads(6, 2, 2), bilinear, eval mode, batch 1, float32 -- forward and the gradient
+// with respect to the input image (event.py: UNet_2heads; reference event_net/unet_model.py:72-122, unet_parts.py).
+//
+// Frozen weights and eval-mode BatchNorm make every conv - BN - ReLU triple one 3x3 convolution with folded weights
+// w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps) (event.py folds in float64 and rounds once).
+// Activations are channels-last ([H*W][C]) so the reduction axis of a tap is contiguous; the public tensors stay
+// [1,C,H,W] (en_pack_x / en_unpack_gx / the heads convert).
+//
+//   conv3x3_kernel   implicit GEMM  out[p][n] = sum_{tap, c} in[p + tap][c] * w[(tap, c)][n]  on v_mfma_f32_32x32x2_f32
+//                    (exact f32, an fmaf chain in k order).  One workgroup (4 waves as 2 x 2) owns 64 pixels x 64 output
+//                    channels, one 32 x 32 accumulator tile per wave; the reduction runs in chunks of 32 k staged in LDS
+//                    (A transposed [k][pixel], row stride 65; B [k][n]), the next chunk's global loads issued before the
+//                    current chunk's MFMAs.  The input may be two sources read in place: the skip and the up-sampled
+//                    deep feature with its centred zero padding (torch.cat / F.pad are not materialised).  The input
+//                    gradient is the SAME kernel on weights packed flipped and transposed: the incoming gradient is
+//                    masked at load by saved_out > 0 (relu'(0) = 0 as in torch), and where the forward read two sources
+//                    the result goes to two destinations.  Layers with few pixels split the reduction over
+//                    blockIdx.z; conv3x3_reduce_kernel sums the partials in split order: no atomics, results are
+//                    bit-reproducible.
+//   pool2 / up2      nn.MaxPool2d(2) and x2 bilinear up-sampling (align_corners=True) with their backward passes as
+//                    gathers (pool: the window's first maximum in row-major order takes the gradient, torch's tie rule;
+//                    up: torch's float32 source-coordinate expression, so the interpolation weights are F.interpolate's).
+//   heads            the two 1x1 heads fused (sigmoid on head 2), and their backward into the 64-channel features.
+#include "../../include/enslam_hip.h"
+#include "common.hpp"
+#include <algorithm>
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int EN_TM = 64;             // pixels per workgroup
+constexpr int EN_TN = 64;             // output channels per workgroup
+constexpr int EN_KC = 32;             // reduction chunk
+constexpr int EN_LDA = EN_TM + 1;     // LDS row stride of the A chunk (floats)
+constexpr int EN_THREADS = 256;
+constexpr int EN_SPLIT_BELOW = 256;   // layers with fewer output tiles than this split the reduction ...
+constexpr int EN_SPLIT_TARGET = 512;  // ... to about this many workgroups
+constexpr int EN_NCONV = 26;
+constexpr int EN_HEADS_FLOATS = 264;  // W1 [2][64] | W2 [2][64] | b1 [2] | b2 [2] | pad
+
+struct ConvArgs {
+    const float* w;       // [9 * (C0 + C1)][N]
+    const float* bias;    // [N] or null
+    const float* s0;      // [H * W][C0]
+    const float* s1;      // [sH1 * sW1][C1]: conv pixel (y, x) reads (y - soy, x - sox), zero outside; null iff C1 == 0
+    const float* mask;    // layout of s0 or null: s0's values count only where mask > 0
+    float* d0;            // [H * W][N0]
+    float* d1;            // [dH1 * dW1][N - N0]: conv pixel (y, x) writes (y - doy, x - dox), dropped outside; null iff N0 == N
+    float* part;          // [splits][H * W][N]
+    int H, W, C0, C1, sH1, sW1, soy, sox;
+    int N, N0, dH1, dW1, doy, dox;
+    int relu, acc0, acc1;
+    int nchunks, cps;     // chunks in all / per split
+};
+
+ENS_DEV f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+// C/D map of the 32x32 f32 MFMA: column lane & 31, row (v & 3) + 8 (v >> 2) + 4 (lane >> 5)
+ENS_DEV int c_row(int v, int lane) { return (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5); }
+
+ENS_DEV void conv_emit(const ConvArgs& a, int p, int n, float v) {
+    if (a.bias) v = v + a.bias[n];
+    if (a.relu) v = v > 0.f ? v : 0.f;
+    float* q;
+    int acc;
+    if (n < a.N0) {
+        q = a.d0 + (int64_t)p * a.N0 + n;
+        acc = a.acc0;
+    } else {
+        const int y = p / a.W - a.doy, x = p % a.W - a.dox;
+        if (y < 0 || y >= a.dH1 || x < 0 || x >= a.dW1) return;
+        q = a.d1 + ((int64_t)y * a.dW1 + x) * (a.N - a.N0) + (n - a.N0);
+        acc = a.acc1;
+    }
+    *q = acc ? *q + v : v;
+}
+
+__global__ __launch_bounds__(EN_THREADS) void conv3x3_kernel(ConvArgs a) {
+    __shared__ float As[EN_KC * EN_LDA];
+    __shared__ __attribute__((aligned(16))) float Bs[EN_KC * EN_TN];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
+    const int r = lane & 31, h = lane >> 5;
+    const int P = a.H * a.W, Cin = a.C0 + a.C1, K = 9 * Cin;
+    const int p0 = blockIdx.x * EN_TM, n0 = blockIdx.y * EN_TN;
+    // loader roles.  A: 4 channels (kq) of pixels t >> 3 and 32 + (t >> 3); B: 4 columns (bc) of rows t >> 4 and 16 + (t >> 4)
+    const int kq = t & 7, apx = t >> 3, brow = t >> 4, bc = (t & 15) * 4;
+    int ay[2], ax[2];
+    bool aok[2];
+    for (int i = 0; i < 2; ++i) {
+        const int p = p0 + apx + 32 * i;
+        aok[i] = p < P;
+        ay[i] = aok[i] ? p / a.W : 0;
+        ax[i] = aok[i] ? p % a.W : 0;
+    }
+    const bool bok = n0 + bc < a.N;        // N is a multiple of 4
+    f32x4 av[2], bv[2];
+    auto load = [&](int ch) {
+        const int k4 = ch * EN_KC + 4 * kq;
+        const int tap = k4 / Cin, c = k4 - tap * Cin;
+        const int dy = tap / 3 - 1, dx = tap % 3 - 1;
+        for (int i = 0; i < 2; ++i) {
+            f32x4 v = splat4(0.f);
+            const int yy = ay[i] + dy, xx = ax[i] + dx;
+            if (k4 < K && aok[i] && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) {
+                if (c < a.C0) {
+                    const int64_t idx = ((int64_t)yy * a.W + xx) * a.C0 + c;
+                    v = ld4(a.s0 + idx);
+                    if (a.mask) {
+                        const f32x4 m = ld4(a.mask + idx);
+                        for (int e = 0; e < 4; ++e) v[e] = m[e] > 0.f ? v[e] : 0.f;
+                    }
+                } else {
+                    const int y1 = yy - a.soy, x1 = xx - a.sox;
+                    if (y1 >= 0 && y1 < a.sH1 && x1 >= 0 && x1 < a.sW1)
+                        v = ld4(a.s1 + ((int64_t)y1 * a.sW1 + x1) * a.C1 + (c - a.C0));
+                }
+            }
+            av[i] = v;
+            const int k = ch * EN_KC + brow + 16 * i;
+            bv[i] = (k < K && bok) ? ld4(a.w + (int64_t)k * a.N + n0 + bc) : splat4(0.f);
+        }
+    };
+    f32x16 acc;
+    for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+    const int c_begin = blockIdx.z * a.cps;
+    const int c_end = min(c_begin + a.cps, a.nchunks);
+    if (c_begin < c_end) load(c_begin);
+    for (int ch = c_begin; ch < c_end; ++ch) {
+        __syncthreads();                       // every wave has finished reading the previous chunk
+        for (int i = 0; i < 2; ++i) {
+            for (int e = 0; e < 4; ++e) As[(4 * kq + e) * EN_LDA + apx + 32 * i] = av[i][e];
+            *reinterpret_cast<f32x4*>(&Bs[(brow + 16 * i) * EN_TN + bc]) = bv[i];
+        }
+        __syncthreads();
+        if (ch + 1 < c_end) load(ch + 1);      // in flight under this chunk's MFMAs
+        for (int kk = 0; kk < EN_KC; kk += 2)
+            acc = mfma32(As[(kk + h) * EN_LDA + 32 * wm + r], Bs[(kk + h) * EN_TN + 32 * wn + r], acc);
+    }
+    const int n = n0 + 32 * wn + r;
+    if (n >= a.N) return;
+    const bool split = gridDim.z > 1;
+    for (int v = 0; v < 16; ++v) {
+        const int p = p0 + 32 * wm + c_row(v, lane);
+        if (p >= P) continue;
+        if (split) a.part[((int64_t)blockIdx.z * P + p) * a.N + n] = acc[v];
+        else conv_emit(a, p, n, acc[v]);
+    }
+}
+
+__global__ __launch_bounds__(256) void conv3x3_reduce_kernel(ConvArgs a, int splits) {
+    const int64_t PN = (int64_t)a.H * a.W * a.N;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= PN) return;
+    float s = a.part[i];
+    for (int k = 1; k < splits; ++k) s = s + a.part[k * PN + i];     // fixed order
+    conv_emit(a, (int)(i / a.N), (int)(i % a.N), s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// 2x2 max pool, [H][W][C] -> [H/2][W/2][C] (floor).  The first maximum in row-major order wins (ATen: val > max).
+// ---------------------------------------------------------------------------------------------------------------
+ENS_DEV int pool_argmax(const float* in, int W, int C, int oy, int ox, int c, float& best) {
+    int arg = 0;
+    best = in[((int64_t)(2 * oy) * W + 2 * ox) * C + c];
+    for (int k = 1; k < 4; ++k) {
+        const float v = in[((int64_t)(2 * oy + (k >> 1)) * W + 2 * ox + (k & 1)) * C + c];
+        if (v > best || v != v) { best = v; arg = k; }
+    }
+    return arg;
+}
+
+__global__ __launch_bounds__(256) void pool2_fwd_kernel(const float* __restrict__ in, int H, int W, int C,
+                                                        float* __restrict__ out) {
+    const int Ho = H / 2, Wo = W / 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)Ho * Wo * C) return;
+    const int c = (int)(i % C), q = (int)(i / C);
+    float best;
+    pool_argmax(in, W, C, q / Wo, q % Wo, c, best);
+    out[i] = best;
+}
+
+// d_in[H][W][C] (=, or += with acc) g_out[H/2][W/2][C] where the pixel is its window's first maximum; 0 elsewhere
+__global__ __launch_bounds__(256) void pool2_bwd_kernel(const float* __restrict__ in, int H, int W, int C,
+                                                        const float* __restrict__ g_out, float* __restrict__ d_in, int acc) {
+    const int Ho = H / 2, Wo = W / 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)H * W * C) return;
+    const int c = (int)(i % C), p = (int)(i / C), y = p / W, x = p % W;
+    float g = 0.f;
+    if (y < 2 * Ho && x < 2 * Wo) {
+        float best;
+        const int arg = pool_argmax(in, W, C, y / 2, x / 2, c, best);
+        if (arg == 2 * (y & 1) + (x & 1)) g = g_out[((int64_t)(y / 2) * Wo + x / 2) * C + c];
+    }
+    d_in[i] = acc ? d_in[i] + g : g;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// x2 bilinear up-sampling, align_corners=True, [h][w][C] -> [2h][2w][C].  ATen (UpSample.h): scale = (in - 1) / (out - 1)
+// in float32 (0 when out == 1), src = scale * dst, i0 = floor(src), i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1;
+// value = l0y * (l0x * v00 + l1x * v01) + l1y * (l0x * v10 + l1x * v11).
+// ---------------------------------------------------------------------------------------------------------------
+ENS_DEV float up_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
+ENS_DEV void up_src(float scale, int dst, int in, int& i0, int& i1, float& l0, float& l1) {
+    const float src = scale * (float)dst;
+    i0 = min((int)floorf(src), in - 1);
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    l1 = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
+    l0 = 1.f - l1;
+}
+
+__global__ __launch_bounds__(256) void up2_fwd_kernel(const float* __restrict__ in, int h, int w, int C,
+                                                      float* __restrict__ out) {
+    const int Ho = 2 * h, Wo = 2 * w;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)Ho * Wo * C) return;
+    const int c = (int)(i % C), q = (int)(i / C), Y = q / Wo, X = q % Wo;
+    int y0, y1, x0, x1;
+    float ly0, ly1, lx0, lx1;
+    up_src(up_scale(h, Ho), Y, h, y0, y1, ly0, ly1);
+    up_src(up_scale(w, Wo), X, w, x0, x1, lx0, lx1);
+    const float v00 = in[((int64_t)y0 * w + x0) * C + c], v01 = in[((int64_t)y0 * w + x1) * C + c];
+    const float v10 = in[((int64_t)y1 * w + x0) * C + c], v11 = in[((int64_t)y1 * w + x1) * C + c];
+    out[i] = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+}
+
+// the output rows whose stencil can touch input row i: floor(scale * Y) in {i - 1, i}, with one row of slack either side
+ENS_DEV void up_range(float scale, int i, int out, int& lo, int& hi) {
+    if (scale <= 0.f) { lo = 0; hi = out - 1; return; }
+    lo = max(0, (int)floorf((float)(i - 1) / scale) - 1);
+    hi = min(out - 1, (int)ceilf((float)(i + 1) / scale) + 1);
+}
+
+// d_in[h][w][C] (=, or += with acc) the gather of g_out[2h][2w][C]: output pixels in ascending (Y, X) order
+__global__ __launch_bounds__(256) void up2_bwd_kernel(const float* __restrict__ g_out, int h, int w, int C,
+                                                      float* __restrict__ d_in, int acc) {
+    const int Ho = 2 * h, Wo = 2 * w;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)h * w * C) return;
+    const int c = (int)(i % C), p = (int)(i / C), y = p / w, x = p % w;
+    const float sy = up_scale(h, Ho), sx = up_scale(w, Wo);
+    int Ylo, Yhi, Xlo, Xhi;
+    up_range(sy, y, Ho, Ylo, Yhi);
+    up_range(sx, x, Wo, Xlo, Xhi);
+    float s = 0.f;
+    for (int Y = Ylo; Y <= Yhi; ++Y) {
+        int y0, y1, x0, x1;
+        float ly0, ly1, lx0, lx1;
+        up_src(sy, Y, h, y0, y1, ly0, ly1);
+        const float wy = (y0 == y ? ly0 : 0.f) + (y1 == y ? ly1 : 0.f);
+        if (y0 != y && y1 != y) continue;
+        for (int X = Xlo; X <= Xhi; ++X) {
+            up_src(sx, X, w, x0, x1, lx0, lx1);
+            if (x0 != x && x1 != x) continue;
+            const float wx = (x0 == x ? lx0 : 0.f) + (x1 == x ? lx1 : 0.f);
+            s = fmaf(wy * wx, g_out[((int64_t)Y * Wo + X) * C + c], s);
+        }
+    }
+    d_in[i] = acc ? d_in[i] + s : s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// layout changes of the public tensors and the heads
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void en_pack_x_kernel(const float* __restrict__ x, int P, float* __restrict__ x8) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P * 8) return;
+    const int c = i & 7, p = i >> 3;
+    x8[i] = c < 6 ? x[(int64_t)c * P + p] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void en_unpack_gx_kernel(const float* __restrict__ g8, int P, float* __restrict__ gx) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P * 6) return;
+    const int c = i / P, p = i % P;
+    gx[i] = g8[(int64_t)p * 8 + c];
+}
+
+// hw: W1 [2][64] | W2 [2][64] | b1 [2] | b2 [2].  events [2][P] = W1 f1 + b1, probs [2][P] = sigmoid(W2 f2 + b2)
+__global__ __launch_bounds__(256) void heads_fwd_kernel(const float* __restrict__ hw, const float* __restrict__ f1,
+                                                        const float* __restrict__ f2, int P, float* __restrict__ events,
+                                                        float* __restrict__ probs, float* __restrict__ probs_saved) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * P) return;
+    const int head = i / P, p = i % P;
+    const float* f = (head ? f2 : f1) + (int64_t)p * 64;
+    const float* w = hw + 128 * head;
+    float s0 = 0.f, s1 = 0.f;
+    for (int c = 0; c < 64; c += 4) {
+        const f32x4 v = ld4(f + c);
+        for (int e = 0; e < 4; ++e) { s0 = fmaf(v[e], w[c + e], s0); s1 = fmaf(v[e], w[64 + c + e], s1); }
+    }
+    s0 = s0 + hw[256 + 2 * head];
+    s1 = s1 + hw[257 + 2 * head];
+    if (head) {
+        const float q0 = 1.f / (1.f + expf(-s0)), q1 = 1.f / (1.f + expf(-s1));
+        probs[p] = q0;
+        probs[P + p] = q1;
+        probs_saved[p] = q0;
+        probs_saved[P + p] = q1;
+    } else {
+        events[p] = s0;
+        events[P + p] = s1;
+    }
+}
+
+// g_f [P][64] of head `head`: W^T g (head 1: g through the sigmoid, s (1 - s) from the saved probabilities)
+__global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict__ hw, int head, const float* __restrict__ g,
+                                                        const float* __restrict__ probs, int P, float* __restrict__ g_f) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P * 64) return;
+    const int c = i & 63, p = i >> 6;
+    float g0 = g[p], g1 = g[P + p];
+    if (head) {
+        const float q0 = probs[p], q1 = probs[P + p];
+        g0 = g0 * (q0 * (1.f - q0));
+        g1 = g1 * (q1 * (1.f - q1));
+    }
+    const float* w = hw + 128 * head;
+    g_f[i] = fmaf(g1, w[64 + c], g0 * w[c]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------
+struct SplitPlan { int ptiles, ntiles, nchunks, cps, splits; };
+
+SplitPlan split_plan(int64_t P, int Cin, int N) {
+    SplitPlan s;
+    s.ptiles = (int)((P + EN_TM - 1) / EN_TM);
+    s.ntiles = (N + EN_TN - 1) / EN_TN;
+    s.nchunks = (9 * Cin + EN_KC - 1) / EN_KC;
+    s.cps = s.nchunks;
+    const int64_t tiles = (int64_t)s.ptiles * s.ntiles;
+    if (tiles < EN_SPLIT_BELOW) {
+        const int want = (int)std::min<int64_t>(s.nchunks, (EN_SPLIT_TARGET + tiles - 1) / tiles);
+        s.cps = (s.nchunks + want - 1) / want;
+    }
+    s.splits = (s.nchunks + s.cps - 1) / s.cps;
+    return s;
+}
+int64_t split_floats(int64_t P, int Cin, int N) {
+    const SplitPlan s = split_plan(P, Cin, N);
+    return s.splits > 1 ? (int64_t)s.splits * P * N : 0;
+}
+
+bool chan_ok(int c) { return c >= 8 && c <= 1024 && c % 8 == 0; }
+
+int launch_conv(ConvArgs a, hipStream_t st) {
+    const int64_t P = (int64_t)a.H * a.W;
+    const SplitPlan s = split_plan(P, a.C0 + a.C1, a.N);
+    a.nchunks = s.nchunks;
+    a.cps = s.cps;
+    conv3x3_kernel<<<dim3(s.ptiles, s.ntiles, s.splits), EN_THREADS, 0, st>>>(a);
+    if (s.splits > 1) conv3x3_reduce_kernel<<<(unsigned)((P * a.N + 255) / 256), 256, 0, st>>>(a, s.splits);
+    return 0;
+}
+
+inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// the 26 convolutions in packing order: encoder (inc, down1..4), then per head up1..up4
+struct ConvDim { int cin, cout; };
+const ConvDim EN_CONV[EN_NCONV] = {
+    {8, 64}, {64, 64}, {64, 128}, {128, 128}, {128, 256}, {256, 256}, {256, 512}, {512, 512}, {512, 512}, {512, 512},
+    {1024, 512}, {512, 256}, {512, 256}, {256, 128}, {256, 128}, {128, 64}, {128, 64}, {64, 64},
+    {1024, 512}, {512, 256}, {512, 256}, {256, 128}, {256, 128}, {128, 64}, {128, 64}, {64, 64}};
+const int EN_ENC_C[5] = {64, 128, 256, 512, 512};       // channels of the encoder features f0..f4
+const int EN_DEC_CD[4] = {512, 256, 128, 64};           // per decoder stage: channels of the deep input (= skip = mid)
+const int EN_DEC_OUT[4] = {256, 128, 64, 64};
+
+// packed image: per convolution  Wf [9 cin][cout] | b [cout] | Wt [9 cout][cin],  then the heads block
+struct PackOff { int64_t wf[EN_NCONV], b[EN_NCONV], wt[EN_NCONV], heads, total; };
+PackOff pack_offsets() {
+    PackOff o;
+    int64_t q = 0;
+    for (int i = 0; i < EN_NCONV; ++i) {
+        const int64_t n = (int64_t)9 * EN_CONV[i].cin * EN_CONV[i].cout;
+        o.wf[i] = q; q += n;
+        o.b[i] = q; q += EN_CONV[i].cout;
+        o.wt[i] = q; q += n;
+    }
+    o.heads = q;
+    o.total = q + EN_HEADS_FLOATS;
+    return o;
+}
+
+// workspace (float offsets, every region a multiple of 64 floats)
+struct Plan {
+    int H[5], W[5];
+    int64_t P[5];
+    int64_t x8, a[5], f[5], pl[5], u[2][4], m[2][4], d[2][4], probs, df[5], t[3], part, total;
+};
+Plan make_plan(int H, int W) {
+    Plan pl;
+    for (int l = 0; l < 5; ++l) {
+        pl.H[l] = l ? pl.H[l - 1] / 2 : H;
+        pl.W[l] = l ? pl.W[l - 1] / 2 : W;
+        pl.P[l] = (int64_t)pl.H[l] * pl.W[l];
+    }
+    int64_t q = 0, part = 0;
+    auto take = [&](int64_t n) { const int64_t at = q; q += (n + 63) / 64 * 64; return at; };
+    auto conv = [&](int64_t P, int cin, int cout) {
+        part = std::max(part, std::max(split_floats(P, cin, cout), split_floats(P, cout, cin)));
+    };
+    pl.x8 = take(pl.P[0] * 8);
+    for (int l = 0; l < 5; ++l) {
+        pl.pl[l] = l ? take(pl.P[l] * EN_ENC_C[l - 1]) : -1;
+        pl.a[l] = take(pl.P[l] * EN_ENC_C[l]);
+        pl.f[l] = take(pl.P[l] * EN_ENC_C[l]);
+        pl.df[l] = take(pl.P[l] * EN_ENC_C[l]);
+        conv(pl.P[l], EN_CONV[2 * l].cin, EN_CONV[2 * l].cout);
+        conv(pl.P[l], EN_CONV[2 * l + 1].cin, EN_CONV[2 * l + 1].cout);
+    }
+    for (int hd = 0; hd < 2; ++hd)
+        for (int j = 0; j < 4; ++j) {
+            const int ls = 3 - j, cd = EN_DEC_CD[j];
+            pl.u[hd][j] = take(4 * pl.P[ls + 1] * cd);
+            pl.m[hd][j] = take(pl.P[ls] * cd);
+            pl.d[hd][j] = take(pl.P[ls] * EN_DEC_OUT[j]);
+            conv(pl.P[ls], 2 * cd, cd);
+            conv(pl.P[ls], cd, EN_DEC_OUT[j]);
+        }
+    pl.probs = take(2 * pl.P[0]);
+    // transient gradients: at most P0 * 64 floats each (level l has P0 / 4^l pixels and at most 64 * 2^l channels)
+    for (int k = 0; k < 3; ++k) pl.t[k] = take(pl.P[0] * 64);
+    pl.part = take(part);
+    pl.total = q;
+    return pl;
+}
+
+bool size_ok(int H, int W) { return H >= 16 && W >= 16 && (int64_t)H * W <= (1 << 21); }
+
+}  // namespace
+
+extern "C" {
+
+size_t enslam_eventnet_pack_floats(void) { return (size_t)pack_offsets().total; }
+
+size_t enslam_eventnet_workspace_floats(int32_t H, int32_t W) {
+    if (!size_ok(H, W)) return 0;
+    return (size_t)make_plan(H, W).total;
+}
+
+int enslam_eventnet_forward(const float* packed, const float* x, int32_t H, int32_t W, float* workspace, float* events,
+                            float* probs, void* stream) {
+    if (!packed || !x || !workspace || !events || !probs) return ENSLAM_EINVAL;
+    if (!size_ok(H, W)) return ENSLAM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const Plan pl = make_plan(H, W);
+    const PackOff po = pack_offsets();
+    float* ws = workspace;
+    auto conv = [&](int i, int Hc, int Wc, const float* s0, int C0, const float* s1, int C1, int sH1, int sW1, float* dst) {
+        ConvArgs a = {};
+        a.w = packed + po.wf[i]; a.bias = packed + po.b[i];
+        a.s0 = s0; a.s1 = s1; a.d0 = dst; a.part = ws + pl.part;
+        a.H = Hc; a.W = Wc; a.C0 = C0; a.C1 = C1; a.sH1 = sH1; a.sW1 = sW1;
+        a.N = a.N0 = EN_CONV[i].cout; a.relu = 1;
+        launch_conv(a, st);
+    };
+    en_pack_x_kernel<<<blocks_of(pl.P[0] * 8), 256, 0, st>>>(x, (int)pl.P[0], ws + pl.x8);
+    for (int l = 0; l < 5; ++l) {
+        const float* in = ws + pl.x8;
+        int cin = 8;
+        if (l) {
+            cin = EN_ENC_C[l - 1];
+            pool2_fwd_kernel<<<blocks_of(pl.P[l] * cin), 256, 0, st>>>(ws + pl.f[l - 1], pl.H[l - 1], pl.W[l - 1], cin,
+                                                                       ws + pl.pl[l]);
+            in = ws + pl.pl[l];
+        }
+        conv(2 * l, pl.H[l], pl.W[l], in, cin, nullptr, 0, 0, 0, ws + pl.a[l]);
+        conv(2 * l + 1, pl.H[l], pl.W[l], ws + pl.a[l], EN_ENC_C[l], nullptr, 0, 0, 0, ws + pl.f[l]);
+    }
+    for (int hd = 0; hd < 2; ++hd) {
+        const float* deep = ws + pl.f[4];
+        for (int j = 0; j < 4; ++j) {
+            const int ls = 3 - j, ld = ls + 1, cd = EN_DEC_CD[j];
+            up2_fwd_kernel<<<blocks_of(4 * pl.P[ld] * cd), 256, 0, st>>>(deep, pl.H[ld], pl.W[ld], cd, ws + pl.u[hd][j]);
+            conv(10 + 8 * hd + 2 * j, pl.H[ls], pl.W[ls], ws + pl.f[ls], cd, ws + pl.u[hd][j], cd, 2 * pl.H[ld],
+                 2 * pl.W[ld], ws + pl.m[hd][j]);
+            conv(11 + 8 * hd + 2 * j, pl.H[ls], pl.W[ls], ws + pl.m[hd][j], cd, nullptr, 0, 0, 0, ws + pl.d[hd][j]);
+            deep = ws + pl.d[hd][j];
+        }
+    }
+    heads_fwd_kernel<<<blocks_of(2 * pl.P[0]), 256, 0, st>>>(packed + po.heads, ws + pl.d[0][3], ws + pl.d[1][3],
+                                                             (int)pl.P[0], events, probs, ws + pl.probs);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+int enslam_eventnet_backward(const float* packed, float* workspace, const float* g_events, const float* g_probs,
+                             float* g_x, int32_t H, int32_t W, void* stream) {
+    if (!packed || !workspace || !g_events || !g_probs || !g_x) return ENSLAM_EINVAL;
+    if (!size_ok(H, W)) return ENSLAM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const Plan pl = make_plan(H, W);
+    const PackOff po = pack_offsets();
+    float* ws = workspace;
+    float *tA = ws + pl.t[0], *tB = ws + pl.t[1], *tC = ws + pl.t[2];
+    // d(input of convolution i) from g (masked by the convolution's saved output): N0 channels to d0, the rest to d1
+    auto convT = [&](int i, int Hc, int Wc, const float* g, const float* saved, float* d0, int N0, int acc0, float* d1,
+                     int dH1, int dW1) {
+        ConvArgs a = {};
+        a.w = packed + po.wt[i];
+        a.s0 = g; a.mask = saved; a.C0 = EN_CONV[i].cout;
+        a.d0 = d0; a.d1 = d1; a.part = ws + pl.part;
+        a.H = Hc; a.W = Wc; a.N = EN_CONV[i].cin; a.N0 = N0; a.dH1 = dH1; a.dW1 = dW1; a.acc0 = acc0;
+        launch_conv(a, st);
+    };
+    for (int hd = 0; hd < 2; ++hd) {
+        heads_bwd_kernel<<<blocks_of(pl.P[0] * 64), 256, 0, st>>>(packed + po.heads, hd, hd ? g_probs : g_events,
+                                                                  ws + pl.probs, (int)pl.P[0], tA);
+        for (int j = 3; j >= 0; --j) {
+            const int ls = 3 - j, ld = ls + 1, cd = EN_DEC_CD[j];
+            convT(11 + 8 * hd + 2 * j, pl.H[ls], pl.W[ls], tA, ws + pl.d[hd][j], tB, cd, 0, nullptr, 0, 0);
+            convT(10 + 8 * hd + 2 * j, pl.H[ls], pl.W[ls], tB, ws + pl.m[hd][j], ws + pl.df[ls], cd, hd, tC, 2 * pl.H[ld],
+                  2 * pl.W[ld]);
+            float* dst = j ? tA : ws + pl.df[4];
+            up2_bwd_kernel<<<blocks_of(pl.P[ld] * cd), 256, 0, st>>>(tC, pl.H[ld], pl.W[ld], cd, dst, j ? 0 : hd);
+        }
+    }
+    for (int l = 4; l >= 0; --l) {
+        const int c = EN_ENC_C[l], cin = EN_CONV[2 * l].cin;
+        convT(2 * l + 1, pl.H[l], pl.W[l], ws + pl.df[l], ws + pl.f[l], tA, c, 0, nullptr, 0, 0);
+        convT(2 * l, pl.H[l], pl.W[l], tA, ws + pl.a[l], tB, cin, 0, nullptr, 0, 0);
+        if (l)
+            pool2_bwd_kernel<<<blocks_of(pl.P[l - 1] * cin), 256, 0, st>>>(ws + pl.f[l - 1], pl.H[l - 1], pl.W[l - 1], cin, tB,
+                                                                           ws + pl.df[l - 1], 1);
+    }
+    en_unpack_gx_kernel<<<blocks_of(pl.P[0] * 6), 256, 0, st>>>(tB, (int)pl.P[0], g_x);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+int enslam_eventnet_conv3x3(const float* w, const float* bias, int32_t H, int32_t W, int32_t C0, int32_t C1, int32_t H1,
+                            int32_t W1, int32_t oy, int32_t ox, int32_t Cn, const float* a0, const float* a1, float* d0,
+                            float* d1, int32_t relu, int32_t transposed, float* scratch, int64_t scratch_floats,
+                            void* stream) {
+    if (!w || !a0 || !d0 || H < 1 || W < 1 || (int64_t)H * W > (1 << 21)) return ENSLAM_EINVAL;
+    if (!chan_ok(C0) || !chan_ok(Cn) || (C1 != 0 && !chan_ok(C1)) || C0 + C1 > 1024) return ENSLAM_EUNSUPPORTED;
+    if (C1 && (H1 < 1 || W1 < 1 || oy < 0 || ox < 0 || oy + H1 > H || ox + W1 > W)) return ENSLAM_EINVAL;
+    if (C1 && (transposed ? d1 == nullptr : a1 == nullptr)) return ENSLAM_EINVAL;
+    const int Cin = transposed ? Cn : C0 + C1, N = transposed ? C0 + C1 : Cn;
+    const int64_t need = split_floats((int64_t)H * W, Cin, N);
+    if (need > 0 && (!scratch || scratch_floats < need)) return ENSLAM_EINVAL;
+    ConvArgs a = {};
+    a.w = w; a.bias = bias; a.part = scratch; a.H = H; a.W = W; a.relu = relu; a.d0 = d0;
+    if (!transposed) {
+        a.s0 = a0; a.s1 = C1 ? a1 : nullptr; a.C0 = C0; a.C1 = C1; a.sH1 = H1; a.sW1 = W1; a.soy = oy; a.sox = ox;
+        a.N = a.N0 = Cn;
+    } else {
+        a.s0 = a0; a.mask = a1; a.C0 = Cn;
+        a.N = C0 + C1; a.N0 = C0; a.d1 = C1 ? d1 : nullptr; a.dH1 = H1; a.dW1 = W1; a.doy = oy; a.dox = ox;
+    }
+    launch_conv(a, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+int enslam_eventnet_pool2(const float* in, int32_t H, int32_t W, int32_t C, const float* g_out, float* out, int32_t backward,
+                          void* stream) {
+    if (!in || !out || (backward && !g_out) || H < 2 || W < 2 || C < 1 || (int64_t)H * W > (1 << 21)) return ENSLAM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (backward) pool2_bwd_kernel<<<blocks_of((int64_t)H * W * C), 256, 0, st>>>(in, H, W, C, g_out, out, 0);
+    else pool2_fwd_kernel<<<blocks_of((int64_t)(H / 2) * (W / 2) * C), 256, 0, st>>>(in, H, W, C, out);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+int enslam_eventnet_up2(const float* in, int32_t h, int32_t w, int32_t C, float* out, int32_t backward, void* stream) {
+    if (!in || !out || h < 1 || w < 1 || C < 1 || (int64_t)h * w > (1 << 19)) return ENSLAM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (backward) up2_bwd_kernel<<<blocks_of((int64_t)h * w * C), 256, 0, st>>>(in, h, w, C, out, 0);
+    else up2_fwd_kernel<<<blocks_of((int64_t)4 * h * w * C), 256, 0, st>>>(in, h, w, C, out);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+}  // extern "C"

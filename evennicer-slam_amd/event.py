@@ -5,7 +5,8 @@ Reference: src/Tracker.py:129-150 (ground-truth event / mask / previous colour i
 (`inference_event`: the two colour images -> `UNet_2heads(6, 2, 2)` -> events * P(event)), :206-228 (L2 event loss,
 optionally on Gaussian-blurred images, scaled by `event.balancer`).
 
-The U-Net is a caller-side network and stays a PyTorch-ROCm module (north_star); it is written here from its
+The U-Net is a caller-side network and a PyTorch-ROCm module by default (north_star); `compile_event_net` at the end of
+this file is its opt-in device route (csrc/event_net.hip: forward and input gradient, frozen eval-mode weights).  It is written here from its
 published architecture (5-level U-Net with bilinear up-sampling and two decoder heads) with the parameter names of
 the reference checkpoints (event_net/unet_model.py:72-122, event_net/unet_parts.py), so
 `pretrained/eventnet_2head_*.pth` loads with `load_state_dict`.  torchvision is not part of this image: the two
@@ -206,3 +207,139 @@ def event_loss(gt_event, full_event, blur=True, kernel_sizes=(9,), unblurred_wei
             preds.append(p)
             terms.append(t)
     return loss, gts, preds, terms
+
+
+# ------------------------------------------------------------------------------------------------
+# the event network on the device (csrc/event_net.hip): opt-in, forward and input gradient only
+# ------------------------------------------------------------------------------------------------
+def _conv_pairs(net):
+    """The 13 `_ConvPair`s in packing order: inc, down1..4, then per head up1..up4."""
+    pairs = [net.inc] + [getattr(net, f'down{i}').maxpool_conv[1] for i in (1, 2, 3, 4)]
+    for head in (1, 2):
+        pairs += [getattr(net, f'up{lvl}_{head}').conv for lvl in (1, 2, 3, 4)]
+    return pairs
+
+
+# (cin, cout) of the 26 convolutions in packing order (EN_CONV of csrc/event_net.hip; the first cin is 6 padded to 8)
+EVENTNET_CONVS = ((8, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 512), (512, 512), (512, 512),
+                  (512, 512)) + ((1024, 512), (512, 256), (512, 256), (256, 128), (256, 128), (128, 64), (128, 64), (64, 64)) * 2
+EVENTNET_HEADS_FLOATS = 264
+
+
+def check_event_net(net):
+    """Raise NotImplementedError unless `net` is what the device route implements: UNet_2heads(6, 2, 2), bilinear, the
+    reference's widths, eval mode, every parameter frozen."""
+    if not isinstance(net, UNet_2heads):
+        raise NotImplementedError(f"the HIP event network implements UNet_2heads only, not {type(net).__name__}")
+    if not net.bilinear:
+        raise NotImplementedError("the HIP event network implements bilinear=True only (no transposed-convolution up-sampling)")
+    if (net.n_channels, net.n_classes1, net.n_classes2) != (6, 2, 2):
+        raise NotImplementedError("the HIP event network implements UNet_2heads(6, 2, 2) only, got "
+                                  f"({net.n_channels}, {net.n_classes1}, {net.n_classes2})")
+    convs = [m for pair in _conv_pairs(net) for m in (pair.double_conv[0], pair.double_conv[3])]
+    got = tuple((c.in_channels, c.out_channels) for c in convs)
+    if got != ((6, 64),) + EVENTNET_CONVS[1:]:
+        raise NotImplementedError(f"the HIP event network implements the widths {UNet_2heads.WIDTHS} only")
+    if net.training:
+        raise NotImplementedError("the HIP event network runs eval mode only (BatchNorm folds into the convolutions): call "
+                                  "net.eval() first")
+    hot = [n for n, p in net.named_parameters() if p.requires_grad]
+    if hot:
+        raise NotImplementedError(f"{len(hot)} parameters of the event network require gradients (first: {hot[0]}); the HIP "
+                                  "route builds no weight gradients. Freeze the net as the tracker's use implies: "
+                                  "net.requires_grad_(False)")
+
+
+def fold_event_net(net):
+    """[(w' float64 [cout,cin,3,3], b' float64 [cout])] of the 26 conv + BN pairs in packing order, folded in float64:
+    w' = w * gamma / sqrt(var + eps), b' = beta + (conv bias - mean) * gamma / sqrt(var + eps)."""
+    out = []
+    for pair in _conv_pairs(net):
+        for conv, bn in ((pair.double_conv[0], pair.double_conv[1]), (pair.double_conv[3], pair.double_conv[4])):
+            w = conv.weight.detach().cpu().double()
+            s = bn.weight.detach().cpu().double() / torch.sqrt(bn.running_var.detach().cpu().double() + bn.eps)
+            shift = -bn.running_mean.detach().cpu().double()
+            if conv.bias is not None:
+                shift = shift + conv.bias.detach().cpu().double()
+            out.append((w * s[:, None, None, None], bn.bias.detach().cpu().double() + shift * s))
+    return out
+
+
+def pack_conv(w, b):
+    """One folded convolution (float32 w [cout,cin,3,3], b [cout]) in the kernels' layout: Wf [9 cin'][cout] (row
+    tap * cin' + ci, tap = 3 ky + kx, cin' = cin padded to a multiple of 8) | b | Wt [9 cout][cin'] (row tap * cout + co,
+    holding w[co, ci, 2 - ky, 2 - kx]: the input gradient is the forward kernel on it)."""
+    cout, cin = w.shape[:2]
+    if cin % 8:
+        w = F.pad(w, [0, 0, 0, 0, 0, 8 - cin % 8])
+    wf = w.permute(2, 3, 1, 0).reshape(-1)
+    wt = w.flip(2, 3).permute(2, 3, 0, 1).reshape(-1)
+    return torch.cat([wf, b, wt])
+
+
+def pack_event_net(net):
+    """The float32 weight image of include/enslam_hip.h (enslam_eventnet_forward), on the CPU: fold in float64, round once."""
+    parts = [pack_conv(w.float(), b.float()) for w, b in fold_event_net(net)]
+    heads = torch.zeros(EVENTNET_HEADS_FLOATS)
+    for h, at_w, at_b in ((1, 0, 256), (2, 128, 258)):
+        c = getattr(net, f'outc_{h}').conv
+        heads[at_w:at_w + 128] = c.weight.detach().cpu().float().reshape(-1)
+        heads[at_b:at_b + 2] = c.bias.detach().cpu().float()
+    return torch.cat(parts + [heads]).contiguous()
+
+
+class HipUNet2Heads(nn.Module):
+    """`UNet_2heads.forward` on the device route: `forward(x[1,6,H,W]) -> (events [1,2,H,W], probs [1,2,H,W])`,
+    differentiable in x only.  Wraps a frozen eval-mode net (kept as `self.net`); its weights are folded and packed on
+    first use and again whenever a parameter or buffer of the net has changed (their `_version`s are remembered), except
+    inside a graph capture.  One workspace per (H, W), allocated on first use and kept."""
+
+    def __init__(self, net):
+        super().__init__()
+        check_event_net(net)
+        self.net = net
+        self._packed = None
+        self._versions = None
+        self._workspaces = {}
+
+    def _tensors(self):
+        return list(self.net.parameters()) + list(self.net.buffers())
+
+    def _stamp(self):
+        return tuple((t.data_ptr(), t._version) for t in self._tensors())
+
+    def packed(self, device):
+        from . import functional as EF
+        if self._packed is not None and (EF._capturing() or (self._packed.device == device and self._versions == self._stamp())):
+            return self._packed
+        if EF._capturing():
+            raise RuntimeError("HipUNet2Heads: run one call outside the graph capture first (the weights are packed there)")
+        check_event_net(self.net)
+        stamp = self._stamp()
+        self._packed = pack_event_net(self.net).to(device)
+        self._versions = stamp
+        return self._packed
+
+    def forward(self, x):
+        from . import functional as EF
+        if not x.is_cuda:
+            raise NotImplementedError(f"the HIP event network needs its input on a HIP device (got {x.device}); use the torch "
+                                      "module on the CPU")
+        if x.dim() != 4 or x.shape[0] != 1:
+            raise NotImplementedError(f"the HIP event network runs batch 1 only (got an input of shape {tuple(x.shape)})")
+        if x.shape[1] != 6 or x.shape[2] < 16 or x.shape[3] < 16:
+            raise NotImplementedError(f"the HIP event network takes [1,6,H,W] with H, W >= 16 (got {tuple(x.shape)})")
+        if self.net.training:
+            raise NotImplementedError("the HIP event network runs eval mode only: call .eval()")
+        packed = self.packed(x.device)
+        key = (int(x.shape[2]), int(x.shape[3]), x.device)
+        ws = self._workspaces.get(key)
+        if ws is None:
+            ws = self._workspaces[key] = EF.EventNetWorkspace(key[0], key[1], x.device)
+        return EF.eventnet_apply(x, packed, ws)
+
+
+def compile_event_net(net):
+    """The device route of a frozen, eval-mode `UNet_2heads(6, 2, 2)`: same call signature and output shapes, so it drops in
+    as `slam.event_net` / `inference_event(net=...)`.  Raises NotImplementedError for anything it does not implement."""
+    return HipUNet2Heads(net)

@@ -2407,3 +2407,65 @@ def composite_density(raw, z_vals, rays_d):
     """(depth f64 [N], var f64 [N], rgb f32 [N,3], weights f32 [N,S]) of raw [N,S,4] (sigma = volume density), z_vals
     [N,S], rays_d [N,3]: raw2outputs_nerf_color(occupancy=False)."""
     return _CompositeDensityFn.apply(raw, z_vals, rays_d)
+
+
+# ------------------------------------------------------------------------------------------------
+# event network (csrc/event_net.hip; event.compile_event_net is the public face)
+# ------------------------------------------------------------------------------------------------
+class EventNetWorkspace:
+    """The device workspace of one image size: saved activations, gradient scratch, split-reduction partials.  `generation`
+    counts the forwards that have written it, so a backward can tell whether it still holds ITS forward."""
+
+    def __init__(self, H, W, device):
+        n = L.lib().enslam_eventnet_workspace_floats(H, W)
+        if n == 0:
+            raise L.EnslamError(f"event network: unsupported image size {H} x {W}")
+        self.H, self.W = H, W
+        self.buf = torch.empty(n, dtype=torch.float32, device=device)
+        self.generation = 0
+
+
+eventnet_launches = {'forward': 0, 'backward': 0}        # calls made so far (tests read it)
+
+
+def eventnet_forward(packed, x, ws):
+    """x float32 contiguous [1,6,H,W] -> (events, probs) [1,2,H,W]; leaves the activations in `ws`."""
+    events = torch.empty((1, 2, ws.H, ws.W), dtype=torch.float32, device=x.device)
+    probs = torch.empty_like(events)
+    L.check(L.lib().enslam_eventnet_forward(_ptr(packed), _ptr(x), ws.H, ws.W, _ptr(ws.buf), _ptr(events), _ptr(probs),
+                                            _stream()), "enslam_eventnet_forward")
+    ws.generation += 1
+    eventnet_launches['forward'] += 1
+    return events, probs
+
+
+def eventnet_backward(packed, ws, g_events, g_probs):
+    g_x = torch.empty((1, 6, ws.H, ws.W), dtype=torch.float32, device=g_events.device)
+    L.check(L.lib().enslam_eventnet_backward(_ptr(packed), _ptr(ws.buf), _ptr(g_events), _ptr(g_probs), _ptr(g_x), ws.H, ws.W,
+                                             _stream()), "enslam_eventnet_backward")
+    eventnet_launches['backward'] += 1
+    return g_x
+
+
+class _EventNetFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, packed, ws):
+        xc = _f32c(x)
+        events, probs = eventnet_forward(packed, xc, ws)
+        ctx.packed, ctx.ws, ctx.generation = packed, ws, ws.generation
+        ctx.save_for_backward(xc)
+        return events, probs
+
+    @staticmethod
+    def backward(ctx, g_events, g_probs):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        ws = ctx.ws
+        if ws.generation != ctx.generation:              # another forward of this size ran in between: restore the activations
+            eventnet_forward(ctx.packed, ctx.saved_tensors[0], ws)
+        return eventnet_backward(ctx.packed, ws, _f32c(g_events), _f32c(g_probs)), None, None
+
+
+def eventnet_apply(x, packed, ws):
+    _require_hip(x, "the event network's input")
+    return _EventNetFn.apply(x, packed, ws)

@@ -104,6 +104,10 @@ class SLAM:
         os.makedirs(self.ckptsdir, exist_ok=True)
         self.nice = True
         self.renderer = Renderer(cfg, None, self)
+        if event_net is not None and (cfg.get('event') or {}).get('net_backend', 'torch') == 'hip':
+            from .event import HipUNet2Heads, compile_event_net
+            if not isinstance(event_net, HipUNet2Heads):
+                event_net = compile_event_net(event_net)
         self.event_net = event_net
         self.low_gpu_mem = False
         self.logger = Logger(cfg, None, self)

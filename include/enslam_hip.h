@@ -783,6 +783,39 @@ int enslam_composite_density_bwd(int32_t n_rays, int32_t n_samples, const float 
                                  const float *rays_d, const double *depth, const double *g_depth, const double *g_var,
                                  const float *g_rgb, float *d_raw, float *d_rays_d, void *stream);
 
+/* Event network (event.py: UNet_2heads(6, 2, 2), bilinear=True, eval mode, frozen weights, batch 1, float32): forward and the
+ * gradient with respect to the input image, reference event_net/unet_model.py:72-122 and unet_parts.py.  Conv + BatchNorm
+ * pairs arrive folded (event.py: pack_event_net folds in float64 and rounds once).  Activations are channels-last
+ * ([H*W][C]) inside; x / g_x are [6,H,W], events / probs and their gradients [2,H,W].  Deterministic: no atomics, partial
+ * sums reduced in a fixed order.  H, W >= 16 (four poolings).
+ *   packed     float32 [enslam_eventnet_pack_floats]: per convolution, in the order inc.{0,1}, down1..4.{0,1}, then per head
+ *              up1..up4.{0,1} (26 in all):  Wf [9 cin][cout] (row = tap * cin + ci, tap = 3 ky + kx; the first layer's cin 6
+ *              padded to 8 with zeros) | b [cout] | Wt [9 cout][cin] (row = tap * cout + co, holding w[8 - tap][ci][co]: the
+ *              input gradient is the same kernel on it);  then the heads: W1 [2][64] | W2 [2][64] | b1 [2] | b2 [2] | pad to 264.
+ *   workspace  float32 [enslam_eventnet_workspace_floats]: every saved activation, gradient scratch and split-reduction
+ *              partials; the backward reads what the LAST forward on this workspace left.
+ * The single-operation entries exist for the tests.  conv3x3: an H x W pixel grid; the "two-part side" has C0 channels at
+ * [H*W][C0] and, with C1 > 0, C1 more at [H1*W1][C1] placed at offset (oy, ox) inside the grid (zero outside it); the
+ * "single side" has Cn channels.  transposed == 0: out[H*W][Cn] = act(sum in[p + tap][c] w[tap (C0 + C1) + c][n] + bias[n])
+ * with a0 / a1 the two inputs and d0 the output.  transposed != 0: a0 [H*W][Cn] is the incoming gradient, counted only where
+ * a1 (same layout, may be NULL) is > 0; w is [9 Cn][C0 + C1]; channels [0, C0) go to d0, the rest to d1 [H1*W1][C1].  Every
+ * channel count a multiple of 8, at most 1024 (else ENSLAM_EUNSUPPORTED); bias may be NULL.  scratch: 2^22 + H W N floats
+ * (N the output channel count) always suffice.  pool2: nn.MaxPool2d(2) of in [H][W][C] -> out [H/2][W/2][C]; backward != 0:
+ * out [H][W][C] = gradient of in from g_out [H/2][W/2][C] (first maximum in row-major order).  up2: x2 bilinear,
+ * align_corners=True, in [h][w][C] -> out [2h][2w][C]; backward != 0: in is the gradient [2h][2w][C], out [h][w][C]. */
+size_t enslam_eventnet_pack_floats(void);
+size_t enslam_eventnet_workspace_floats(int32_t H, int32_t W);     /* 0: unsupported size */
+int enslam_eventnet_forward(const float *packed, const float *x, int32_t H, int32_t W, float *workspace, float *events,
+                            float *probs, void *stream);
+int enslam_eventnet_backward(const float *packed, float *workspace, const float *g_events, const float *g_probs, float *g_x,
+                             int32_t H, int32_t W, void *stream);
+int enslam_eventnet_conv3x3(const float *w, const float *bias, int32_t H, int32_t W, int32_t C0, int32_t C1, int32_t H1,
+                            int32_t W1, int32_t oy, int32_t ox, int32_t Cn, const float *a0, const float *a1, float *d0,
+                            float *d1, int32_t relu, int32_t transposed, float *scratch, int64_t scratch_floats, void *stream);
+int enslam_eventnet_pool2(const float *in, int32_t H, int32_t W, int32_t C, const float *g_out, float *out, int32_t backward,
+                          void *stream);
+int enslam_eventnet_up2(const float *in, int32_t h, int32_t w, int32_t C, float *out, int32_t backward, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

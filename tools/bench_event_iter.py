@@ -5,11 +5,15 @@ blurred-L2 event loss (kernel 9, balancer 0.025) -> backward to the 7 pose numbe
 Reports the path alone (render + backward of the rescaled image) and path + U-Net + losses."""
 import os, sys, time, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import argparse
 import torch
 import bench
 import evennicer_slam_amd as E
 from evennicer_slam_amd.mapper import FusedAdam
 
+_ap = argparse.ArgumentParser()
+_ap.add_argument('--net-backend', choices=('torch', 'hip'), default='torch', help='event network route')
+ARGS = _ap.parse_args()
 dev = torch.device('cuda', 0)
 DEV = 'cuda:0'
 sc = bench.build_scene_cpu('room0', 0)
@@ -33,6 +37,9 @@ torch.manual_seed(0)
 net = E.event.UNet_2heads(6, 2, 2)
 for p in net.parameters(): p.requires_grad_(False)
 net = net.to(dev).eval()
+if ARGS.net_backend == 'hip':            # the device route of the same weights (event.compile_event_net), packed by one eager call
+    net = E.event.compile_event_net(net)
+    with torch.no_grad(): net(torch.rand(1, 6, int(bench.CAM['H'] * 0.15), int(bench.CAM['W'] * 0.15), device=dev))
 if os.environ.get('CHANNELS_LAST', '0') == '1':
     net = net.to(memory_format=torch.channels_last)
 slam = types.SimpleNamespace(nice=True, bound=sc['bound'], renderer=renderer, event_net=net, low_gpu_mem=False, **bench.CAM)

@@ -11,12 +11,16 @@ mapping round like Tracker.update_para_from_mapping).  Mapper: MaskedGridOptimiz
 iteration, write_back after the round."""
 import copy, os, sys, time, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import argparse
 import torch
 import bench
 import evennicer_slam_amd as E
 from evennicer_slam_amd.mapper import MaskedGridOptimizer, FusedAdam
 from evennicer_slam_amd.graph import GraphedStep
 
+_ap = argparse.ArgumentParser()
+_ap.add_argument('--net-backend', choices=('torch', 'hip'), default='torch', help='event network route')
+ARGS = _ap.parse_args()
 dev = torch.device('cuda', 0)
 DEV = 'cuda:0'
 FRAMES = int(os.environ.get('FRAMES', 20))
@@ -80,6 +84,9 @@ torch.manual_seed(0)
 net = E.event.UNet_2heads(6, 2, 2)
 for p in net.parameters(): p.requires_grad_(False)
 net = net.to(dev).eval()
+if ARGS.net_backend == 'hip':            # the device route of the same weights (event.compile_event_net), packed by one eager call
+    net = E.event.compile_event_net(net)
+    with torch.no_grad(): net(torch.rand(1, 6, int(bench.CAM['H'] * 0.15), int(bench.CAM['W'] * 0.15), device=dev))
 t_renderer = E.Renderer(sc['cfg'], None, types.SimpleNamespace(nice=True, bound=sc['bound'], **bench.CAM))
 slam = types.SimpleNamespace(nice=True, bound=sc['bound'], renderer=t_renderer, event_net=net, low_gpu_mem=False, **bench.CAM)
 trk = E.tracker.TrackerIteration(cfg, None, slam)
