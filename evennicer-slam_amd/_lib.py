@@ -163,6 +163,12 @@ _SIGS = {
     "enslam_mesh_depth_workspace": (ctypes.c_int, [c_int32, c_int32, POINTER(c_int64)]),
     "enslam_mesh_depth": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_double,
                                          c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "enslam_scene_normals": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "enslam_scene_raster_workspace": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "enslam_scene_raster": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                           c_int32, c_void_p, c_int32, c_int32, c_int32, c_double, c_double, c_double, c_double,
+                                           c_double, c_double, c_int32, c_double, ctypes.c_uint32, c_int32, c_void_p, c_int64, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
     "enslam_frame_plan_bytes": (c_int64, []),
     "enslam_frame_prepare": (ctypes.c_int, [POINTER(FramePlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),

@@ -2109,6 +2109,108 @@ def mesh_depth(vertices, faces, w2c, cam, z_near=0.0, z_far=20.0):
 
 
 # ------------------------------------------------------------------------------------------------
+# Scene rasteriser (csrc/scene_raster.hip): the colour renderer of the headless visualiser (viz.py)
+# ------------------------------------------------------------------------------------------------
+def _mesh_vertices(vertices):
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype is not torch.float64:
+        raise L.EnslamError(f"vertices must be float64 [V,3] (got {vertices.dtype} {tuple(vertices.shape)})")
+    return vertices.detach().contiguous()
+
+
+def vertex_normals(vertices, faces):
+    """float64 [V,3]: Open3D's compute_vertex_normals of a mesh on a HIP device (vertices float64 [V,3], faces int32 [F,3]):
+    per vertex the unnormalised face normals (b - a) x (c - a) of its incident faces, summed in ascending face order by one
+    thread (enslam_scene_normals: the same bits in every run), then normalised; a vertex no face uses, or whose sum is zero,
+    gets zero.  A face with an index outside [0, V) is dropped.  The vertex -> face incidence is built here with torch sorts."""
+    if not vertices.is_cuda:
+        raise NotImplementedError("vertex_normals needs a HIP device")
+    lib = L.lib()
+    v = _mesh_vertices(vertices)
+    V, dev = int(v.shape[0]), v.device
+    f = _mesh_faces(faces, V)
+    if f.device != dev:
+        raise L.EnslamError("vertices and faces must live on one device")
+    F = int(f.shape[0])
+    out = torch.empty((V, 3), dtype=torch.float64, device=dev)
+    if V == 0:
+        return out
+    with torch.cuda.device(dev):
+        ok = ((f >= 0) & (f < V)).all(dim=1)
+        vert = f[ok].reshape(-1).to(torch.int64)
+        face = torch.arange(F, dtype=torch.int64, device=dev)[ok].repeat_interleave(3)
+        order = torch.argsort(vert * max(F, 1) + face)                      # by vertex, then by face: ties are the same face
+        inc = face[order].to(torch.int32).contiguous()
+        off = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+        off[1:] = torch.cumsum(torch.bincount(vert, minlength=V), 0)
+        n_inc = int(inc.shape[0])
+        L.check(lib.enslam_scene_normals(_ptr(v), V, _ptr(f) if F else None, F, _ptr(off), _ptr(inc) if n_inc else None, n_inc,
+                                         _ptr(out), _stream()), "enslam_scene_normals")
+    return out
+
+
+def scene_raster(vertices, faces, w2c, cam, colors=None, normals=None, points=None, point_colors=None, point_size=4, cull=1,
+                 z_near=0.0, z_far=1000.0, ambient=0.35, background=(255, 255, 255), want_depth=False, want_id=False,
+                 workspace_bytes=None):
+    """uint8 [K,H,W,3] colour images of a triangle mesh (vertices float64 [V,3], faces int32 [F,3]; colors uint8 [V,3] or None:
+    0.7 grey; normals float64 [V,3] or None: the face normal) and a point set (points float64 [P,3] with point_colors uint8
+    [P,3], or None) on a HIP device, from the K cameras w2c of `mesh_depth`; cam is a dict with H, W, fx, fy, cx, cy
+    (enslam_scene_raster, enslam_hip.h).  Per pixel the nearest primitive with z_near < depth <= z_far shows, a face before
+    a point at the same float32 depth and the smaller index among equals.  cull: 0 both sides, 1 triangles whose stored
+    normal points away from the eye (what the reference's viewer shows), 2 the others.  A point is a point_size x point_size
+    square of its colour; a face pixel is its interpolated vertex colour times ambient + (1 - ambient) |n^ . d^|; nothing
+    gives `background`.  With want_depth / want_id the result is the tuple (rgb, depth float32 [K,H,W] or None, id int32
+    [K,H,W] or None): depth 0 and id -1 where empty, id -2 - p for point p.  workspace_bytes: the size of the scratch
+    allocation (default: enslam_scene_raster_workspace); a smaller one shortens the list of large triangles and changes
+    nothing in the images."""
+    if not vertices.is_cuda:
+        raise NotImplementedError("scene_raster needs a HIP device")
+    lib = L.lib()
+    v = _mesh_vertices(vertices)
+    V, dev = int(v.shape[0]), v.device
+    f = _mesh_faces(faces, V)
+    F = int(f.shape[0])
+
+    def per(t, n, dtype, what):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (n, 3) or t.dtype is not dtype or t.device != dev:
+            raise L.EnslamError(f"{what} must be {dtype} [{n},3] on {dev}")
+        return t.detach().contiguous()
+
+    if f.device != dev:
+        raise L.EnslamError("vertices and faces must live on one device")
+    col, nrm = per(colors, V, torch.uint8, "colors"), per(normals, V, torch.float64, "normals")
+    P = 0 if points is None else int(points.shape[0])
+    pts, pcol = per(points, P, torch.float64, "points"), per(point_colors, P, torch.uint8, "point_colors")
+    if (pts is None) != (pcol is None):
+        raise L.EnslamError("points and point_colors come together")
+    w = torch.as_tensor(w2c)
+    if w.dim() != 3 or tuple(w.shape[1:]) not in ((3, 4), (4, 4)):
+        raise L.EnslamError(f"w2c must be [K,3,4] or [K,4,4] (got shape {tuple(w.shape)})")
+    K = int(w.shape[0])
+    w = w[:, :3].to(torch.float64).contiguous().to(dev)
+    bg = [int(c) for c in background]
+    if len(bg) != 3 or min(bg) < 0 or max(bg) > 255:
+        raise L.EnslamError(f"background must be three levels in 0..255 (got {background})")
+    H, W = int(cam['H']), int(cam['W'])
+    rgb = torch.empty((K, H, W, 3), dtype=torch.uint8, device=dev)
+    depth = torch.empty((K, H, W), dtype=torch.float32, device=dev) if want_depth else None
+    ids = torch.empty((K, H, W), dtype=torch.int32, device=dev) if want_id else None
+    with torch.cuda.device(dev):
+        nbytes = ctypes.c_int64()
+        L.check(lib.enslam_scene_raster_workspace(F, K, H, W, ctypes.byref(nbytes)), "enslam_scene_raster_workspace")
+        nbytes = nbytes.value if workspace_bytes is None else int(workspace_bytes)
+        ws = torch.empty(max(nbytes, 0), dtype=torch.uint8, device=dev)
+        L.check(lib.enslam_scene_raster(_ptr(v) if V else None, V, _ptr(f) if F else None, F, _ptr(col), _ptr(nrm),
+                                        _ptr(pts) if P else None, P, _ptr(pcol) if P else None, int(point_size), _ptr(w), K, H, W,
+                                        float(cam['fx']), float(cam['fy']), float(cam['cx']), float(cam['cy']), float(z_near),
+                                        float(z_far), int(cull), float(ambient), bg[0] | bg[1] << 8 | bg[2] << 16, 7,
+                                        _ptr(ws) if nbytes > 0 else None, nbytes, _ptr(rgb), _ptr(depth), _ptr(ids), _stream()),
+                "enslam_scene_raster")
+    return (rgb, depth, ids) if (want_depth or want_id) else rgb
+
+
+# ------------------------------------------------------------------------------------------------
 # Block-sparse TSDF volume (csrc/tsdf.hip): the raw calls; tsdf.TSDFVolume holds the arrays and allocates
 # ------------------------------------------------------------------------------------------------
 def _i32x3(v):

@@ -490,6 +490,45 @@ int enslam_mesh_depth(const double *vertices, int32_t n_verts, const int32_t *fa
                       int32_t n_views, int32_t H, int32_t W, double fx, double fy, double cx, double cy, double z_near,
                       double z_far, void *workspace, float *depth_out, void *stream);
 
+/* Colour images of a triangle mesh and a point set from K cameras: the headless renderer of the SLAM visualiser (the Open3D
+ * window of src/tools/viz.py).  Conventions, arithmetic and limits of the triangle test are those of enslam_mesh_depth.
+ *   vertices float64 [V,3], faces int32 [F,3]; vertex_colors uint8 [V,3] or NULL (0.7 grey); vertex_normals float64 [V,3] or
+ *   NULL (the face normal; also used where the interpolated normal is zero); points float64 [P,3], point_colors uint8 [P,3];
+ *   w2c float64 [K,12]; rgb_out uint8 [K,H,W,3]; depth_out float32 [K,H,W] or NULL (0 where empty); id_out int32 [K,H,W] or
+ *   NULL (the face index, -2 - p for point p, -1 where empty).
+ * Visibility: per pixel the primitive with the smallest (float32 depth, id), a face's id being its index and a point's
+ * 0x80000000 | p -- an unsigned 64-bit integer minimum, so the images are the same bits in every run and do not depend on
+ * how the views are split over calls.  cull: 0 both sides, 1 keeps triangles with det = a . (b x c) > 0 in camera space (the
+ * stored normal (b - a) x (c - a) points away from the eye: what the reference shows after it reverses the faces and hides
+ * back faces), 2 keeps det < 0.  A point of camera depth z = -p_z in (z_near, z_far] covers the point_size x point_size
+ * pixels whose first column is ceil(u - point_size / 2) and first row ceil(w - point_size / 2), u = cx + fx p_x / z,
+ * w = cy - fy p_y / z, at the constant depth z.  A face pixel is floor(255 c shade + 0.5) with c the barycentric mix of the
+ * vertex colours / 255 and shade = ambient + (1 - ambient) |n^ . d^| (two-sided); a point pixel is the point's colour; an
+ * empty pixel is `background` (r | g << 8 | b << 16).
+ * workspace_bytes: at least 264 + 8 K H W rounded up to 256; what lies beyond holds the list of triangles whose pixel box
+ * exceeds 256 pixels (8 bytes each, enslam_scene_raster_workspace gives room for all that can be used); a triangle that
+ * finds the list full is rasterised by its own thread: the images do not depend on the size.
+ * passes: 7 for an image.  The bits select the fill and the triangle pass (1), the point pass (2) and the resolve pass (4):
+ * three calls with 1, 2 and 4 on one workspace give the image of one call with 7 (tools/bench_viz.py times them so).
+ * A fixed set of launches per call.  Limits: K*H*W <= 2^31, F*K < 2^31, P*K < 2^31 (ENSLAM_EUNSUPPORTED beyond); 0 <= z_near
+ * < z_far, finite intrinsics with fx, fy != 0, cull in 0..2, passes in 1..7, 1 <= point_size <= 64, 0 <= ambient <= 1 (ENSLAM_EINVAL
+ * otherwise).  F = 0 and / or P = 0 are valid (the background shows), K = 0 is valid.
+ *
+ * enslam_scene_normals: Open3D's compute_vertex_normals.  vf_offsets int64 [V+1] and vf_faces int32 [n_incident] list, per
+ * vertex, its incident faces; the unnormalised face normals (b - a) x (c - a) are summed in the order of the list (ascending
+ * face index gives a result that is reproducible to the bit), then normalised; a zero sum stays zero.  normals_out float64
+ * [V,3]. */
+int enslam_scene_normals(const double *vertices, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                         const int64_t *vf_offsets, const int32_t *vf_faces, int64_t n_incident, double *normals_out,
+                         void *stream);
+int enslam_scene_raster_workspace(int32_t n_faces, int32_t n_views, int32_t H, int32_t W, int64_t *bytes_host);
+int enslam_scene_raster(const double *vertices, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                        const uint8_t *vertex_colors, const double *vertex_normals, const double *points, int32_t n_points,
+                        const uint8_t *point_colors, int32_t point_size, const double *w2c, int32_t n_views, int32_t H,
+                        int32_t W, double fx, double fy, double cx, double cy, double z_near, double z_far, int32_t cull,
+                        double ambient, uint32_t background, int32_t passes, void *workspace, int64_t workspace_bytes,
+                        uint8_t *rgb_out, float *depth_out, int32_t *id_out, void *stream);
+
 /* Frame preparation (the per-frame work of src/utils/datasets.py between the image decoders and the tracker): one launch
  * turns the raw decoded images of one frame into the tensors the readers hand out.
  *   color_raw  uint8 [h0,w0,C], C = 3 or C = 1 (grey, replicated to three channels)
