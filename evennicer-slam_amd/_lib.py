@@ -266,6 +266,16 @@ _SIGS = {
                                                c_void_p, c_int64, c_void_p]),
     "enslam_eventnet_pool2": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "enslam_eventnet_up2": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "enslam_eventnet_fold_pack": (ctypes.c_int, [POINTER(c_void_p), c_void_p, c_void_p]),
+    "enslam_eventnet_fold_pack_backward": (ctypes.c_int, [POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p, c_void_p]),
+    "enslam_eventnet_wgrad_scratch_floats": (c_size_t, [c_int32, c_int32]),
+    "enslam_eventnet_backward_weights": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                        c_int64, c_int32, c_int32, c_void_p]),
+    "enslam_eventnet_heads_wgrad": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                                   c_void_p]),
+    "enslam_eventnet_conv3x3_wgrad": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_int64, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

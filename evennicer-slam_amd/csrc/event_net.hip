@@ -21,6 +21,17 @@
 //                    gathers (pool: the window's first maximum in row-major order takes the gradient, torch's tie rule;
 //                    up: torch's float32 source-coordinate expression, so the interpolation weights are F.interpolate's).
 //   heads            the two 1x1 heads fused (sigmoid on head 2), and their backward into the 64-channel features.
+//
+// Training (enslam_eventnet_backward_weights) adds the gradients of the packed image itself:
+//   conv3x3_wgrad_kernel   implicit GEMM  dWf[tap * Cin + c][n] = sum_p in[p + tap][c] * G[p][n],  G = g where saved_out > 0,
+//                    on the same MFMA.  One workgroup (4 waves as 2 x 2) owns 64 weight rows x 64 output channels; the
+//                    reduction runs over the pixels in chunks of 32 staged in LDS, both operands as [pixel][row] (both are
+//                    channels-last in memory: no transpose), the next chunk's loads issued before the current chunk's
+//                    MFMAs.  The input is read as the forward reads it (zero outside the image per tap, two sources in
+//                    place).  The workgroups of the first row tile also sum G's columns: the bias gradient.  Layers with
+//                    few output tiles split the PIXEL axis over blockIdx.z; conv3x3_wgrad_reduce_kernel sums the partials
+//                    in split order (no atomics).
+//   heads_wgrad      gradients of the heads block, a fixed-order two-stage reduction over the pixels.
 #include "../../include/enslam_hip.h"
 #include "common.hpp"
 #include <algorithm>
@@ -322,6 +333,279 @@ __global__ __launch_bounds__(256) void heads_bwd_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// weight gradients
+// ---------------------------------------------------------------------------------------------------------------
+struct WgradArgs {
+    const float* s0;      // [H * W][C0]: the convolution's input ...
+    const float* s1;      // ... and its second source [sH1 * sW1][C1] at (soy, sox), zero outside; null iff C1 == 0
+    const float* g;       // [H * W][N]: gradient of the convolution's output
+    const float* saved;   // [H * W][N] or null: g counts only where saved > 0
+    float* dw;            // [9 * (C0 + C1)][N]
+    float* db;            // [N] or null
+    float* part;          // [splits][9 * (C0 + C1) * N + N]
+    int H, W, C0, C1, sH1, sW1, soy, sox, N;
+    int nchunks, cps;     // pixel chunks in all / per split
+};
+
+constexpr int EN_WG_PC = 32;          // pixels per chunk
+
+__global__ __launch_bounds__(EN_THREADS) void conv3x3_wgrad_kernel(WgradArgs a) {
+    __shared__ __attribute__((aligned(16))) float As[EN_WG_PC * EN_TM];     // [pixel][weight row]
+    __shared__ __attribute__((aligned(16))) float Bs[EN_WG_PC * EN_TN];     // [pixel][output channel]
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
+    const int r = lane & 31, h = lane >> 5;
+    const int P = a.H * a.W, Cin = a.C0 + a.C1, M = 9 * Cin;
+    const int m0 = blockIdx.x * EN_TM, n0 = blockIdx.y * EN_TN;
+    // loader roles: 4 rows / columns (q) of pixels t >> 4 and 16 + (t >> 4) of the chunk.  Cin is a multiple of 8, so the
+    // four rows share a tap and a source.
+    const int q = (t & 15) * 4, px = t >> 4;
+    const int m4 = m0 + q;
+    const bool mok = m4 < M, nok = n0 + q < a.N;           // M and N are multiples of 4
+    const int tap = mok ? m4 / Cin : 0, c = mok ? m4 - tap * Cin : 0;
+    const int dy = tap / 3 - 1, dx = tap % 3 - 1;
+    f32x4 av[2], bv[2];
+    auto load = [&](int ch) {
+        for (int i = 0; i < 2; ++i) {
+            const int p = ch * EN_WG_PC + px + 16 * i;
+            f32x4 va = splat4(0.f), vb = splat4(0.f);
+            if (p < P) {
+                const int y = p / a.W, x = p - y * a.W;
+                const int yy = y + dy, xx = x + dx;
+                if (mok && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) {
+                    if (c < a.C0) {
+                        va = ld4(a.s0 + ((int64_t)yy * a.W + xx) * a.C0 + c);
+                    } else {
+                        const int y1 = yy - a.soy, x1 = xx - a.sox;
+                        if (y1 >= 0 && y1 < a.sH1 && x1 >= 0 && x1 < a.sW1)
+                            va = ld4(a.s1 + ((int64_t)y1 * a.sW1 + x1) * a.C1 + (c - a.C0));
+                    }
+                }
+                if (nok) {
+                    const int64_t idx = (int64_t)p * a.N + n0 + q;
+                    vb = ld4(a.g + idx);
+                    if (a.saved) {
+                        const f32x4 s = ld4(a.saved + idx);
+                        for (int e = 0; e < 4; ++e) vb[e] = s[e] > 0.f ? vb[e] : 0.f;
+                    }
+                }
+            }
+            av[i] = va;
+            bv[i] = vb;
+        }
+    };
+    f32x16 acc;
+    for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+    float bsum = 0.f;                                      // column t of G, summed by the first row tile's first wave
+    const bool do_bias = blockIdx.x == 0 && t < EN_TN;
+    const int c_begin = blockIdx.z * a.cps;
+    const int c_end = min(c_begin + a.cps, a.nchunks);
+    if (c_begin < c_end) load(c_begin);
+    for (int ch = c_begin; ch < c_end; ++ch) {
+        __syncthreads();                       // every wave has finished reading the previous chunk
+        for (int i = 0; i < 2; ++i) {
+            *reinterpret_cast<f32x4*>(&As[(px + 16 * i) * EN_TM + q]) = av[i];
+            *reinterpret_cast<f32x4*>(&Bs[(px + 16 * i) * EN_TN + q]) = bv[i];
+        }
+        __syncthreads();
+        if (ch + 1 < c_end) load(ch + 1);      // in flight under this chunk's MFMAs
+        for (int kk = 0; kk < EN_WG_PC; kk += 2)
+            acc = mfma32(As[(kk + h) * EN_TM + 32 * wm + r], Bs[(kk + h) * EN_TN + 32 * wn + r], acc);
+        if (do_bias)
+            for (int kk = 0; kk < EN_WG_PC; ++kk) bsum = bsum + Bs[kk * EN_TN + t];
+    }
+    const int64_t MN = (int64_t)M * a.N;
+    const bool split = gridDim.z > 1;
+    float* dw = split ? a.part + (int64_t)blockIdx.z * (MN + a.N) : a.dw;
+    float* db = split ? dw + MN : a.db;
+    if (do_bias && db && n0 + t < a.N) db[n0 + t] = bsum;
+    const int n = n0 + 32 * wn + r;
+    if (n >= a.N) return;
+    for (int v = 0; v < 16; ++v) {
+        const int m = m0 + 32 * wm + c_row(v, lane);
+        if (m < M) dw[(int64_t)m * a.N + n] = acc[v];
+    }
+}
+
+__global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(WgradArgs a, int splits) {
+    const int64_t MN = (int64_t)9 * (a.C0 + a.C1) * a.N, total = MN + a.N;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    float s = a.part[i];
+    for (int k = 1; k < splits; ++k) s = s + a.part[k * total + i];     // fixed order
+    if (i < MN) a.dw[i] = s;
+    else if (a.db) a.db[i - MN] = s;
+}
+
+// Heads block gradient, stage 1: block b sums its pixel range.  Thread t owns weight t of W1 | W2 ([2][2][64]: head, row,
+// channel); the threads of channel 0 also own the row's bias.  part [blocks][260].
+__global__ __launch_bounds__(256) void heads_wgrad_kernel(const float* __restrict__ g_events, const float* __restrict__ g_probs,
+                                                          const float* __restrict__ probs, const float* __restrict__ f1,
+                                                          const float* __restrict__ f2, int P, int per_block,
+                                                          float* __restrict__ part) {
+    const int t = threadIdx.x, head = t >> 7, row = (t >> 6) & 1, c = t & 63;
+    const float* g = (head ? g_probs : g_events) + (int64_t)row * P;
+    const float* pr = probs + (int64_t)row * P;
+    const float* f = head ? f2 : f1;
+    const int p_begin = blockIdx.x * per_block, p_end = min(p_begin + per_block, P);
+    float sw = 0.f, sb = 0.f;
+    for (int p = p_begin; p < p_end; ++p) {
+        float gv = g[p];
+        if (head) {
+            const float qv = pr[p];
+            gv = gv * (qv * (1.f - qv));
+        }
+        sw = fmaf(gv, f[(int64_t)p * 64 + c], sw);
+        sb = sb + gv;
+    }
+    part[(int64_t)blockIdx.x * 260 + t] = sw;
+    if (c == 0) part[(int64_t)blockIdx.x * 260 + 256 + 2 * head + row] = sb;
+}
+
+// stage 2: the partials in block order; the pad of the heads block is written as zero
+__global__ __launch_bounds__(EN_HEADS_FLOATS) void heads_wgrad_reduce_kernel(const float* __restrict__ part, int blocks,
+                                                                             float* __restrict__ g_heads) {
+    const int t = threadIdx.x;
+    float s = 0.f;
+    if (t < 260) {
+        s = part[t];
+        for (int b = 1; b < blocks; ++b) s = s + part[(int64_t)b * 260 + t];
+    }
+    g_heads[t] = s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The packed image from live parameters, and its chain rule back to them (training: the weights change every step).
+// One convolution: Wf, b, Wt of event.pack_conv from w [cout][cin][3][3], BatchNorm gamma / beta and the host's float64
+// sq = sqrt(var + eps), shift = -mean, with event.fold_event_net's float64 operations in its order, rounded once:
+//   s = gamma / sq,  w' = float(w * s),  b' = float(beta + shift * s).
+// A workgroup moves a 32 (cout) x 32 (cin) x 9 tile through LDS so that reads and writes are both contiguous runs.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int EN_FT = 32;                     // tile edge in output and in input channels
+constexpr int EN_FLD = EN_FT * 9 + 1;         // LDS row stride (floats): 289, odd, so columns spread over the banks
+
+struct FoldArgs {
+    const float* w;        // [cout][cin][3][3]
+    const float* gamma;    // [cout]
+    const float* beta;     // [cout]
+    const double* sq;      // [cout]
+    const double* shift;   // [cout]
+    float* wf;             // [9 cinp][cout]   (forward: written; backward: the gradient, read)
+    float* b;              // [cout]
+    float* wt;             // [9 cout][cinp]   (forward only)
+    float* dw;             // [cout][cin][3][3]                 (backward)
+    double* part;          // [cinp / 32 tiles][cout]           (backward: per-tile sums of dWf * w)
+    float* dgamma;         // [cout]                            (backward)
+    float* dbeta;          // [cout]                            (backward)
+    int cin, cinp, cout;
+};
+// all 26 convolutions in one launch: workgroup blockIdx.x belongs to convolution i with first[i] <= blockIdx.x < first[i + 1]
+struct FoldTable {
+    FoldArgs a[EN_NCONV];
+    int first[EN_NCONV + 1];
+};
+static_assert(sizeof(FoldTable) <= 4096, "FoldTable travels as a kernel argument");
+
+ENS_DEV int fold_locate(const FoldTable& tb, int& bx, int& by) {
+    int i = 0;
+    while (i + 1 < EN_NCONV && (int)blockIdx.x >= tb.first[i + 1]) ++i;
+    const int local = blockIdx.x - tb.first[i], tiles = (tb.a[i].cinp + EN_FT - 1) / EN_FT;
+    bx = local % tiles;
+    by = local / tiles;
+    return i;
+}
+
+__global__ __launch_bounds__(256) void fold_pack_kernel(FoldTable tb) {
+    __shared__ float tile[EN_FT * EN_FLD];
+    __shared__ double sS[EN_FT];
+    int bx, by;
+    const FoldArgs a = tb.a[fold_locate(tb, bx, by)];
+    const int t = threadIdx.x, ci0 = bx * EN_FT, co0 = by * EN_FT;
+    if (t < EN_FT) {
+        const int co = co0 + t;
+        const double s = co < a.cout ? (double)a.gamma[co] / a.sq[co] : 0.0;
+        sS[t] = s;
+        if (bx == 0 && co < a.cout) a.b[co] = (float)((double)a.beta[co] + a.shift[co] * s);
+    }
+    __syncthreads();
+    for (int e = t; e < EN_FT * EN_FT * 9; e += 256) {
+        const int row = e / (EN_FT * 9), col = e - row * (EN_FT * 9);
+        const int co = co0 + row, ci = ci0 + col / 9;
+        float v = 0.f;
+        if (co < a.cout && ci < a.cin) v = (float)((double)a.w[((int64_t)co * a.cin + ci0) * 9 + col] * sS[row]);
+        tile[row * EN_FLD + col] = v;
+    }
+    __syncthreads();
+    for (int e = t; e < EN_FT * EN_FT * 9; e += 256) {
+        const int lo = e & (EN_FT - 1), mid = (e >> 5) & (EN_FT - 1), tap = e >> 10;
+        // Wf: lo = cout, mid = cin
+        if (co0 + lo < a.cout && ci0 + mid < a.cinp)
+            a.wf[((int64_t)tap * a.cinp + ci0 + mid) * a.cout + co0 + lo] = tile[lo * EN_FLD + mid * 9 + tap];
+        // Wt: lo = cin, mid = cout, the flipped tap
+        if (co0 + mid < a.cout && ci0 + lo < a.cinp)
+            a.wt[((int64_t)tap * a.cout + co0 + mid) * a.cinp + ci0 + lo] = tile[mid * EN_FLD + lo * 9 + (8 - tap)];
+    }
+}
+
+// dw = float(dWf * s) in w's layout, and per (cin tile, cout) the float64 sum of dWf * w in a fixed order
+__global__ __launch_bounds__(256) void fold_pack_bwd_kernel(FoldTable tb) {
+    __shared__ float tile[EN_FT * EN_FLD];
+    __shared__ double red[256];
+    __shared__ double sS[EN_FT];
+    int bx, by;
+    const FoldArgs a = tb.a[fold_locate(tb, bx, by)];
+    const int t = threadIdx.x, ci0 = bx * EN_FT, co0 = by * EN_FT;
+    if (t < EN_FT) sS[t] = co0 + t < a.cout ? (double)a.gamma[co0 + t] / a.sq[co0 + t] : 0.0;
+    for (int e = t; e < EN_FT * EN_FT * 9; e += 256) {
+        const int lo = e & (EN_FT - 1), mid = (e >> 5) & (EN_FT - 1), tap = e >> 10;
+        float v = 0.f;
+        if (co0 + lo < a.cout && ci0 + mid < a.cinp) v = a.wf[((int64_t)tap * a.cinp + ci0 + mid) * a.cout + co0 + lo];
+        tile[lo * EN_FLD + mid * 9 + tap] = v;
+    }
+    __syncthreads();
+    // 8 threads per row, each a contiguous run of 36 columns
+    const int row = t >> 3, sub = t & 7, co = co0 + row;
+    double acc = 0.0;
+    for (int k = 0; k < 36; ++k) {
+        const int col = sub * 36 + k, ci = ci0 + col / 9;
+        if (co < a.cout && ci < a.cin) {
+            const int64_t at = ((int64_t)co * a.cin + ci0) * 9 + col;
+            const double g = (double)tile[row * EN_FLD + col];
+            a.dw[at] = (float)(g * sS[row]);
+            acc = acc + g * (double)a.w[at];
+        }
+    }
+    red[t] = acc;
+    __syncthreads();
+    if (sub == 0 && co < a.cout) {
+        double sum = red[t];
+        for (int k = 1; k < 8; ++k) sum = sum + red[t + k];
+        a.part[(int64_t)bx * a.cout + co] = sum;
+    }
+}
+
+// dgamma = float((sum over the cin tiles + shift * db) / sq), dbeta = db; blockIdx.y is the convolution
+__global__ __launch_bounds__(256) void fold_pack_bwd_finish_kernel(FoldTable tb) {
+    const FoldArgs a = tb.a[blockIdx.y];
+    const int co = blockIdx.x * blockDim.x + threadIdx.x, tiles = (a.cinp + EN_FT - 1) / EN_FT;
+    if (co >= a.cout) return;
+    double sum = a.part[co];
+    for (int k = 1; k < tiles; ++k) sum = sum + a.part[(int64_t)k * a.cout + co];
+    const float db = a.b[co];
+    sum = sum + (double)db * a.shift[co];
+    a.dgamma[co] = (float)(sum / a.sq[co]);
+    a.dbeta[co] = db;
+}
+
+// heads block: pack (dir 0: parameters -> block, pad zero) or unpack (dir 1: block gradient -> parameter gradients)
+__global__ __launch_bounds__(EN_HEADS_FLOATS) void heads_pack_kernel(float* w1, float* w2, float* b1, float* b2, float* block,
+                                                                     int dir) {
+    const int t = threadIdx.x;
+    float* q = t < 128 ? w1 + t : t < 256 ? w2 + (t - 128) : t < 258 ? b1 + (t - 256) : t < 260 ? b2 + (t - 258) : nullptr;
+    if (dir == 0) block[t] = q ? *q : 0.f;
+    else if (q) *q = block[t];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 struct SplitPlan { int ptiles, ntiles, nchunks, cps, splits; };
@@ -358,6 +642,45 @@ int launch_conv(ConvArgs a, hipStream_t st) {
 }
 
 inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// Weight gradient: the tiles cover the 9 Cin x N weight block and the reduction runs over the pixels, so the PIXEL axis is
+// what a layer with few tiles splits -- the same rule as split_plan (below EN_SPLIT_BELOW tiles, to about EN_SPLIT_TARGET
+// workgroups), counted in chunks of EN_WG_PC pixels.
+struct WgradPlan { int mtiles, ntiles, nchunks, cps, splits; };
+WgradPlan wgrad_plan(int64_t P, int Cin, int N) {
+    WgradPlan s;
+    s.mtiles = (9 * Cin + EN_TM - 1) / EN_TM;
+    s.ntiles = (N + EN_TN - 1) / EN_TN;
+    s.nchunks = (int)((P + EN_WG_PC - 1) / EN_WG_PC);
+    s.cps = s.nchunks;
+    const int64_t tiles = (int64_t)s.mtiles * s.ntiles;
+    if (tiles < EN_SPLIT_BELOW) {
+        const int want = (int)std::min<int64_t>(s.nchunks, (EN_SPLIT_TARGET + tiles - 1) / tiles);
+        s.cps = (s.nchunks + want - 1) / want;
+    }
+    s.splits = (s.nchunks + s.cps - 1) / s.cps;
+    return s;
+}
+int64_t wgrad_floats(int64_t P, int Cin, int N) {
+    const WgradPlan s = wgrad_plan(P, Cin, N);
+    return s.splits > 1 ? (int64_t)s.splits * ((int64_t)9 * Cin * N + N) : 0;
+}
+
+void launch_wgrad(WgradArgs a, hipStream_t st) {
+    const int Cin = a.C0 + a.C1;
+    const WgradPlan s = wgrad_plan((int64_t)a.H * a.W, Cin, a.N);
+    a.nchunks = s.nchunks;
+    a.cps = s.cps;
+    conv3x3_wgrad_kernel<<<dim3(s.mtiles, s.ntiles, s.splits), EN_THREADS, 0, st>>>(a);
+    if (s.splits > 1)
+        conv3x3_wgrad_reduce_kernel<<<blocks_of((int64_t)9 * Cin * a.N + a.N), 256, 0, st>>>(a, s.splits);
+}
+
+// heads: at most 256 blocks, at least 64 pixels each
+int heads_wgrad_blocks(int64_t P, int& per_block) {
+    per_block = (int)std::max<int64_t>(64, (P + 255) / 256);
+    return (int)((P + per_block - 1) / per_block);
+}
 
 // the 26 convolutions in packing order: encoder (inc, down1..4), then per head up1..up4
 struct ConvDim { int cin, cout; };
@@ -431,6 +754,17 @@ Plan make_plan(int H, int W) {
 
 bool size_ok(int H, int W) { return H >= 16 && W >= 16 && (int64_t)H * W <= (1 << 21); }
 
+// scratch of the weight gradients of an H x W image: the largest split-partial block of the 26 convolutions, or the heads'
+int64_t wgrad_scratch_floats(const Plan& pl) {
+    int per_block;
+    int64_t need = (int64_t)heads_wgrad_blocks(pl.P[0], per_block) * 260;
+    for (int l = 0; l < 5; ++l)
+        for (int k = 0; k < 2; ++k) need = std::max(need, wgrad_floats(pl.P[l], EN_CONV[2 * l + k].cin, EN_CONV[2 * l + k].cout));
+    for (int j = 0; j < 4; ++j)
+        for (int k = 0; k < 2; ++k) need = std::max(need, wgrad_floats(pl.P[3 - j], EN_CONV[10 + 2 * j + k].cin, EN_CONV[10 + 2 * j + k].cout));
+    return (need + 63) / 64 * 64;
+}
+
 }  // namespace
 
 extern "C" {
@@ -487,14 +821,17 @@ int enslam_eventnet_forward(const float* packed, const float* x, int32_t H, int3
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
 
-int enslam_eventnet_backward(const float* packed, float* workspace, const float* g_events, const float* g_probs,
-                             float* g_x, int32_t H, int32_t W, void* stream) {
-    if (!packed || !workspace || !g_events || !g_probs || !g_x) return ENSLAM_EINVAL;
-    if (!size_ok(H, W)) return ENSLAM_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+
+// The backward pass.  g_packed == null: the input gradient only (enslam_eventnet_backward).  Otherwise every layer's weight
+// gradient is launched next to its transposed convolution, while the layer's incoming gradient is still in the transient
+// buffers; g_x == null then skips the first layer's transposed convolution and the unpack.
+int run_backward(const float* packed, float* ws, const float* g_events, const float* g_probs, float* g_x, float* g_packed,
+                 float* scratch, int H, int W, hipStream_t st) {
     const Plan pl = make_plan(H, W);
     const PackOff po = pack_offsets();
-    float* ws = workspace;
     float *tA = ws + pl.t[0], *tB = ws + pl.t[1], *tC = ws + pl.t[2];
     // d(input of convolution i) from g (masked by the convolution's saved output): N0 channels to d0, the rest to d1
     auto convT = [&](int i, int Hc, int Wc, const float* g, const float* saved, float* d0, int N0, int acc0, float* d1,
@@ -506,27 +843,171 @@ int enslam_eventnet_backward(const float* packed, float* workspace, const float*
         a.H = Hc; a.W = Wc; a.N = EN_CONV[i].cin; a.N0 = N0; a.dH1 = dH1; a.dW1 = dW1; a.acc0 = acc0;
         launch_conv(a, st);
     };
+    // d(Wf, b of convolution i) from the same g and saved output, and the input(s) the forward read
+    auto wgrad = [&](int i, int Hc, int Wc, const float* s0, int C0, const float* s1, int C1, int sH1, int sW1, const float* g,
+                     const float* saved) {
+        if (!g_packed) return;
+        WgradArgs a = {};
+        a.s0 = s0; a.s1 = s1; a.g = g; a.saved = saved;
+        a.dw = g_packed + po.wf[i]; a.db = g_packed + po.b[i]; a.part = scratch;
+        a.H = Hc; a.W = Wc; a.C0 = C0; a.C1 = C1; a.sH1 = sH1; a.sW1 = sW1; a.N = EN_CONV[i].cout;
+        launch_wgrad(a, st);
+        (void)hipMemsetAsync(g_packed + po.wt[i], 0, sizeof(float) * 9 * EN_CONV[i].cin * EN_CONV[i].cout, st);   // hipGetLastError below
+    };
+    if (g_packed) {
+        int per_block;
+        const int blocks = heads_wgrad_blocks(pl.P[0], per_block);
+        heads_wgrad_kernel<<<blocks, 256, 0, st>>>(g_events, g_probs, ws + pl.probs, ws + pl.d[0][3], ws + pl.d[1][3],
+                                                   (int)pl.P[0], per_block, scratch);
+        heads_wgrad_reduce_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>(scratch, blocks, g_packed + po.heads);
+    }
     for (int hd = 0; hd < 2; ++hd) {
         heads_bwd_kernel<<<blocks_of(pl.P[0] * 64), 256, 0, st>>>(packed + po.heads, hd, hd ? g_probs : g_events,
                                                                   ws + pl.probs, (int)pl.P[0], tA);
         for (int j = 3; j >= 0; --j) {
             const int ls = 3 - j, ld = ls + 1, cd = EN_DEC_CD[j];
-            convT(11 + 8 * hd + 2 * j, pl.H[ls], pl.W[ls], tA, ws + pl.d[hd][j], tB, cd, 0, nullptr, 0, 0);
-            convT(10 + 8 * hd + 2 * j, pl.H[ls], pl.W[ls], tB, ws + pl.m[hd][j], ws + pl.df[ls], cd, hd, tC, 2 * pl.H[ld],
-                  2 * pl.W[ld]);
+            const int i1 = 11 + 8 * hd + 2 * j, i0 = i1 - 1;
+            wgrad(i1, pl.H[ls], pl.W[ls], ws + pl.m[hd][j], cd, nullptr, 0, 0, 0, tA, ws + pl.d[hd][j]);
+            convT(i1, pl.H[ls], pl.W[ls], tA, ws + pl.d[hd][j], tB, cd, 0, nullptr, 0, 0);
+            wgrad(i0, pl.H[ls], pl.W[ls], ws + pl.f[ls], cd, ws + pl.u[hd][j], cd, 2 * pl.H[ld], 2 * pl.W[ld], tB,
+                  ws + pl.m[hd][j]);
+            convT(i0, pl.H[ls], pl.W[ls], tB, ws + pl.m[hd][j], ws + pl.df[ls], cd, hd, tC, 2 * pl.H[ld], 2 * pl.W[ld]);
             float* dst = j ? tA : ws + pl.df[4];
             up2_bwd_kernel<<<blocks_of(pl.P[ld] * cd), 256, 0, st>>>(tC, pl.H[ld], pl.W[ld], cd, dst, j ? 0 : hd);
         }
     }
     for (int l = 4; l >= 0; --l) {
         const int c = EN_ENC_C[l], cin = EN_CONV[2 * l].cin;
+        wgrad(2 * l + 1, pl.H[l], pl.W[l], ws + pl.a[l], c, nullptr, 0, 0, 0, ws + pl.df[l], ws + pl.f[l]);
         convT(2 * l + 1, pl.H[l], pl.W[l], ws + pl.df[l], ws + pl.f[l], tA, c, 0, nullptr, 0, 0);
-        convT(2 * l, pl.H[l], pl.W[l], tA, ws + pl.a[l], tB, cin, 0, nullptr, 0, 0);
+        wgrad(2 * l, pl.H[l], pl.W[l], l ? ws + pl.pl[l] : ws + pl.x8, cin, nullptr, 0, 0, 0, tA, ws + pl.a[l]);
+        if (l || g_x) convT(2 * l, pl.H[l], pl.W[l], tA, ws + pl.a[l], tB, cin, 0, nullptr, 0, 0);
         if (l)
             pool2_bwd_kernel<<<blocks_of(pl.P[l - 1] * cin), 256, 0, st>>>(ws + pl.f[l - 1], pl.H[l - 1], pl.W[l - 1], cin, tB,
                                                                            ws + pl.df[l - 1], 1);
     }
-    en_unpack_gx_kernel<<<blocks_of(pl.P[0] * 6), 256, 0, st>>>(tB, (int)pl.P[0], g_x);
+    if (g_x) en_unpack_gx_kernel<<<blocks_of(pl.P[0] * 6), 256, 0, st>>>(tB, (int)pl.P[0], g_x);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+}  // namespace
+
+extern "C" {
+
+int enslam_eventnet_backward(const float* packed, float* workspace, const float* g_events, const float* g_probs,
+                             float* g_x, int32_t H, int32_t W, void* stream) {
+    if (!packed || !workspace || !g_events || !g_probs || !g_x) return ENSLAM_EINVAL;
+    if (!size_ok(H, W)) return ENSLAM_EINVAL;
+    return run_backward(packed, workspace, g_events, g_probs, g_x, nullptr, nullptr, H, W, (hipStream_t)stream);
+}
+
+size_t enslam_eventnet_wgrad_scratch_floats(int32_t H, int32_t W) {
+    if (!size_ok(H, W)) return 0;
+    return (size_t)wgrad_scratch_floats(make_plan(H, W));
+}
+
+int enslam_eventnet_backward_weights(const float* packed, float* workspace, const float* g_events, const float* g_probs,
+                                     float* g_x, float* g_packed, float* scratch, int64_t scratch_floats, int32_t H, int32_t W,
+                                     void* stream) {
+    if (!packed || !workspace || !g_events || !g_probs || !g_packed || !scratch) return ENSLAM_EINVAL;
+    if (!size_ok(H, W)) return ENSLAM_EINVAL;
+    if (scratch_floats < wgrad_scratch_floats(make_plan(H, W))) return ENSLAM_EINVAL;
+    return run_backward(packed, workspace, g_events, g_probs, g_x, g_packed, scratch, H, W, (hipStream_t)stream);
+}
+
+int enslam_eventnet_heads_wgrad(const float* workspace, const float* g_events, const float* g_probs, float* g_heads,
+                                float* scratch, int64_t scratch_floats, int32_t H, int32_t W, void* stream) {
+    if (!workspace || !g_events || !g_probs || !g_heads || !scratch) return ENSLAM_EINVAL;
+    if (!size_ok(H, W)) return ENSLAM_EINVAL;
+    const Plan pl = make_plan(H, W);
+    int per_block;
+    const int blocks = heads_wgrad_blocks(pl.P[0], per_block);
+    if (scratch_floats < (int64_t)blocks * 260) return ENSLAM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    heads_wgrad_kernel<<<blocks, 256, 0, st>>>(g_events, g_probs, workspace + pl.probs, workspace + pl.d[0][3],
+                                               workspace + pl.d[1][3], (int)pl.P[0], per_block, scratch);
+    heads_wgrad_reduce_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>(scratch, blocks, g_heads);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+}  // extern "C"
+
+namespace {
+constexpr int EN_FOLD_PART = 32 * 512;        // float64 partials per convolution: at most 32 cin tiles x 512 cout
+int fold_table(const void* const* params, FoldTable& tb) {
+    int blocks = 0;
+    for (int i = 0; i < EN_NCONV; ++i) {
+        FoldArgs& a = tb.a[i];
+        a = FoldArgs{};
+        a.w = (const float*)params[5 * i]; a.gamma = (const float*)params[5 * i + 1]; a.beta = (const float*)params[5 * i + 2];
+        a.sq = (const double*)params[5 * i + 3]; a.shift = (const double*)params[5 * i + 4];
+        a.cinp = EN_CONV[i].cin; a.cin = i ? a.cinp : 6; a.cout = EN_CONV[i].cout;
+        tb.first[i] = blocks;
+        blocks += ((a.cinp + EN_FT - 1) / EN_FT) * ((a.cout + EN_FT - 1) / EN_FT);
+    }
+    tb.first[EN_NCONV] = blocks;
+    return blocks;
+}
+}  // namespace
+
+extern "C" {
+
+/* params: per convolution 5 device addresses (w, gamma, beta, sq float64, shift float64), then W1, W2, b1, b2 of the heads */
+int enslam_eventnet_fold_pack(const void* const* params, float* packed, void* stream) {
+    if (!params || !packed) return ENSLAM_EINVAL;
+    for (int k = 0; k < 5 * EN_NCONV + 4; ++k)
+        if (!params[k]) return ENSLAM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const PackOff po = pack_offsets();
+    FoldTable tb;
+    const int blocks = fold_table(params, tb);
+    for (int i = 0; i < EN_NCONV; ++i) {
+        tb.a[i].wf = packed + po.wf[i]; tb.a[i].b = packed + po.b[i]; tb.a[i].wt = packed + po.wt[i];
+    }
+    fold_pack_kernel<<<blocks, 256, 0, st>>>(tb);
+    const void* const* h = params + 5 * EN_NCONV;
+    heads_pack_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>((float*)h[0], (float*)h[1], (float*)h[2], (float*)h[3], packed + po.heads, 0);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+/* grads: per convolution 3 device addresses (dw, dgamma, dbeta), then dW1, dW2, db1, db2; scratch: float64 [26 * 16384] */
+int enslam_eventnet_fold_pack_backward(const void* const* params, const float* g_packed, void* const* grads, double* scratch,
+                                       void* stream) {
+    if (!params || !g_packed || !grads || !scratch) return ENSLAM_EINVAL;
+    for (int k = 0; k < 5 * EN_NCONV + 4; ++k)
+        if (!params[k]) return ENSLAM_EINVAL;
+    for (int k = 0; k < 3 * EN_NCONV + 4; ++k)
+        if (!grads[k]) return ENSLAM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const PackOff po = pack_offsets();
+    FoldTable tb;
+    const int blocks = fold_table(params, tb);
+    for (int i = 0; i < EN_NCONV; ++i) {
+        FoldArgs& a = tb.a[i];
+        a.wf = const_cast<float*>(g_packed) + po.wf[i]; a.b = const_cast<float*>(g_packed) + po.b[i];
+        a.dw = (float*)grads[3 * i]; a.dgamma = (float*)grads[3 * i + 1]; a.dbeta = (float*)grads[3 * i + 2];
+        a.part = scratch + (int64_t)i * EN_FOLD_PART;
+    }
+    fold_pack_bwd_kernel<<<blocks, 256, 0, st>>>(tb);
+    fold_pack_bwd_finish_kernel<<<dim3(2, EN_NCONV), 256, 0, st>>>(tb);
+    void* const* h = grads + 3 * EN_NCONV;
+    heads_pack_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>((float*)h[0], (float*)h[1], (float*)h[2], (float*)h[3],
+                                                    const_cast<float*>(g_packed) + po.heads, 1);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+int enslam_eventnet_conv3x3_wgrad(int32_t H, int32_t W, int32_t C0, int32_t C1, int32_t H1, int32_t W1, int32_t oy, int32_t ox,
+                                  int32_t Cn, const float* a0, const float* a1, const float* g, const float* saved, float* dw,
+                                  float* db, float* scratch, int64_t scratch_floats, void* stream) {
+    if (!a0 || !g || !dw || H < 1 || W < 1 || (int64_t)H * W > (1 << 21)) return ENSLAM_EINVAL;
+    if (!chan_ok(C0) || !chan_ok(Cn) || (C1 != 0 && !chan_ok(C1)) || C0 + C1 > 1024) return ENSLAM_EUNSUPPORTED;
+    if (C1 && (!a1 || H1 < 1 || W1 < 1 || oy < 0 || ox < 0 || oy + H1 > H || ox + W1 > W)) return ENSLAM_EINVAL;
+    const int64_t need = wgrad_floats((int64_t)H * W, C0 + C1, Cn);
+    if (need > 0 && (!scratch || scratch_floats < need)) return ENSLAM_EINVAL;
+    WgradArgs a = {};
+    a.s0 = a0; a.s1 = C1 ? a1 : nullptr; a.g = g; a.saved = saved; a.dw = dw; a.db = db; a.part = scratch;
+    a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.sH1 = H1; a.sW1 = W1; a.soy = oy; a.sox = ox; a.N = Cn;
+    launch_wgrad(a, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
 

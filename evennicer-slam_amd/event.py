@@ -210,7 +210,7 @@ def event_loss(gt_event, full_event, blur=True, kernel_sizes=(9,), unblurred_wei
 
 
 # ------------------------------------------------------------------------------------------------
-# the event network on the device (csrc/event_net.hip): opt-in, forward and input gradient only
+# the event network on the device (csrc/event_net.hip): opt-in; the frozen route first, the trainable one after it
 # ------------------------------------------------------------------------------------------------
 def _conv_pairs(net):
     """The 13 `_ConvPair`s in packing order: inc, down1..4, then per head up1..up4."""
@@ -226,9 +226,9 @@ EVENTNET_CONVS = ((8, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 25
 EVENTNET_HEADS_FLOATS = 264
 
 
-def check_event_net(net):
+def check_event_net(net, frozen=True):
     """Raise NotImplementedError unless `net` is what the device route implements: UNet_2heads(6, 2, 2), bilinear, the
-    reference's widths, eval mode, every parameter frozen."""
+    reference's widths, eval mode and (`frozen`, the route of compile_event_net) every parameter frozen."""
     if not isinstance(net, UNet_2heads):
         raise NotImplementedError(f"the HIP event network implements UNet_2heads only, not {type(net).__name__}")
     if not net.bilinear:
@@ -243,11 +243,11 @@ def check_event_net(net):
     if net.training:
         raise NotImplementedError("the HIP event network runs eval mode only (BatchNorm folds into the convolutions): call "
                                   "net.eval() first")
-    hot = [n for n, p in net.named_parameters() if p.requires_grad]
+    hot = [n for n, p in net.named_parameters() if p.requires_grad] if frozen else []
     if hot:
         raise NotImplementedError(f"{len(hot)} parameters of the event network require gradients (first: {hot[0]}); the HIP "
-                                  "route builds no weight gradients. Freeze the net as the tracker's use implies: "
-                                  "net.requires_grad_(False)")
+                                  "route of compile_event_net builds no weight gradients. Freeze the net as the tracker's "
+                                  "use implies: net.requires_grad_(False), or train it through compile_event_net_trainable")
 
 
 def fold_event_net(net):
@@ -343,3 +343,122 @@ def compile_event_net(net):
     """The device route of a frozen, eval-mode `UNet_2heads(6, 2, 2)`: same call signature and output shapes, so it drops in
     as `slam.event_net` / `inference_event(net=...)`.  Raises NotImplementedError for anything it does not implement."""
     return HipUNet2Heads(net)
+
+
+# ------------------------------------------------------------------------------------------------
+# the trainable route: the packed image is built on the device from the live parameters, autograd carries its gradient
+# (csrc/event_net.hip: enslam_eventnet_backward_weights) back through the fold
+# ------------------------------------------------------------------------------------------------
+def _bn_host_constants(bn):
+    """sqrt(running_var + eps) and -running_mean in float64, computed on the host exactly as fold_event_net does."""
+    return (torch.sqrt(bn.running_var.detach().cpu().double() + bn.eps), -bn.running_mean.detach().cpu().double())
+
+
+def pack_event_net_differentiable(net, device=None, constants=None):
+    """pack_event_net(net) built on `device` from the live parameters with differentiable torch operations, bit-equal to
+    it: sqrt(var + eps) comes from the host in float64 (`constants`: a cached list of _bn_host_constants per conv + BN
+    pair, in packing order); the fold itself is fold_event_net's IEEE float64 divide, multiply and add in the same order,
+    rounded once to float32; then pack_conv's layout.  The transposed blocks are built without a graph: the image depends
+    on a weight through Wf alone, which is where enslam_eventnet_backward_weights puts its gradient."""
+    device = torch.device(device) if device is not None else next(net.parameters()).device
+    pairs = [(p.double_conv[i], p.double_conv[i + 1]) for p in _conv_pairs(net) for i in (0, 3)]
+    if constants is None:
+        constants = [_bn_host_constants(bn) for _, bn in pairs]
+    parts = []
+    for (conv, bn), (sq, shift) in zip(pairs, constants):
+        sq, shift = sq.to(device), shift.to(device)
+        s = bn.weight.to(device).double() / sq
+        if conv.bias is not None:
+            shift = shift + conv.bias.to(device).double()
+        w = (conv.weight.to(device).double() * s[:, None, None, None]).float()
+        b = (bn.bias.to(device).double() + shift * s).float()
+        if w.shape[1] % 8:
+            w = F.pad(w, [0, 0, 0, 0, 0, 8 - w.shape[1] % 8])
+        with torch.no_grad():
+            wt = w.flip(2, 3).permute(2, 3, 0, 1).reshape(-1)
+        parts += [w.permute(2, 3, 1, 0).reshape(-1), b, wt]
+    c1, c2 = net.outc_1.conv, net.outc_2.conv
+    parts += [c.weight.to(device).float().reshape(-1) for c in (c1, c2)] + [c.bias.to(device).float() for c in (c1, c2)]
+    parts.append(torch.zeros(EVENTNET_HEADS_FLOATS - 260, dtype=torch.float32, device=device))
+    return torch.cat(parts)
+
+
+class HipUNet2HeadsTrainable(nn.Module):
+    """`UNet_2heads.forward` on the device route with parameter gradients: `forward(x[1,6,H,W]) -> (events, probs)`,
+    differentiable in x and in every parameter of `self.net` that requires a gradient (convolution weights, BatchNorm
+    gamma and beta, head weights and biases).  The net stays in eval mode: BatchNorm's statistics are frozen and the
+    gradients are those of the eval-mode module.  The packed image is rebuilt from the live parameters on every call
+    (pack_event_net_differentiable); when no parameter requires a gradient the call is HipUNet2Heads', with no
+    weight-gradient launch."""
+
+    def __init__(self, net):
+        super().__init__()
+        check_event_net(net, frozen=False)
+        self.net = net
+        self._plain = {}              # the frozen route, a dict so that the net is registered once
+        self._constants = None
+        self._stamp = None
+        self._workspaces = {}
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("the HIP event network runs eval mode only (BatchNorm folds into the convolutions; its "
+                                      "statistics stay frozen while the weights train): keep it in .eval()")
+        return super().train(mode)
+
+    def _bn_constants(self, device):
+        buffers = list(self.net.buffers())
+        stamp = (device,) + tuple((t.data_ptr(), t._version) for t in buffers)
+        if self._stamp != stamp:
+            pairs = [p.double_conv[i + 1] for p in _conv_pairs(self.net) for i in (0, 3)]
+            self._constants = [tuple(t.to(device) for t in _bn_host_constants(bn)) for bn in pairs]
+            self._stamp = stamp
+        return self._constants
+
+    def packed(self, device):
+        """The packed image of the live parameters on `device` (with a graph when gradients are enabled): one fused fold on
+        the device (csrc/event_net.hip: fold_pack_kernel, bit-equal to pack_event_net, with its own chain rule) when every
+        parameter is a contiguous float32 tensor there, pack_event_net_differentiable's torch operations otherwise."""
+        from . import functional as EF
+        consts = self._bn_constants(device)
+        pairs = [(p.double_conv[i], p.double_conv[i + 1]) for p in _conv_pairs(self.net) for i in (0, 3)]
+        params = [t for conv, bn in pairs for t in (conv.weight, bn.weight, bn.bias)]
+        params += [self.net.outc_1.conv.weight, self.net.outc_2.conv.weight, self.net.outc_1.conv.bias, self.net.outc_2.conv.bias]
+        fused = device.type == 'cuda' and all(conv.bias is None for conv, _ in pairs) and all(
+            t.device == device and t.dtype is torch.float32 and t.is_contiguous() for t in params)
+        if not fused:
+            return pack_event_net_differentiable(self.net, device, consts)
+        return EF.eventnet_fold_pack(params, [t for pair in consts for t in pair])
+
+    def forward(self, x):
+        from . import functional as EF
+        check_event_net(self.net, frozen=False)
+        hot = [n for n, p in self.net.named_parameters() if p.requires_grad]
+        if not hot:
+            if 'net' not in self._plain:
+                self._plain['net'] = HipUNet2Heads(self.net)
+            return self._plain['net'](x)
+        if not x.is_cuda:
+            raise NotImplementedError(f"the HIP event network needs its input on a HIP device (got {x.device}); use the torch "
+                                      "module on the CPU")
+        if x.dim() != 4 or x.shape[0] != 1:
+            raise NotImplementedError(f"the HIP event network runs batch 1 only (got an input of shape {tuple(x.shape)})")
+        if x.shape[1] != 6 or x.shape[2] < 16 or x.shape[3] < 16:
+            raise NotImplementedError(f"the HIP event network takes [1,6,H,W] with H, W >= 16 (got {tuple(x.shape)})")
+        if EF._capturing():
+            raise RuntimeError("the trainable HIP event network does not support graph capture of a training step; capture "
+                               "the frozen route (compile_event_net) instead")
+        key = (int(x.shape[2]), int(x.shape[3]), x.device)
+        ws = self._workspaces.get(key)
+        if ws is None:
+            ws = self._workspaces[key] = (EF.EventNetWorkspace(key[0], key[1], x.device),
+                                          EF.EventNetTrainScratch(key[0], key[1], x.device))
+        convs_hot = any(not n.startswith('outc_') for n in hot)
+        return EF.eventnet_train_apply(x, self.packed(x.device), ws[0], ws[1], convs_hot)
+
+
+def compile_event_net_trainable(net):
+    """The device route of an eval-mode `UNet_2heads(6, 2, 2)` whose parameters may require gradients: same call signature
+    and output shapes as the net, `parameters()` / `state_dict()` are the net's own (under `net.`), so
+    `torch.optim.Adam(tnet.parameters())` trains it.  Raises NotImplementedError for anything it does not implement."""
+    return HipUNet2HeadsTrainable(net)

@@ -2527,7 +2527,11 @@ class EventNetWorkspace:
         self.generation = 0
 
 
-eventnet_launches = {'forward': 0, 'backward': 0}        # calls made so far (tests read it)
+# Calls made so far (tests read it):
+#   'wgrad'        backward passes that ran the convolutions' weight gradients;
+#   'heads_wgrad'  backward passes that built the heads block's gradient alone;
+#   'fold_pack'    packed images built on the device from live parameters.
+eventnet_launches = {'forward': 0, 'backward': 0, 'wgrad': 0, 'heads_wgrad': 0, 'fold_pack': 0}
 
 
 def eventnet_forward(packed, x, ws):
@@ -2571,3 +2575,140 @@ class _EventNetFn(torch.autograd.Function):
 def eventnet_apply(x, packed, ws):
     _require_hip(x, "the event network's input")
     return _EventNetFn.apply(x, packed, ws)
+
+
+class EventNetTrainScratch:
+    """Split partials of the weight gradients of one image size (enslam_eventnet_wgrad_scratch_floats)."""
+
+    def __init__(self, H, W, device):
+        n = L.lib().enslam_eventnet_wgrad_scratch_floats(H, W)
+        if n == 0:
+            raise L.EnslamError(f"event network: unsupported image size {H} x {W}")
+        self.buf = torch.empty(n, dtype=torch.float32, device=device)
+
+
+def eventnet_backward_weights(packed, ws, scratch, g_events, g_probs, want_gx=True):
+    """(g_x or None, g_packed): the input gradient and the gradient of the packed image (Wt blocks and pad zero)."""
+    g_x = torch.empty((1, 6, ws.H, ws.W), dtype=torch.float32, device=g_events.device) if want_gx else None
+    g_packed = torch.empty_like(packed)
+    L.check(L.lib().enslam_eventnet_backward_weights(_ptr(packed), _ptr(ws.buf), _ptr(g_events), _ptr(g_probs), _ptr(g_x),
+                                                     _ptr(g_packed), _ptr(scratch.buf), scratch.buf.numel(), ws.H, ws.W,
+                                                     _stream()), "enslam_eventnet_backward_weights")
+    eventnet_launches['backward'] += 1
+    eventnet_launches['wgrad'] += 1
+    return g_x, g_packed
+
+
+def eventnet_heads_wgrad(packed, ws, scratch, g_events, g_probs):
+    """g_packed with only the heads block's gradient built; everything else zero."""
+    g_packed = torch.zeros_like(packed)
+    heads = g_packed[-264:]
+    L.check(L.lib().enslam_eventnet_heads_wgrad(_ptr(ws.buf), _ptr(g_events), _ptr(g_probs), _ptr(heads), _ptr(scratch.buf),
+                                                scratch.buf.numel(), ws.H, ws.W, _stream()), "enslam_eventnet_heads_wgrad")
+    eventnet_launches['heads_wgrad'] += 1
+    return g_packed
+
+
+class _EventNetTrainFn(torch.autograd.Function):
+    """_EventNetFn with the packed image as a second differentiable input."""
+
+    @staticmethod
+    def forward(ctx, x, packed, ws, scratch, convs_hot):
+        xc, pc = _f32c(x), _f32c(packed)
+        events, probs = eventnet_forward(pc, xc, ws)
+        ctx.ws, ctx.scratch, ctx.generation, ctx.convs_hot = ws, scratch, ws.generation, convs_hot
+        ctx.save_for_backward(xc, pc)
+        return events, probs
+
+    @staticmethod
+    def backward(ctx, g_events, g_probs):
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_w):
+            return None, None, None, None, None
+        if _capturing():
+            raise RuntimeError("the trainable HIP event network does not support graph capture of a training step")
+        xc, pc = ctx.saved_tensors
+        ws = ctx.ws
+        if ws.generation != ctx.generation:              # another forward of this size ran in between: restore the activations
+            eventnet_forward(pc, xc, ws)
+        ge, gp = _f32c(g_events), _f32c(g_probs)
+        if need_w and ctx.convs_hot:
+            g_x, g_packed = eventnet_backward_weights(pc, ws, ctx.scratch, ge, gp, want_gx=need_x)
+            return g_x, g_packed, None, None, None
+        g_x = eventnet_backward(pc, ws, ge, gp) if need_x else None
+        g_packed = eventnet_heads_wgrad(pc, ws, ctx.scratch, ge, gp) if need_w else None
+        return g_x, g_packed, None, None, None
+
+
+def eventnet_train_apply(x, packed, ws, scratch, convs_hot=True):
+    """(events, probs) of x [1,6,H,W] and the packed image, differentiable in both.  `convs_hot` False: only the heads
+    block of the packed image's gradient is wanted (no convolution weight gradient is launched)."""
+    _require_hip(x, "the event network's input")
+    _require_hip(packed, "the event network's packed weights")
+    return _EventNetTrainFn.apply(x, packed, ws, scratch, convs_hot)
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+_fold_scratch = {}                      # device -> float64 [26 * 16384], the partial sums of fold_pack_backward
+
+
+def _fold_flat(consts, params):
+    """The address order of enslam_eventnet_fold_pack: per convolution w, gamma, beta, sq, shift; then the heads' four."""
+    flat = []
+    for i in range(26):
+        flat += [params[3 * i], params[3 * i + 1], params[3 * i + 2], consts[2 * i], consts[2 * i + 1]]
+    return flat + list(params[78:])
+
+
+class _EventNetFoldPackFn(torch.autograd.Function):
+    """The packed image from live parameters (enslam_eventnet_fold_pack) and its chain rule back to them.  Inputs: the 52
+    float64 constants (sq, shift per convolution; no gradient), then per convolution w, gamma, beta and the heads' four.
+    All of them are saved through save_for_backward, so a parameter updated in place between forward and backward is an
+    autograd error, not a gradient from other weights."""
+
+    @staticmethod
+    def forward(ctx, n_const, *tensors):
+        consts, params = tensors[:n_const], tensors[n_const:]
+        packed = torch.empty(L.lib().enslam_eventnet_pack_floats(), dtype=torch.float32, device=params[0].device)
+        L.check(L.lib().enslam_eventnet_fold_pack(_ptr_array(_fold_flat(consts, params)), _ptr(packed), _stream()),
+                "enslam_eventnet_fold_pack")
+        eventnet_launches['fold_pack'] += 1
+        ctx.n_const = n_const
+        ctx.save_for_backward(*tensors)
+        return packed
+
+    @staticmethod
+    def backward(ctx, g_packed):
+        n_const = ctx.n_const
+        tensors = ctx.saved_tensors
+        consts, params = tensors[:n_const], tensors[n_const:]
+        needs = ctx.needs_input_grad[1 + n_const:]
+        g = _f32c(g_packed)
+        none = (None,) * (1 + n_const)
+        if not any(needs[:78]):                                    # the heads alone: their gradients are slices of the block
+            h = g[-264:]
+            heads = (h[:128].view(params[78].shape), h[128:256].view(params[79].shape), h[256:258], h[258:260])
+            return none + (None,) * 78 + tuple(t if need else None for t, need in zip(heads, needs[78:]))
+        sizes = [p.numel() for p in params]
+        buf = torch.empty(sum(sizes), dtype=torch.float32, device=g.device)      # one allocation, the gradients are its views
+        grads = [t.view(p.shape) for t, p in zip(buf.split(sizes), params)]
+        base, at, addr = buf.data_ptr(), 0, []
+        for n in sizes:
+            addr.append(base + 4 * at)
+            at += n
+        scratch = _fold_scratch.get(g.device)
+        if scratch is None:
+            scratch = _fold_scratch[g.device] = torch.empty(26 * 16384, dtype=torch.float64, device=g.device)
+        L.check(L.lib().enslam_eventnet_fold_pack_backward(_ptr_array(_fold_flat(consts, params)), _ptr(g),
+                                                           (ctypes.c_void_p * len(addr))(*addr), _ptr(scratch), _stream()),
+                "enslam_eventnet_fold_pack_backward")
+        return none + tuple(t if need else None for t, need in zip(grads, needs))
+
+
+def eventnet_fold_pack(params, consts):
+    """params: [w, gamma, beta] x 26 + [W1, W2, b1, b2], float32 contiguous on the device; consts: [sq, shift] x 26, float64 on
+    the device.  The packed image, differentiable in the parameters."""
+    return _EventNetFoldPackFn.apply(len(consts), *consts, *params)

@@ -855,6 +855,38 @@ int enslam_eventnet_pool2(const float *in, int32_t H, int32_t W, int32_t C, cons
                           void *stream);
 int enslam_eventnet_up2(const float *in, int32_t h, int32_t w, int32_t C, float *out, int32_t backward, void *stream);
 
+/* Training of the event network: the gradient of the packed image.  backward_weights does everything the backward entry above
+ * does (g_x may be NULL: no input gradient is built) and writes g_packed, laid out like packed: the Wf and b blocks of every
+ * convolution hold the gradients of the FOLDED weights and biases (relu'(0) = 0), the heads block those of W1 | W2 | b1 | b2;
+ * every Wt block and the pad are written as zero (Wt is a copy of Wf: the caller's chain rule goes through Wf alone).  Each
+ * weight gradient is an implicit GEMM over the pixels on the exact-f32 MFMA; layers with few weight tiles split the pixel
+ * axis and the partials, kept in scratch [at least wgrad_scratch_floats(H, W)], are summed in split order: no atomics, two
+ * runs are bit-equal.  The workspace is the forward's, unchanged in layout and size.  No allocation, no synchronisation.
+ * heads_wgrad writes only the heads block's gradient [264] from the workspace of the last forward (scratch: as above).
+ * conv3x3_wgrad is the single-operation entry for the tests, with the conventions of the conv3x3 entry: a0 [H*W][C0] and,
+ * with C1 > 0, a1 [H1*W1][C1] at (oy, ox) are the convolution's input, g [H*W][Cn] the gradient of its output, counted only
+ * where saved (same layout, may be NULL) is > 0;  dw [9 (C0 + C1)][Cn] (row = tap * (C0 + C1) + c), db [Cn] (may be NULL).
+ * scratch: 2^22 floats always suffice. */
+/* fold_pack builds the packed image on the device from live parameters, bit-equal to event.pack_event_net: params holds, per
+ * convolution in packing order, five device addresses -- w float32 [cout][cin][3][3] (the first layer's cin is 6), BatchNorm
+ * gamma and beta float32 [cout], sq = sqrt(var + eps) and shift = -mean float64 [cout], both computed on the host -- and then
+ * the heads' W1, W2, b1, b2 (134 addresses).  Folding is float64 (s = gamma / sq, w s, beta + shift s), rounded once.
+ * fold_pack_backward is its chain rule: from g_packed (Wf, b and heads blocks; Wt is not read) to grads, per convolution dw,
+ * dgamma, dbeta (float32, shaped like the parameters, overwritten) and then the heads' four (82 addresses): dw = dWf s,
+ * dgamma = (sum dWf w + shift db) / sq with the sum in float64 in a fixed order, dbeta = db.  scratch: float64 [26 * 16384].  Each is one launch over all 26 convolutions. */
+int enslam_eventnet_fold_pack(const void *const *params, float *packed, void *stream);
+int enslam_eventnet_fold_pack_backward(const void *const *params, const float *g_packed, void *const *grads, double *scratch,
+                                       void *stream);
+size_t enslam_eventnet_wgrad_scratch_floats(int32_t H, int32_t W);     /* 0: unsupported size */
+int enslam_eventnet_backward_weights(const float *packed, float *workspace, const float *g_events, const float *g_probs,
+                                     float *g_x, float *g_packed, float *scratch, int64_t scratch_floats, int32_t H, int32_t W,
+                                     void *stream);
+int enslam_eventnet_heads_wgrad(const float *workspace, const float *g_events, const float *g_probs, float *g_heads,
+                                float *scratch, int64_t scratch_floats, int32_t H, int32_t W, void *stream);
+int enslam_eventnet_conv3x3_wgrad(int32_t H, int32_t W, int32_t C0, int32_t C1, int32_t H1, int32_t W1, int32_t oy, int32_t ox,
+                                  int32_t Cn, const float *a0, const float *a1, const float *g, const float *saved, float *dw,
+                                  float *db, float *scratch, int64_t scratch_floats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,12 +2,15 @@
 
     python tools/run_slam.py CONFIG [--default-config PATH] [--input_folder DIR] [--event_folder DIR] [--output DIR]
                                     [--max-frames N] [--prepare host|device] [--prefit ITERS] [--device cuda:0]
+                                    [--event-net PATH] [--net-backend hip|torch]
 
 CONFIG may name parents with `inherit_from` (config.load_config); --default-config is the root under a chain that names
 none (the reference passes configs/nice_slam.yaml).  The reference's YAML files are not part of this repository: point at
 your own copy.  --prepare overrides `data.prepare` (frame preparation on the host or in csrc/frame_prep.hip); --prefit fits
 the decoders to a handful of ground-truth-posed frames first (SLAM.prefit_decoders, the stand-in for the reference's
-pretrained decoders).  Prints one JSON line: checkpoint path, frames, frames per second and the ATE."""
+pretrained decoders); --event-net loads a state_dict (tools/train_event_net.py, or a reference checkpoint) into a frozen
+eval-mode UNet_2heads(6, 2, 2) and hands it to the harness as its event network, --net-backend picks `event.net_backend`
+for it (hip: event.compile_event_net); without --event-net the harness runs without one, as before.  Prints one JSON line: checkpoint path, frames, frames per second and the ATE."""
 import argparse
 import copy
 import json
@@ -42,6 +45,8 @@ def main(argv=None):
     ap.add_argument('--prepare', choices=('host', 'device'), default=None)
     ap.add_argument('--prefit', type=int, default=0)
     ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--event-net', default=None)
+    ap.add_argument('--net-backend', choices=('hip', 'torch'), default=None)
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -58,7 +63,15 @@ def main(argv=None):
                        device=args.device)
     torch.manual_seed(0)
     np.random.seed(0)
-    slam = SLAM(slam_camera(cfg), ds, output, device=args.device, static_shapes=True)
+    extra = {}
+    if args.event_net is not None:
+        from evennicer_slam_amd.event import UNet_2heads
+        net = UNet_2heads(6, 2, 2)
+        net.load_state_dict(torch.load(args.event_net, map_location='cpu'))
+        extra['event_net'] = net.requires_grad_(False).to(args.device).eval()
+        if args.net_backend is not None:
+            cfg.setdefault('event', {})['net_backend'] = args.net_backend
+    slam = SLAM(slam_camera(cfg), ds, output, device=args.device, static_shapes=True, **extra)
     n = len(ds) if args.max_frames is None else min(args.max_frames, len(ds))
     if args.prefit > 0:
         slam.prefit_decoders(list(range(0, n, max(n // 6, 1))), iters=args.prefit)
