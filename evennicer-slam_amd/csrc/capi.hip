@@ -793,6 +793,7 @@ int enslam_composite_loss_bwd(int32_t n_rays, int32_t n_samples, const float* ra
     const LossSpec ls{gt_depth, gt_color, w_color, nullptr, g_loss, nullptr};
     WorkList wl;
     if (!work_list_of(work_list, work_count, wl)) return ENSLAM_EINVAL;
+    if (work_list && n_samples % 16 != 0) return ENSLAM_EINVAL;      // the list holds whole 16-sample tiles only
     return ens_launch_composite_bwd(n_rays, n_samples, raw, z_vals, depth, nullptr, nullptr, nullptr, d_raw,
                                     (hipStream_t)stream, &ls, rgb, work_list ? &wl : nullptr) == 0 ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
@@ -844,6 +845,7 @@ int enslam_composite_bwd_list(int32_t n_rays, int32_t n_samples, const float* ra
     if (n_rays == 0) return ENSLAM_OK;
     WorkList wl;
     if (!raw || !z_vals || !depth || !d_raw || !work_list_of(work_list, work_count, wl)) return ENSLAM_EINVAL;
+    if (work_list && n_samples % 16 != 0) return ENSLAM_EINVAL;      // the list holds whole 16-sample tiles only
     return ens_launch_composite_bwd(n_rays, n_samples, raw, z_vals, depth, g_depth, g_var, g_rgb, d_raw, (hipStream_t)stream,
                                     nullptr, nullptr, work_list ? &wl : nullptr);
 }

@@ -697,7 +697,9 @@ int enslam_decoder_bwd_partials(int32_t stage, int32_t n_rays, int32_t n_samples
  * gradient.  The kernel that produces d_raw appends them ray by ray (work_list int32 [n_rays * n_samples/16], work_count
  * int32 [1], ZERO on entry): enslam_render_loss_fwd (with d_raw_unit), enslam_composite_loss_bwd,
  * enslam_composite_bwd_list.  enslam_decoder_bwd_scaled (saved-activation roles only) and enslam_step_finish_rays then
- * walk the list instead of all tiles; both must be given the same list. */
+ * walk the list instead of all tiles; both must be given the same list.  The list holds whole tiles only: with a work list
+ * n_samples must be a multiple of 16 (ENSLAM_EINVAL otherwise; the samples past the last whole tile would never be listed).
+ * Without a list the two compositing entries take every n_samples from 1 to 64. */
 int enslam_composite_bwd_list(int32_t n_rays, int32_t n_samples, const float *raw, const double *z_vals,
                               const double *depth, const double *g_depth, const double *g_var, const float *g_rgb,
                               float *d_raw, int32_t *work_list, int32_t *work_count, void *stream);

@@ -46,6 +46,15 @@ def test_bad_arguments_return_error_codes():
                                          None, None, None, st) == EINVAL
     assert lib.enslam_composite_bwd_list(4, 48, P(ro), P(z), P(out_d), None, None, None, P(ro), P(ro), None, st) == EINVAL   # list without count
     assert lib.enslam_composite_loss_bwd(4, 48, None, P(z), P(out_d), P(out_c), P(ro), None, 0.2, P(out_d), P(ro), None, None, st) == EINVAL
+    # a work list holds whole 16-sample tiles: 40 samples per ray are refused with a list, taken without one
+    wl, wc = torch.zeros(4 * 3, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    raw40, d40 = torch.zeros(4 * 40, 4, device=dev), torch.empty(4 * 40, 4, device=dev)
+    assert lib.enslam_composite_bwd_list(4, 40, P(raw40), P(z), P(out_d), P(out_d), None, None, P(d40), P(wl), P(wc), st) == EINVAL
+    assert lib.enslam_composite_loss_bwd(4, 40, P(raw40), P(z), P(out_d), None, P(ro), None, 0.2, P(out_d), P(d40), P(wl), P(wc), st) == EINVAL
+    assert lib.enslam_composite_bwd_list(4, 40, P(raw40), P(z), P(out_d), P(out_d), None, None, P(d40), None, None, st) == 0
+    assert lib.enslam_composite_loss_bwd(4, 40, P(raw40), P(z), P(out_d), None, P(ro), None, 0.2, P(out_d), P(d40), None, None, st) == 0
+    torch.cuda.synchronize()
+    assert int(wc) == 0
     assert lib.enslam_composite_loss_bwd(4, 48, P(ro), P(z), P(out_d), None, P(ro), P(out_c), 0.2, P(out_d), P(ro), None, None, st) == EINVAL  # colour without rgb
     assert lib.enslam_step_finish_rays(0, None, None, None, None, 0, None, None, None, 3, 4, 40, P(ro), P(ro), P(z), ctypes.byref(sc),
                                        P(ro), P(ro), P(ro), None, None, st) == EUNSUPPORTED           # sample count
