@@ -59,6 +59,13 @@ class FramePlan(ctypes.Structure):            # enslam_frame_plan
                 ("dist", c_double * 8), ("png_depth_scale", c_double), ("scale", c_double)]
 
 
+class EventSimPlan(ctypes.Structure):         # enslam_event_sim_plan
+    _fields_ = [("H", c_int32), ("W", c_int32), ("K", c_int32), ("channels", c_int32), ("init", c_int32), ("has_box", c_int32),
+                ("eps", c_double), ("c_pos", c_double), ("c_neg", c_double), ("fx", c_double), ("fy", c_double),
+                ("cx", c_double), ("cy", c_double), ("room_lo", c_double * 3), ("room_hi", c_double * 3),
+                ("box_lo", c_double * 3), ("box_hi", c_double * 3), ("freq", c_double * 9), ("phase", c_double * 3)]
+
+
 class EnslamError(RuntimeError):
     pass
 
@@ -276,6 +283,12 @@ _SIGS = {
     "enslam_eventnet_conv3x3_wgrad": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                                      c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                      c_void_p, c_int64, c_void_p]),
+    "enslam_event_sim_plan_bytes": (c_int64, []),
+    "enslam_event_sim_max_substeps": (ctypes.c_int, []),
+    "enslam_event_sim_images": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_event_sim_boxroom": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -304,6 +317,8 @@ def lib():
             raise EnslamError("libenslam_hip.so: enslam_step_plan / enslam_step_layout do not have the sizes this binding declares")
         if hasattr(handle, "enslam_frame_plan_bytes") and handle.enslam_frame_plan_bytes() != ctypes.sizeof(FramePlan):
             raise EnslamError("libenslam_hip.so: enslam_frame_plan does not have the size this binding declares")
+        if hasattr(handle, "enslam_event_sim_plan_bytes") and handle.enslam_event_sim_plan_bytes() != ctypes.sizeof(EventSimPlan):
+            raise EnslamError("libenslam_hip.so: enslam_event_sim_plan does not have the size this binding declares")
         _lib = handle
     return _lib
 

@@ -456,9 +456,7 @@ def write_rpg_event_sequence(root, frames, poses, png_depth_scale, events):
             p[:3, 2] *= -1
             f.write(' '.join(repr(float(v)) for v in p.reshape(-1)) + '\n')
     for i, ev in enumerate(events):
-        rgb = np.zeros(ev.shape[:2] + (3,), dtype=np.uint8)
-        rgb[..., 0], rgb[..., 1] = ev[..., 1], ev[..., 0]
-        Image.fromarray(rgb, 'RGB').save(os.path.join(evf, f'event{i + 1:06d}.png'))
+        save_event_image(evf, i + 1, ev, 'rpg_event')
     return inp, evf
 
 
@@ -483,10 +481,27 @@ def write_replica_event_sequence(root, frames, poses, png_depth_scale, events=No
             f.write(' '.join(repr(float(v)) for v in p.reshape(-1)) + '\n')
     if events is not None:
         for i, ev in enumerate(events):
-            rgb = np.zeros(ev.shape[:2] + (3,), dtype=np.uint8)
-            rgb[..., 1:] = ev
-            Image.fromarray(rgb, 'RGB').save(os.path.join(evf, f'event_frame{i + 1:06d}.png'))
+            save_event_image(evf, i + 1, ev, 'replica_event')
     return inp, evf
+
+
+def save_event_image(folder, number, ev, layout='replica_event'):
+    """One event image uint8 [H,W,2] = (-, +) as the png the `layout` reader expects, named and ordered as the sequence
+    writers above do: 'replica_event' event_frame{number:06d}.png with channels (0, -, +), 'rpg_event' event{number:06d}.png
+    with (+, -, 0).  `number` is the frame the interval ends at (1 for the first image).  Returns the path."""
+    from PIL import Image
+    ev = np.asarray(ev, dtype=np.uint8)
+    rgb = np.zeros(ev.shape[:2] + (3,), dtype=np.uint8)
+    if layout == 'replica_event':
+        rgb[..., 1:] = ev
+        path = os.path.join(folder, f'event_frame{number:06d}.png')
+    elif layout == 'rpg_event':
+        rgb[..., 0], rgb[..., 1] = ev[..., 1], ev[..., 0]
+        path = os.path.join(folder, f'event{number:06d}.png')
+    else:
+        raise ValueError(f"save_event_image: layout must be 'replica_event' or 'rpg_event' (got {layout!r})")
+    Image.fromarray(rgb, 'RGB').save(path)
+    return path
 
 
 def _color_u8(color):

@@ -1,0 +1,284 @@
+"""Event-camera simulator: a contrast-threshold sensor in the style of ESIM / vid2e, the source of the event images that the
+`*_event` readers, the event network's trainer and the tracker's event term consume.
+
+The model (include/enslam_hip.h repeats it; csrc/event_sim.hip runs it), all in float64:
+
+    luminance   Y = (0.299 R + 0.587 G) + 0.114 B of values in [0, 1]; a grey image is its own Y
+    level       L = log(Y + eps), eps = 1e-3
+    state       one reference level per pixel, L_ref [H,W]: L of the first frame (which emits no events), then carried from
+                interval to interval
+    interval    frame k -> frame k+1 is visited at K sub-steps s = 1..K (default 8), the last one being frame k+1; at each,
+                per pixel, with d = L - L_ref:
+                    d >= C_pos:        n = floor(d / C_pos),  pos += n,  L_ref += n * C_pos
+                    else -d >= C_neg:  n = floor(-d / C_neg), neg += n,  L_ref -= n * C_neg
+                This closed form is the definition (a loop that fires one event at a time rounds differently).
+    output      uint8 [H,W,2] = (-, +), the writers' order, saturated at 255; L_ref moves by the unsaturated n
+    thresholds  scalars (default 0.2) or, with sigma_c > 0, per-pixel maps drawn ONCE per simulator from a seeded CPU generator:
+                C * (1 + sigma_c * randn), clamped to at least 0.01
+
+Two routes to L at a sub-step:
+
+    images    any recorded sequence: two decoded uint8 images; L of a grey value from a 256-entry table, of an RGB pixel from
+              its three bytes / 255.; sub-step s sees L_a + (s / K) * (L_b - L_a), in this operation order
+    scene     synthetic.BoxRoom: the room is rendered at K poses between the two frames' (`interpolate_poses`: translation
+              linear, rotation by quaternion slerp), exactly as BoxRoom.render does it
+
+On a HIP device both run as one launch per interval (functional.event_sim_images / event_sim_boxroom).  On the CPU the same
+methods run a numpy route of the same definition, operation for operation, so sequences can be written without a GPU.  The
+two agree bit for bit wherever no transcendental function of the device decides (grey images, or `host_log=True`); the
+device's log and sin are an ulp or two from numpy's, which moves a count only where d / C sits that close to an integer.
+
+Not modelled: refractory period, leak and shot noise, per-event time stamps, bandwidth-limited pixels, learned
+frame interpolation."""
+import numpy as np
+import torch
+
+from ._lib import EnslamError
+
+C_MIN = 0.01                        # floor of a per-pixel threshold
+
+
+def grey_table(eps=1e-3):
+    """log(v / 255 + eps) of the 256 grey values, float64: the table both routes read grey images through."""
+    return np.log(np.arange(256, dtype=np.float64) / 255.0 + eps)
+
+
+def luminance(rgb):
+    """Y float64 [...] of float64 [...,3] values, summed in the model's order."""
+    return (0.299 * rgb[..., 0] + 0.587 * rgb[..., 1]) + 0.114 * rgb[..., 2]
+
+
+def log_intensity(image, eps=1e-3):
+    """L float64 [H,W] of a decoded uint8 image: [H,W] / [H,W,1] (grey, through `grey_table`) or [H,W,3] (bytes / 255.)."""
+    a = np.asarray(image)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+        raise EnslamError(f"event simulator: an image must be uint8 [H,W], [H,W,1] or [H,W,3] (got {a.dtype} {a.shape})")
+    if a.ndim == 2:
+        return grey_table(eps)[a]
+    return np.log(luminance(a.astype(np.float64) / 255.0) + eps)
+
+
+def sensor_update(L, ref, pos, neg, c_pos, c_neg):
+    """The per-pixel update at one sub-step, in place on the float64 arrays ref, pos, neg (counts are kept unsaturated)."""
+    d = L - ref
+    up = d >= c_pos
+    down = ~up & (-d >= c_neg)
+    n_up = np.floor(d / c_pos)
+    n_down = np.floor(-d / c_neg)
+    pos[...] = np.where(up, pos + n_up, pos)
+    neg[...] = np.where(down, neg + n_down, neg)
+    ref[...] = np.where(up, ref + n_up * c_pos, np.where(down, ref - n_down * c_neg, ref))
+
+
+def saturate(neg, pos):
+    """uint8 [H,W,2] = (-, +) of two float64 count arrays"""
+    return np.stack([np.minimum(neg, 255.0), np.minimum(pos, 255.0)], axis=-1).astype(np.uint8)
+
+
+def render_boxroom(room, c2w, cam):
+    """synthetic.BoxRoom.render in numpy with every sum written out in a fixed order -- the order of csrc/event_sim.hip:
+    (color float64 [H,W,3], t float64 [H,W]) of the view c2w ([3|4,4] float64)."""
+    H, W, fx, fy, cx, cy = (cam[k] for k in ('H', 'W', 'fx', 'fy', 'cx', 'cy'))
+    P = np.asarray(c2w, dtype=np.float64)
+    i, j = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    dirs = ((i - cx) / fx, -(j - cy) / fy, -np.ones_like(i))
+    d = [(dirs[0] * P[a, 0] + dirs[1] * P[a, 1]) + dirs[2] * P[a, 2] for a in range(3)]
+    o = [P[a, 3] for a in range(3)]
+    dc = [np.where(np.abs(v) < 1e-12, 1e-12, v) for v in d]
+    lo, hi = room.room_lo.numpy(), room.room_hi.numpy()
+    t = None
+    for a in range(3):
+        far = np.maximum((lo[a] - o[a]) / dc[a], (hi[a] - o[a]) / dc[a])
+        t = far if t is None else np.minimum(t, far)
+    if room.box_lo is not None:
+        blo, bhi = room.box_lo.numpy(), room.box_hi.numpy()
+        t1 = t2 = None
+        for a in range(3):
+            u, v = (blo[a] - o[a]) / dc[a], (bhi[a] - o[a]) / dc[a]
+            near, far = np.minimum(u, v), np.maximum(u, v)
+            t1 = near if t1 is None else np.maximum(t1, near)
+            t2 = far if t2 is None else np.minimum(t2, far)
+        t = np.where((t1 < t2) & (t1 > 0) & (t1 < t), t1, t)
+    p = [o[a] + d[a] * t for a in range(3)]
+    f, ph = room.freq.numpy(), room.phase.numpy()
+    col = [0.5 + 0.45 * np.sin(((p[0] * f[c, 0] + p[1] * f[c, 1]) + p[2] * f[c, 2]) + ph[c]) for c in range(3)]
+    return np.stack(col, axis=-1), t
+
+
+def interpolate_poses(c2w_a, c2w_b, K):
+    """The K poses s = 1..K of an interval, float64 [K,4,4]: translation a + (s / K) * (b - a), rotation by quaternion slerp
+    of the two rotations along the shorter arc; the pose of s = K is c2w_b itself.  Host arithmetic (numpy float64)."""
+    from .datasets import matrix_quaternion, quaternion_matrix
+    A, B = (np.asarray(torch.as_tensor(m).double().numpy() if torch.is_tensor(m) else m, dtype=np.float64) for m in (c2w_a, c2w_b))
+    if K < 1:
+        raise EnslamError(f"interpolate_poses: K must be at least 1 (got {K})")
+    qa, qb = matrix_quaternion(A[:3, :3]), matrix_quaternion(B[:3, :3])
+    qa, qb = qa / np.linalg.norm(qa), qb / np.linalg.norm(qb)
+    dot = float(np.dot(qa, qb))
+    if dot < 0.0:
+        qb, dot = -qb, -dot
+    theta = float(np.arccos(min(dot, 1.0)))
+    out = np.zeros((K, 4, 4), dtype=np.float64)
+    out[:, 3, 3] = 1.0
+    for s in range(1, K + 1):
+        if s == K:
+            out[s - 1, :3, :] = B[:3, :]
+            continue
+        u = s / K
+        if theta < 1e-8:                                            # sin(theta) ~ theta: the chord is the arc
+            q = qa + u * (qb - qa)
+        else:
+            q = (np.sin((1.0 - u) * theta) * qa + np.sin(u * theta) * qb) / np.sin(theta)
+        out[s - 1, :3, :3] = quaternion_matrix(q)
+        out[s - 1, :3, 3] = A[:3, 3] + u * (B[:3, 3] - A[:3, 3])
+    return out
+
+
+class EventSimulator:
+    """One simulated sensor of H x W pixels: thresholds, sub-step count and the carried state.
+
+        sim = EventSimulator(H, W, device='cuda:0')
+        sim.reset(first_image)                              # or sim.reset((room, c2w, cam))
+        events = sim.step_images(prev_image, cur_image)     # uint8 [H,W,2] = (-, +) on `device`
+        events = sim.step_scene(room, c2w_prev, c2w_cur, cam)
+
+    device: a HIP device runs csrc/event_sim.hip, 'cpu' the numpy route of the same definition."""
+
+    def __init__(self, H, W, c_pos=0.2, c_neg=0.2, sigma_c=0.0, substeps=8, eps=1e-3, seed=0, device='cuda:0'):
+        self.H, self.W, self.substeps, self.eps = int(H), int(W), int(substeps), float(eps)
+        self.c_pos, self.c_neg, self.sigma_c, self.seed = float(c_pos), float(c_neg), float(sigma_c), int(seed)
+        self.device = torch.device(device)
+        if self.H <= 0 or self.W <= 0 or self.substeps < 1:
+            raise EnslamError(f"EventSimulator: H, W and substeps must be positive (got {H}, {W}, {substeps})")
+        if not (self.c_pos > 0 and self.c_neg > 0 and self.eps > 0 and self.sigma_c >= 0):
+            raise EnslamError("EventSimulator: c_pos, c_neg and eps must be positive, sigma_c not negative")
+        if self.device.type == 'cuda':
+            from . import functional as EF
+            from . import _lib as L
+            kmax = L.lib().enslam_event_sim_max_substeps()
+            if self.substeps > kmax:
+                raise EnslamError(f"EventSimulator: at most {kmax} sub-steps on the device (got {substeps})")
+            self._EF = EF
+        self.c_pos_map = self.c_neg_map = None
+        if self.sigma_c > 0:
+            rng = np.random.default_rng(self.seed)
+            maps = [np.maximum(c * (1.0 + self.sigma_c * rng.standard_normal((self.H, self.W))), C_MIN) for c in (self.c_pos, self.c_neg)]
+            self.c_pos_map, self.c_neg_map = (torch.from_numpy(m).to(self.device) for m in maps)
+        self._lut = torch.from_numpy(grey_table(self.eps)).to(self.device)
+        self._ref = None
+
+    # ---- state -------------------------------------------------------------------------------------------------------------
+    @property
+    def state(self):
+        """L_ref, float64 [H,W] on the simulator's device (None before `reset`); the live tensor, updated in place."""
+        return self._ref
+
+    @property
+    def on_device(self):
+        return self.device.type == 'cuda'
+
+    def _need_state(self):
+        if self._ref is None:
+            raise EnslamError("EventSimulator: reset() with the first frame before the first step")
+
+    def _thresholds(self):
+        """(c_pos, c_neg) for the numpy route: the maps where there are any"""
+        return (self.c_pos if self.c_pos_map is None else self.c_pos_map.numpy(),
+                self.c_neg if self.c_neg_map is None else self.c_neg_map.numpy())
+
+    def _kw(self):
+        return dict(eps=self.eps, c_pos=self.c_pos, c_neg=self.c_neg, c_pos_map=self.c_pos_map, c_neg_map=self.c_neg_map)
+
+    def _image(self, image):
+        """a decoded image as the kernel takes it: uint8 [H,W] or [H,W,3] on the device"""
+        t = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
+        if t.dim() == 3 and t.shape[2] == 1:
+            t = t[:, :, 0]
+        if t.dtype != torch.uint8 or tuple(t.shape[:2]) != (self.H, self.W):
+            raise EnslamError(f"EventSimulator: an image must be uint8 [{self.H},{self.W}] or [{self.H},{self.W},3] (got {t.dtype} "
+                              f"{tuple(t.shape)})")
+        return t.to(self.device).contiguous()
+
+    def _host_level(self, image):
+        a = image.cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+        if a.dtype != np.uint8 or tuple(a.shape[:2]) != (self.H, self.W):
+            raise EnslamError(f"EventSimulator: an image must be uint8 [{self.H},{self.W}] or [{self.H},{self.W},3] (got {a.dtype} "
+                              f"{a.shape})")
+        return log_intensity(a, self.eps)
+
+    def _check_cam(self, cam):
+        if int(cam['H']) != self.H or int(cam['W']) != self.W:
+            raise EnslamError(f"EventSimulator: the camera is {cam['H']} x {cam['W']}, the sensor {self.H} x {self.W}")
+
+    # ---- the first frame ---------------------------------------------------------------------------------------------------
+    def reset(self, first, host_log=False):
+        """State := L of the first frame, which emits no events.  first: a decoded image, or (room, c2w, cam)."""
+        scene = isinstance(first, (tuple, list)) and len(first) == 3 and hasattr(first[0], 'room_lo')
+        if scene:
+            self._check_cam(first[2])
+        if not self.on_device:
+            if scene:
+                room, c2w, cam = first
+                L = np.log(luminance(render_boxroom(room, _pose64(c2w), cam)[0]) + self.eps)
+            else:
+                L = self._host_level(first)
+            self._ref = torch.from_numpy(np.ascontiguousarray(L))
+            return self
+        self._ref = torch.empty((self.H, self.W), dtype=torch.float64, device=self.device)
+        if scene:
+            room, c2w, cam = first
+            self._EF.event_sim_boxroom(room, _pose64(c2w)[None], cam, self._ref, init=True, **self._kw())
+        elif host_log:
+            self._ref.copy_(torch.from_numpy(self._host_level(first)))
+        else:
+            img = self._image(first)
+            self._EF.event_sim_images(img, img, self._ref, substeps=1, lut=self._lut, init=True, **self._kw())
+        return self
+
+    # ---- one interval ------------------------------------------------------------------------------------------------------
+    def step_images(self, prev, cur, host_log=False):
+        """Events uint8 [H,W,2] = (-, +) between two decoded images (numpy arrays, or tensors on the device).  host_log: on a
+        device, take the two level images from the host (numpy's log) instead of the kernel's -- bit-equal to the CPU route
+        for RGB images too, at the price of two float64 uploads."""
+        self._need_state()
+        if not self.on_device:
+            La, Lb = self._host_level(prev), self._host_level(cur)
+            ref = self._ref.numpy()
+            pos, neg = np.zeros_like(ref), np.zeros_like(ref)
+            cp, cn = self._thresholds()
+            dL = Lb - La
+            for s in range(1, self.substeps + 1):
+                sensor_update(La + (s / self.substeps) * dL, ref, pos, neg, cp, cn)
+            return torch.from_numpy(saturate(neg, pos))
+        if host_log:
+            levels = tuple(torch.from_numpy(self._host_level(im)).to(self.device) for im in (prev, cur))
+            return self._EF.event_sim_images(None, None, self._ref, substeps=self.substeps, levels=levels, **self._kw())
+        a, b = self._image(prev), self._image(cur)
+        if a.shape != b.shape:
+            raise EnslamError(f"EventSimulator: the two images differ in shape ({tuple(a.shape)}, {tuple(b.shape)})")
+        return self._EF.event_sim_images(a, b, self._ref, substeps=self.substeps, lut=self._lut, **self._kw())
+
+    def step_scene(self, room, c2w_prev, c2w_cur, cam, want_frame=False):
+        """Events of the interval between two views of `room`; with want_frame also (color float64 [H,W,3], depth float32
+        [H,W]) of c2w_cur, what room.render(c2w_cur, cam) returns."""
+        self._need_state()
+        self._check_cam(cam)
+        poses = interpolate_poses(_pose64(c2w_prev), _pose64(c2w_cur), self.substeps)
+        if self.on_device:
+            return self._EF.event_sim_boxroom(room, poses, cam, self._ref, want_frame=want_frame, **self._kw())
+        ref = self._ref.numpy()
+        pos, neg = np.zeros_like(ref), np.zeros_like(ref)
+        cp, cn = self._thresholds()
+        for P in poses:
+            col, t = render_boxroom(room, P, cam)
+            sensor_update(np.log(luminance(col) + self.eps), ref, pos, neg, cp, cn)
+        events = torch.from_numpy(saturate(neg, pos))
+        if want_frame:
+            return events, torch.from_numpy(col), torch.from_numpy(t.astype(np.float32))
+        return events
+
+
+def _pose64(c2w):
+    return (c2w.detach().cpu().double().numpy() if torch.is_tensor(c2w) else np.asarray(c2w, dtype=np.float64))

@@ -2712,3 +2712,130 @@ def eventnet_fold_pack(params, consts):
     """params: [w, gamma, beta] x 26 + [W1, W2, b1, b2], float32 contiguous on the device; consts: [sq, shift] x 26, float64 on
     the device.  The packed image, differentiable in the parameters."""
     return _EventNetFoldPackFn.apply(len(consts), *consts, *params)
+
+
+# ------------------------------------------------------------------------------------------------
+# Event-camera simulator (csrc/event_sim.hip; event_sim.EventSimulator drives it)
+# ------------------------------------------------------------------------------------------------
+def event_sim_plan(H, W, substeps, eps, c_pos, c_neg, channels=1, init=False, cam=None, room=None):
+    """The enslam_event_sim_plan of one launch (host arithmetic only).  cam: dict with fx, fy, cx, cy and room: a
+    synthetic.BoxRoom, both for the analytic route only."""
+    p = L.EventSimPlan()
+    p.H, p.W, p.K, p.channels, p.init = int(H), int(W), int(substeps), int(channels), int(bool(init))
+    p.eps, p.c_pos, p.c_neg = float(eps), float(c_pos), float(c_neg)
+    if cam is not None:
+        p.fx, p.fy, p.cx, p.cy = (float(cam[k]) for k in ('fx', 'fy', 'cx', 'cy'))
+    if room is not None:
+        p.room_lo[:], p.room_hi[:] = room.room_lo.tolist(), room.room_hi.tolist()
+        p.has_box = int(room.box_lo is not None)
+        if p.has_box:
+            p.box_lo[:], p.box_hi[:] = room.box_lo.tolist(), room.box_hi.tolist()
+        p.freq[:], p.phase[:] = room.freq.reshape(-1).tolist(), room.phase.tolist()
+    return p
+
+
+def _event_sim_checks(what, H, W, substeps, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, init):
+    if H <= 0 or W <= 0:
+        raise L.EnslamError(f"{what}: the image must have pixels (got {H} x {W})")
+    kmax = L.lib().enslam_event_sim_max_substeps()
+    if not 1 <= int(substeps) <= kmax:
+        raise L.EnslamError(f"{what}: substeps must be in 1..{kmax} (got {substeps})")
+    if not (eps > 0 and eps < float('inf')):
+        raise L.EnslamError(f"{what}: eps must be positive and finite (got {eps})")
+    _event_sim_tensor(what, 'state', state, torch.float64, (H, W), None)
+    for name, c, m in (('c_pos', c_pos, c_pos_map), ('c_neg', c_neg, c_neg_map)):
+        if m is None:
+            if not init and not (c > 0 and c < float('inf')):
+                raise L.EnslamError(f"{what}: {name} must be positive and finite (got {c})")
+        else:
+            _event_sim_tensor(what, name + '_map', m, torch.float64, (H, W), state.device)
+
+
+def _event_sim_tensor(what, name, t, dtype, shape, device):
+    if not torch.is_tensor(t):
+        raise L.EnslamError(f"{what}: {name} must be a tensor (got {type(t).__name__})")
+    _require_hip(t, f"{what}: {name}")
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or (device is not None and t.device != device):
+        raise L.EnslamError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}"
+                            f"{'' if device is None else f' on {device}'} (got {t.dtype} {tuple(t.shape)} on {t.device}, "
+                            f"contiguous: {t.is_contiguous()})")
+
+
+def event_sim_images(prev, cur, state, substeps=8, eps=1e-3, c_pos=0.2, c_neg=0.2, lut=None, levels=None, c_pos_map=None,
+                     c_neg_map=None, init=False):
+    """One interval of the image route (enslam_event_sim_images, enslam_hip.h): events uint8 [H,W,2] = (-, +) between two
+    decoded images, `state` (L_ref, float64 [H,W] on a HIP device) updated in place.
+
+      prev, cur  uint8 [H,W] / [H,W,1] (grey) or [H,W,3] (RGB) on the state's device
+      lut        float64 [256]: log(v / 255 + eps) of the grey values, computed by the host (required for grey images)
+      levels     (L_prev, L_cur) float64 [H,W]: host-computed log intensities used INSTEAD of the images (prev and cur may
+                 then be None), so that no device log decides a count
+      c_pos_map, c_neg_map  float64 [H,W] per-pixel thresholds replacing the scalars
+      init       the first frame: no events (None is returned), state := L of `cur`"""
+    what = "event_sim_images"
+    if not torch.is_tensor(state):
+        raise L.EnslamError(f"{what}: state must be a tensor")
+    H, W = (int(v) for v in state.shape) if state.dim() == 2 else (0, 0)
+    _event_sim_checks(what, H, W, substeps, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, init)
+    dev = state.device
+    channels = 1
+    if levels is not None:
+        if len(levels) != 2:
+            raise L.EnslamError(f"{what}: levels must be the pair (L_prev, L_cur)")
+        for name, t in zip(('L_prev', 'L_cur'), levels):
+            _event_sim_tensor(what, name, t, torch.float64, (H, W), dev)
+    else:
+        if not torch.is_tensor(prev) or not torch.is_tensor(cur):
+            raise L.EnslamError(f"{what}: prev and cur must be tensors (or pass `levels`)")
+        for name, t in (('prev', prev), ('cur', cur)):
+            if t.dim() not in (2, 3) or t.shape != cur.shape:
+                raise L.EnslamError(f"{what}: prev and cur must be uint8 tensors of one shape [H,W] or [H,W,C]")
+            shape = (H, W) if t.dim() == 2 else (H, W, int(t.shape[2]))
+            if t.dim() == 3 and shape[2] not in (1, 3):
+                raise L.EnslamError(f"{what}: images must have 1 or 3 channels (got {shape[2]})")
+            _event_sim_tensor(what, name, t, torch.uint8, shape, dev)
+        channels = 3 if cur.dim() == 3 and cur.shape[2] == 3 else 1
+        if channels == 1:
+            if lut is None:
+                raise L.EnslamError(f"{what}: grey images need the host-computed table `lut` (float64 [256])")
+            _event_sim_tensor(what, 'lut', lut, torch.float64, (256,), dev)
+    plan = event_sim_plan(H, W, substeps, eps, c_pos, c_neg, channels=channels, init=init)
+    with torch.cuda.device(dev):
+        events = None if init else torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
+        la, lb = levels if levels is not None else (None, None)
+        L.check(L.lib().enslam_event_sim_images(ctypes.byref(plan), _ptr(prev) if levels is None else None,
+                                                _ptr(cur) if levels is None else None, _ptr(lut), _ptr(la), _ptr(lb),
+                                                _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state), _ptr(events), _stream()),
+                "enslam_event_sim_images")
+    return events
+
+
+def event_sim_boxroom(room, poses, cam, state, eps=1e-3, c_pos=0.2, c_neg=0.2, c_pos_map=None, c_neg_map=None, init=False,
+                      want_frame=False):
+    """One interval of the analytic route (enslam_event_sim_boxroom, enslam_hip.h): the kernel renders synthetic.BoxRoom
+    `room` at the K poses `poses` (float64 [K,3|4,4] camera-to-world on the state's device, or a host array that is uploaded;
+    the last one is the frame the interval ends at) for the camera `cam` (H, W, fx, fy, cx, cy) and returns the events uint8
+    [H,W,2] = (-, +); `state` (L_ref, float64 [H,W]) is updated in place.  want_frame: also (color float64 [H,W,3], depth
+    float32 [H,W]) of the last pose, what BoxRoom.render returns.  init: the first frame -- no events (None), state := L."""
+    what = "event_sim_boxroom"
+    if not torch.is_tensor(state):
+        raise L.EnslamError(f"{what}: state must be a tensor")
+    H, W = int(cam['H']), int(cam['W'])
+    dev = state.device
+    p = poses if torch.is_tensor(poses) else torch.as_tensor(poses)
+    if p.dim() != 3 or p.shape[1] not in (3, 4) or p.shape[2] != 4 or p.dtype != torch.float64:
+        raise L.EnslamError(f"{what}: poses must be float64 [K,3|4,4] (got {p.dtype} {tuple(p.shape)})")
+    _event_sim_checks(what, H, W, int(p.shape[0]), eps, c_pos, c_neg, state, c_pos_map, c_neg_map, init)
+    if torch.is_tensor(poses):
+        _require_hip(poses, f"{what}: a pose tensor")
+    if not (float(cam['fx']) != 0 and float(cam['fy']) != 0):
+        raise L.EnslamError(f"{what}: fx and fy must not be zero")
+    p = p[:, :3, :].to(dev).contiguous()
+    plan = event_sim_plan(H, W, p.shape[0], eps, c_pos, c_neg, init=init, cam=cam, room=room)
+    with torch.cuda.device(dev):
+        events = None if init else torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
+        color = torch.empty((H, W, 3), dtype=torch.float64, device=dev) if want_frame else None
+        depth = torch.empty((H, W), dtype=torch.float32, device=dev) if want_frame else None
+        L.check(L.lib().enslam_event_sim_boxroom(ctypes.byref(plan), _ptr(p), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state),
+                                                 _ptr(events), _ptr(color), _ptr(depth), _stream()), "enslam_event_sim_boxroom")
+    return (events, color, depth) if want_frame else events

@@ -166,18 +166,36 @@ def demo_config(inp, evf, cam, device='cuda:0', env=None):
     }
 
 
-def write_demo_sequence(root, n, cam, step=0.012, yaw_deg=0.5):
-    """n frames of a BoxRoom inside the demo bound along `trajectory`, written in the Replica_event layout (all-zero events).
+def write_demo_sequence(root, n, cam, step=0.012, yaw_deg=0.5, events=None, sim=None):
+    """n frames of a BoxRoom inside the demo bound along `trajectory`, written in the Replica_event layout.
+    events: None writes all-zero event images; 'simulate' fills them from `event_sim.EventSimulator.step_scene` along the
+    trajectory with `sim` (default: a simulator with default parameters on the CPU, its numpy route; pass one on a HIP device
+    to run the kernel, which then renders the frames as well -- one launch per frame).
     Returns ((input_folder, event_folder), poses)."""
     from . import datasets as D
     from .scene import scene_bound
+    if events not in (None, 'simulate'):
+        raise ValueError(f"write_demo_sequence: events must be None or 'simulate' (got {events!r})")
     bound = scene_bound([[-1.0, 1.1], [-0.9, 0.8], [-0.7, 0.6]], 1.0, 0.32)
     room = BoxRoom.for_bound(bound, margin=0.12, seed=1)
     poses = trajectory(room, n, step=step, yaw_deg=yaw_deg)
-    frames, events = [], []
+    if events == 'simulate' and sim is None:
+        from .event_sim import EventSimulator
+        sim = EventSimulator(cam['H'], cam['W'], device='cpu')
+    frames, evs = [], []
     for i, c2w in enumerate(poses):
-        col, dep = room.render(c2w.double(), cam)
-        frames.append((col.numpy(), dep.numpy()))
-        if i > 0:
-            events.append(np.zeros((cam['H'], cam['W'], 2), dtype=np.uint8))
-    return D.write_replica_event_sequence(root, frames, [p.numpy() for p in poses], 6553.5, events), poses
+        if events is None:
+            col, dep = room.render(c2w.double(), cam)
+            if i > 0:
+                evs.append(np.zeros((cam['H'], cam['W'], 2), dtype=np.uint8))
+        elif i == 0:
+            col, dep = room.render(c2w.double(), cam)
+            sim.reset((room, c2w.double(), cam))
+        elif sim.on_device:
+            ev, col, dep = sim.step_scene(room, poses[i - 1].double(), c2w.double(), cam, want_frame=True)
+            evs.append(ev.cpu().numpy())
+        else:
+            col, dep = room.render(c2w.double(), cam)
+            evs.append(sim.step_scene(room, poses[i - 1].double(), c2w.double(), cam).numpy())
+        frames.append((col.cpu().numpy(), dep.cpu().numpy()))
+    return D.write_replica_event_sequence(root, frames, [p.numpy() for p in poses], 6553.5, evs), poses

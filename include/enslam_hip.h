@@ -889,6 +889,56 @@ int enslam_eventnet_conv3x3_wgrad(int32_t H, int32_t W, int32_t C0, int32_t C1, 
                                   int32_t Cn, const float *a0, const float *a1, const float *g, const float *saved, float *dw,
                                   float *db, float *scratch, int64_t scratch_floats, void *stream);
 
+/* Event-camera simulator (event_sim.py, csrc/event_sim.hip): a contrast-threshold sensor in the style of ESIM / vid2e.
+ * All arithmetic is float64.
+ *   luminance  Y = (0.299 R + 0.587 G) + 0.114 B of values in [0, 1] (a grey image is its own Y); L = log(Y + eps)
+ *   state      one reference level per pixel, L_ref float64 [H,W], updated in place and carried between intervals
+ *   interval   visited at K sub-steps s = 1..K; at each, with d = L - L_ref:
+ *                d >= C_pos:        n = floor(d / C_pos),  pos += n,  L_ref += n * C_pos
+ *                else -d >= C_neg:  n = floor(-d / C_neg), neg += n,  L_ref -= n * C_neg
+ *              (this closed form is the definition); the counts leave saturated at 255, L_ref moves by the unsaturated n
+ *   output     events uint8 [H,W,2] = (-, +)
+ *   thresholds the plan's scalars c_pos / c_neg, or per pixel where c_pos_map / c_neg_map (float64 [H,W]) are not NULL
+ *   init       plan.init != 0: no events; L_ref := L of the last sub-step (the first frame of a sequence).  events may
+ *              be NULL then and the thresholds are not looked at.
+ * One thread per pixel, one launch, no atomics: the output is deterministic.
+ *
+ * enslam_event_sim_images: two decoded uint8 images prev, cur [H,W,channels] (channels 1 or 3); sub-step s sees
+ *   L_a + (s / K) * (L_b - L_a), in this operation order.  L of a grey value comes from `lut` (device float64 [256], computed
+ *   by the host: required for channels = 1); of an RGB pixel from the three bytes / 255. and the device's log.  With L_prev
+ *   and L_cur (device float64 [H,W], both or neither) the images are not read (they may be NULL) and L_a, L_b are taken from
+ *   there: host-computed levels, so that no device log decides a count.
+ * enslam_event_sim_boxroom: the analytic room of synthetic.BoxRoom rendered inside the kernel at K poses (device float64
+ *   [K,12]: the rows of c2w[:3,:4], interpolated by the host); per pose BoxRoom.render / intersect / color_at step by step:
+ *   direction ((i - cx) / fx, -(j - cy) / fy, -1) rotated ((d0 R_c0 + d1 R_c1) + d2 R_c2), the |d| < 1e-12 clamp, wall exit
+ *   and box entry parameters, hit point o + d * t, colour 0.5 + 0.45 sin(((p0 f_c0 + p1 f_c1) + p2 f_c2) + phase_c),
+ *   luminance, log.  color_out (float64 [H,W,3]) and depth_out (float32 [H,W]), both or neither, receive the frame of the last
+ *   pose.
+ * ENSLAM_EINVAL without a launch: a NULL plan / L_ref, NULL events without init, events at an odd address, images route without a source of levels
+ *   (channels = 1 without lut, NULL prev or cur without L_prev / L_cur, only one of L_prev / L_cur), channels not 1 or 3,
+ *   NULL poses, only one of color_out / depth_out, H, W or K <= 0, eps, c_pos or c_neg (where no map replaces it) not a
+ *   positive finite number, fx or fy zero or not finite.  K above enslam_event_sim_max_substeps (64) or more than 2^28 pixels:
+ *   ENSLAM_EUNSUPPORTED. */
+typedef struct enslam_event_sim_plan {
+    int32_t H, W, K;
+    int32_t channels;               /* images route: 1 or 3 */
+    int32_t init;
+    int32_t has_box;                /* boxroom route: the box stands in the room */
+    double eps, c_pos, c_neg;
+    double fx, fy, cx, cy;          /* boxroom route */
+    double room_lo[3], room_hi[3], box_lo[3], box_hi[3];
+    double freq[9];                 /* [channel][axis] */
+    double phase[3];
+} enslam_event_sim_plan;
+int64_t enslam_event_sim_plan_bytes(void);           /* sizeof(enslam_event_sim_plan): binding self-check */
+int enslam_event_sim_max_substeps(void);
+int enslam_event_sim_images(const enslam_event_sim_plan *plan, const uint8_t *prev, const uint8_t *cur, const double *lut,
+                            const double *L_prev, const double *L_cur, const double *c_pos_map, const double *c_neg_map,
+                            double *L_ref, uint8_t *events, void *stream);
+int enslam_event_sim_boxroom(const enslam_event_sim_plan *plan, const double *poses, const double *c_pos_map,
+                             const double *c_neg_map, double *L_ref, uint8_t *events, double *color_out, float *depth_out,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,11 @@ completion and completion ratio (eval_recon, metres) against the room's analytic
 vertices and, under 'surface_samples', of area-weighted samples of the mesh (eval_recon.sample_surface); with --tsdf the
 keyframes' depth fused under the estimated poses (tsdf.TSDFVolume, the reference's voxel size) is written to DIR/tsdf.ply and
 evaluated beside the neural mesh, under 'tsdf'; --overlap selects
-the mapping window with mapping.keyframe_selection_method 'overlap' (mapper.keyframe_selection_overlap) instead of 'global'."""
+the mapping window with mapping.keyframe_selection_method 'overlap' (mapper.keyframe_selection_overlap) instead of 'global'.
+[--events simulate] writes the sequence with events simulated on the device (event_sim.EventSimulator over the trajectory,
+thresholds EVENT_C, default 0.2) instead of all-zero event images and sets event.activate_events; [--event-net PATH] loads a
+state_dict (tools/train_event_net.py) into a frozen eval-mode UNet_2heads(6, 2, 2) and hands it to the harness, which the
+event term needs; [--net-backend hip|torch] picks event.net_backend for it."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -64,18 +68,34 @@ def mesh_metrics(slam, path, n_gt=200000, tsdf=False):
     return out
 
 
-def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False):
+def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=None, event_net=None, net_backend=None):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
-        (inp, evf), poses = write_demo_sequence(os.path.join(tmp, 'data'), n, cam, step=float(os.environ.get('STEP', 0.012)), yaw_deg=float(os.environ.get('YAW', 0.5)))
+        sim = None
+        if events == 'simulate':
+            from evennicer_slam_amd.event_sim import EventSimulator
+            c = float(os.environ.get('EVENT_C', 0.2))
+            sim = EventSimulator(cam['H'], cam['W'], c_pos=c, c_neg=c, device=DEV)
+        (inp, evf), poses = write_demo_sequence(os.path.join(tmp, 'data'), n, cam, step=float(os.environ.get('STEP', 0.012)), yaw_deg=float(os.environ.get('YAW', 0.5)),
+                                                events=events, sim=sim)
         cfg = demo_config(inp, evf, cam, device=DEV, env=os.environ)
+        extra = {}
+        if events == 'simulate':
+            cfg['event'] = dict(cfg['event'], activate_events=True)
+        if event_net is not None:
+            from evennicer_slam_amd.event import UNet_2heads
+            net = UNet_2heads(6, 2, 2)
+            net.load_state_dict(torch.load(event_net, map_location='cpu'))
+            extra['event_net'] = net.requires_grad_(False).to(DEV).eval()
+            if net_backend is not None:
+                cfg['event'] = dict(cfg['event'], net_backend=net_backend)
         if overlap:
             cfg['mapping'] = dict(cfg['mapping'], keyframe_selection_method='overlap')
         ds = D.get_dataset(cfg, types.SimpleNamespace(input_folder=None, event_folder=None), 1, device=DEV)
         for tag, iters in ((('tracked', None),) if os.environ.get('SKIP_BASE') == '1' else (('tracked', None), ('const_speed_init', 0))):
             torch.manual_seed(0); np.random.seed(0)
-            slam = SLAM(cfg, ds, os.path.join(tmp, 'out_' + tag), device=DEV, static_shapes=True, verbose=os.environ.get('VERBOSE') == '1')
+            slam = SLAM(cfg, ds, os.path.join(tmp, 'out_' + tag), device=DEV, static_shapes=True, verbose=os.environ.get('VERBOSE') == '1', **extra)
             fit = slam.prefit_decoders(list(range(0, n, max(n // 6, 1))), iters=int(os.environ.get('PREFIT', 400)))
             res = slam.run(tracking_iters=iters)
             ate = slam.evaluate(res['ckpt'])
@@ -104,4 +124,12 @@ if __name__ == '__main__':
     tsdf = '--tsdf' in args
     if tsdf:
         args.remove('--tsdf')
-    run(int(args[0]) if args else 30, mesh_dir=mesh_dir, overlap=overlap, tsdf=tsdf)
+    opts = {}
+    for flag, key in (('--events', 'events'), ('--event-net', 'event_net'), ('--net-backend', 'net_backend')):
+        if flag in args:
+            k = args.index(flag)
+            opts[key] = args[k + 1]
+            del args[k:k + 2]
+    if opts.get('events') not in (None, 'simulate'):
+        raise SystemExit("--events takes 'simulate'")
+    run(int(args[0]) if args else 30, mesh_dir=mesh_dir, overlap=overlap, tsdf=tsdf, **opts)
