@@ -716,8 +716,9 @@ int enslam_render_fwd(int32_t stage, int32_t n_rays, int32_t n_samples, const fl
     if (act_ws != nullptr)                               // the saved cell records hold the voxel index in 29 bits
         for (int k = 1; k < 4; ++k)
             if (d.grid[k].data && (int64_t)d.grid[k].D * d.grid[k].H * d.grid[k].W >= ACT_MAX_VOXELS) return ENSLAM_EUNSUPPORTED;
-    return ens_launch_render_fwd(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, nullptr, 0, 1, d, depth, var,
-                                 rgb, raw_out, stage == ENSLAM_STAGE_COARSE ? nullptr : act_ws, act_light != 0, (hipStream_t)stream);
+    const int rc = ens_launch_render_fwd(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, nullptr, 0, 1, d, depth, var,
+                                         rgb, raw_out, stage == ENSLAM_STAGE_COARSE ? nullptr : act_ws, act_light != 0, (hipStream_t)stream);
+    return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EUNSUPPORTED : ENSLAM_ELAUNCH);     // (64 samples without raw_out)
 }
 
 int enslam_render_loss_fwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
