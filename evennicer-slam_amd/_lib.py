@@ -289,6 +289,12 @@ _SIGS = {
                                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "enslam_event_sim_boxroom": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_void_p]),
+    "enslam_vis_panels_workspace": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "enslam_vis_panels": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                         c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "enslam_ssim_workspace": (ctypes.c_int, [c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "enslam_ssim": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
+                                   c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -2839,3 +2839,95 @@ def event_sim_boxroom(room, poses, cam, state, eps=1e-3, c_pos=0.2, c_neg=0.2, c
         L.check(L.lib().enslam_event_sim_boxroom(ctypes.byref(plan), _ptr(p), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state),
                                                  _ptr(events), _ptr(color), _ptr(depth), _stream()), "enslam_event_sim_boxroom")
     return (events, color, depth) if want_frame else events
+
+
+# ------------------------------------------------------------------------------------------------
+# Frame report (csrc/frame_report.hip; frame_vis.Visualizer and frame_vis.render_metrics drive it)
+# ------------------------------------------------------------------------------------------------
+SSIM_TILE = (16, 32)                    # ENSLAM_SSIM_TILE_H, ENSLAM_SSIM_TILE_W: output pixels of one workgroup
+VIS_STAT_NAMES = ('n_valid', 'depth_abs_sum', 'color_sq_sum', 'color_sq_sum_valid')
+
+
+def _report_image(what, name, t, shape, dev):
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or (dev is not None and t.device != dev):
+        raise L.EnslamError(f"{what}: {name} must be a float tensor {list(shape)}" + (f" on {dev}" if dev is not None else "") +
+                            f" (got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__})")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise L.EnslamError(f"{what}: {name} must be float32 or float64 (got {t.dtype})")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def vis_panels(gt_depth, gt_color, depth, color, gt_event=None, pred_event=None, gutter=8, title=16):
+    """(sheet, stats): the figure of the reference's Visualizer as one uint8 image [R H + (R + 1) g + R t, 3 W + 4 g, 3] on the
+    HIP device of the inputs -- rows depth, colour and, with gt_event / pred_event (float [h,w,2], both or neither), events;
+    columns input, generated, residual; g = gutter, t = title, the white strip above each panel -- and stats, a float64 [8]
+    device tensor {n_valid, sum |depth residual| over gt_depth > 0, sum of squared clipped colour error over everything and
+    over gt_depth > 0} followed by the sums of the absolute terms (VIS_STAT_NAMES; enslam_vis_panels in enslam_hip.h holds
+    every pixel rule).  gt_depth, depth: [H,W]; gt_color, color: [H,W,3]; float64 inputs are cast to float32 once.  Nothing is
+    brought to the host here."""
+    what = "vis_panels"
+    if not isinstance(gt_depth, torch.Tensor) or not gt_depth.is_cuda:
+        raise NotImplementedError("vis_panels needs a HIP device")
+    if gt_depth.dim() != 2:
+        raise L.EnslamError(f"{what}: gt_depth must be [H,W] (got {tuple(gt_depth.shape)})")
+    H, W, dev = int(gt_depth.shape[0]), int(gt_depth.shape[1]), gt_depth.device
+    gd = _report_image(what, 'gt_depth', gt_depth, (H, W), dev)
+    gc = _report_image(what, 'gt_color', gt_color, (H, W, 3), dev)
+    d = _report_image(what, 'depth', depth, (H, W), dev)
+    c = _report_image(what, 'color', color, (H, W, 3), dev)
+    if (gt_event is None) != (pred_event is None):
+        raise L.EnslamError(f"{what}: gt_event and pred_event come together")
+    ge = pe = None
+    h = w = 0
+    if gt_event is not None:
+        if gt_event.dim() != 3 or gt_event.shape[2] != 2:
+            raise L.EnslamError(f"{what}: gt_event must be [h,w,2] (got {tuple(gt_event.shape)})")
+        h, w = int(gt_event.shape[0]), int(gt_event.shape[1])
+        ge = _report_image(what, 'gt_event', gt_event, (h, w, 2), dev)
+        pe = _report_image(what, 'pred_event', pred_event, (h, w, 2), dev)
+    rows, g, t = 3 if ge is not None else 2, int(gutter), int(title)
+    if g < 0 or t < 0:
+        raise L.EnslamError(f"{what}: gutter and title must not be negative (got {gutter}, {title})")
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        nbytes = ctypes.c_int64()
+        L.check(lib.enslam_vis_panels_workspace(H, W, rows, g, t, ctypes.byref(nbytes)), "enslam_vis_panels_workspace")
+        ws = torch.empty(nbytes.value // 8, dtype=torch.float64, device=dev)
+        sheet = torch.empty((rows * H + (rows + 1) * g + rows * t, 3 * W + 4 * g, 3), dtype=torch.uint8, device=dev)
+        stats = torch.empty(8, dtype=torch.float64, device=dev)
+        L.check(lib.enslam_vis_panels(_ptr(gd), _ptr(gc), _ptr(d), _ptr(c), _ptr(ge), _ptr(pe), H, W, h, w, g, t, _ptr(ws),
+                                      nbytes.value, _ptr(sheet), _ptr(stats), _stream()), "enslam_vis_panels")
+    return sheet, stats
+
+
+def ssim(x, y, want_map=False):
+    """Mean structural similarity of two images on a HIP device as a float64 [1] device tensor (with want_map the tuple (mean,
+    map float64 [H-10,W-10,C])): x, y float [H,W,C] or [H,W], C 1 or 3, data range 1; 11 x 11 Gaussian window of sigma 1.5,
+    K1 = 0.01, K2 = 0.03, population covariance, the mean over the interior and the channels, moments in float64
+    (enslam_ssim, enslam_hip.h).  What skimage.metrics.structural_similarity(gaussian_weights=True, sigma=1.5,
+    use_sample_covariance=False, data_range=1) and pytorch_msssim compute.  H, W >= 11."""
+    what = "ssim"
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise NotImplementedError("ssim needs a HIP device")
+    if x.dim() == 2:
+        x = x[..., None]
+        y = y[..., None] if isinstance(y, torch.Tensor) and y.dim() == 2 else y
+    if x.dim() != 3:
+        raise L.EnslamError(f"{what}: x must be [H,W,C] or [H,W] (got {tuple(x.shape)})")
+    H, W, C, dev = int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), x.device
+    if C not in (1, 3):
+        raise L.EnslamError(f"{what}: 1 or 3 channels (got {C})")
+    if H < 11 or W < 11:
+        raise L.EnslamError(f"{what}: the window is 11 x 11, the images are {H} x {W}")
+    a = _report_image(what, 'x', x, (H, W, C), dev)
+    b = _report_image(what, 'y', y, (H, W, C), dev)
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        nbytes = ctypes.c_int64()
+        L.check(lib.enslam_ssim_workspace(H, W, C, ctypes.byref(nbytes)), "enslam_ssim_workspace")
+        ws = torch.empty(nbytes.value // 8, dtype=torch.float64, device=dev)
+        mean = torch.empty(1, dtype=torch.float64, device=dev)
+        smap = torch.empty((H - 10, W - 10, C), dtype=torch.float64, device=dev) if want_map else None
+        L.check(lib.enslam_ssim(_ptr(a), _ptr(b), H, W, C, _ptr(ws), nbytes.value, _ptr(mean), _ptr(smap), _stream()),
+                "enslam_ssim")
+    return (mean, smap) if want_map else mean

@@ -24,7 +24,10 @@ sequence, the decoders are kept, the grids are re-initialised -- the run itself 
 only, as the reference does.
 
 Mesh extraction is opt-in: `SLAM.get_mesh` (or `run(mesh_file=...)`) runs `mesher.Mesher.get_mesh` on the run's keyframes and
-poses.  Not here: visualiser, wandb."""
+poses.  The per-iteration figures of the reference's Visualizer are opt-in too: `SLAM(vis=True)` builds one
+`frame_vis.Visualizer` for the tracker (`tracking.vis_freq` / `vis_inside_freq`, folder `tracking_vis`) and one for the mapper
+(`mapping.vis_freq` / `vis_inside_freq`, folder `mapping_vis`) and calls them where Tracker.py:306-308,444-447 and
+Mapper.py:705-713 do; `mapping.no_vis_on_first_frame` is honoured (absent: False).  Not here: wandb."""
 import os
 import time
 import types
@@ -77,7 +80,8 @@ def frustum_mask(c2w, depth, shape, bound, cam):
 
 
 class SLAM:
-    def __init__(self, cfg, dataset, output, device='cuda:0', event_net=None, verbose=False, static_shapes=False):
+    def __init__(self, cfg, dataset, output, device='cuda:0', event_net=None, verbose=False, static_shapes=False, vis=False,
+                 experiment=None):
         self.cfg, self.dataset, self.output, self.device, self.verbose = cfg, dataset, output, device, verbose
         self.static_shapes = static_shapes
         self.scale = cfg['scale']
@@ -114,6 +118,16 @@ class SLAM:
         self.tracker = TrackerIteration(cfg, None, self)
         self.keyframe_dict, self.keyframe_list = [], []
         self.timing = dict(track=0.0, map=0.0)
+        self.vis_tracker = self.vis_mapper = None
+        if vis:
+            from .frame_vis import Visualizer
+            tr, mp = cfg['tracking'], cfg['mapping']
+            self.vis_tracker = Visualizer(freq=tr.get('vis_freq', 50), inside_freq=tr.get('vis_inside_freq', 25),
+                                          vis_dir=os.path.join(output, 'tracking_vis'), renderer=self.renderer, verbose=verbose,
+                                          experiment=experiment, device=device, stage='tracker')
+            self.vis_mapper = Visualizer(freq=mp.get('vis_freq', 50), inside_freq=mp.get('vis_inside_freq', 30),
+                                         vis_dir=os.path.join(output, 'mapping_vis'), renderer=self.renderer, verbose=verbose,
+                                         experiment=experiment, device=device, stage='mapper')
 
     # ---------------------------------------------------------------- tracker side
     def update_para_from_mapping(self):
@@ -148,6 +162,8 @@ class SLAM:
                 first_loss = loss
             if best_loss is None or loss < best_loss:                       # Tracker.py:321-330 (candidate with the least loss)
                 best_loss, best = loss, camera_tensor.detach().clone()
+            if self.vis_tracker is not None:
+                self._vis_camera_iteration(idx, it, gt_depth, gt_color, camera_tensor, out if use_event else None)
         c2w = torch.eye(4, device=self.device)
         c2w[:3] = get_camera_from_tensor(best)
         if self.verbose:
@@ -155,6 +171,20 @@ class SLAM:
             print(f'frame {idx}: tracking loss {first_loss} -> {best_loss}; translation error init '
                   f'{float((est[:3, 3] - gt).norm()):.4f} -> {float((c2w[:3, 3] - gt).norm()):.4f} m', flush=True)
         return c2w
+
+    def _vis_camera_iteration(self, idx, it, gt_depth, gt_color, camera_tensor, out):
+        """The tracker's figure of camera iteration `it` (Tracker.py:444-447): with the event term `out` is the tuple of
+        `optimize_cam_in_batch` (low-resolution ground-truth events at [3], predicted events at [4], with blur the lists at
+        [5], [6]); without it (None) the two-row figure."""
+        v, trk = self.vis_tracker, self.tracker
+        if not v.due(idx, it):
+            return
+        if out is not None and out[4] is not None:
+            blurred = (out[5], out[6]) if len(out) == 10 else ([], [])
+            v.vis_event(idx, it, gt_depth, gt_color, None, out[3], out[4], blurred[0], blurred[1], camera_tensor.detach(), trk.c,
+                        trk.decoders)
+        else:
+            v.vis(idx, it, gt_depth, gt_color, camera_tensor.detach(), trk.c, trk.decoders)
 
     def _track_graphed(self, idx, est, gt_color, gt_depth, gt_event, gt_mask, pre_gt_color, t, use_event):
         """`track` with the camera iterations as replays of ONE hipGraph (tracker.GraphedCameraIteration, captured at the first tracked
@@ -188,6 +218,8 @@ class SLAM:
             l_rgbd, l_event, _l_mask = git.step()
             g['losses'][it].copy_(l_rgbd + l_event if use_event else l_rgbd)
             g['cams'][it].copy_(ct.detach().reshape(-1))         # the candidate of this loss: the pose AFTER the step (Tracker.py:321-330)
+            if self.vis_tracker is not None:                     # between two replays, never inside a capture: the captured camera tensor
+                self._vis_camera_iteration(idx, it, gt_depth, gt_color, ct.detach().reshape(-1), None)
         k = torch.argmin(g['losses'])
         best = g['cams'][k]
         c2w = torch.eye(4, device=self.device)
@@ -229,8 +261,13 @@ class SLAM:
         it = MapperIteration(cfg, self.renderer, self.shared_c, self.shared_decoders, frames, self.cam, masks=masks, keys=MAP_KEYS,
                              static_shapes=self.static_shapes)
         loss = None
+        show = self.vis_mapper is not None and not (idx == 0 and m.get('no_vis_on_first_frame', False))
         for j in range(iters):
             loss = it.step(j, iters)
+            if show and self.vis_mapper.due(idx, j):                         # Mapper.py:705-713
+                ct = it.camera_tensors[-1]
+                self.vis_mapper.vis(idx, j, gt_depth, gt_color.float(), cur_c2w if ct is None else ct.detach(),
+                                    it.grid_opt.render_grids(), self.shared_decoders)
         cams = it.finish()
         if self.cfg.get('coarse', False):
             # the coarse mapper's round on this frame (the reference's third process): stage `coarse`, every voxel of grid_coarse,
@@ -314,6 +351,10 @@ class SLAM:
             t0 = time.perf_counter()
             if idx == 0 or t.get('gt_camera', False):
                 c2w = gt_c2w.clone()
+                if self.vis_tracker is not None and not m.get('no_vis_on_first_frame', False):           # Tracker.py:306-308
+                    # (before the first mapping round the tracker holds no copy of the map yet: the shared one)
+                    self.vis_tracker.vis(idx, 0, gt_depth, gt_color.float(), c2w.to(self.device), self.tracker.c or self.shared_c,
+                                         self.tracker.decoders or self.shared_decoders)
             else:
                 c2w = self.track(idx, gt_color.float(), gt_depth, gt_event, gt_mask, pre_color)
             torch.cuda.synchronize()

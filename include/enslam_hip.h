@@ -939,6 +939,52 @@ int enslam_event_sim_boxroom(const enslam_event_sim_plan *plan, const double *po
                              const double *c_neg_map, double *L_ref, uint8_t *events, double *color_out, float *depth_out,
                              void *stream);
 
+/* Per-iteration frame report (frame_vis.py, csrc/frame_report.hip): the figure of the reference's src/utils/Visualizer.py
+ * as one uint8 sheet, the frame's error sums, and the mean SSIM of two images.
+ *
+ * enslam_vis_panels: inputs gt_depth, depth float32 [H,W], gt_color, color float32 [H,W,3] and, both or neither, gt_event,
+ *   pred_event float32 [h,w,2] at their own resolution.  sheet uint8 [R H + (R + 1) g + R t, 3 W + 4 g, 3] with R = 2 rows of
+ *   panels without events and 3 with them, g = gutter and t = title: panel (r, c) starts at row g + t + r (H + g + t) and
+ *   column g + c (W + g); gutters and the title strip above each panel are 255 (the host draws the titles after the download).
+ *   Columns are input, generated, residual; rows depth, colour, events.  Every rule is float32 with separate operations:
+ *     max_depth  the maximum of gt_depth (a NaN is skipped), reduced on the device first
+ *     depth      max_depth == 0: entry 0 of the table; else u = v / max_depth: NaN white, u < 0 entry 0, u >= 1 entry 255,
+ *                else entry (int)(u * 256.0f) of the 256-entry plasma table (csrc/plasma_lut.hpp); the residual is
+ *                |gt - pred|, 0 where gt_depth == 0, against the same max_depth
+ *     colour     c' = c > 0 ? c : 0, then c' < 1 ? c' : 1 (a NaN gives 0), level (uint8)(c' * 255.0f + 0.5f); the residual is
+ *                |gt - pred| per channel, 0 where gt_depth == 0, then the same
+ *     events     channels (e0, e1, 0), level (uint8) of e * 50.0f limited to [0, 255] the same way; panel pixel (y, x) shows
+ *                source pixel ((2 y + 1) h / (2 H), (2 x + 1) w / (2 W)) in integer arithmetic; the residual is |a - b| of the
+ *                two levels (the reference subtracts the uint8 arrays, which wraps)
+ *   stats (device float64 [8]): {n, L, S, Sv, n, L, S, Sv} with n the number of pixels with gt_depth > 0, L the sum over
+ *   them of |gt_depth - depth| (float32, added in float64), S the sum over all pixels and channels of (c'(gt) - c'(pred))^2
+ *   (the difference float32, squared and added in float64), Sv the same over the gt_depth > 0 pixels; the second four are
+ *   the sums of the absolute values of the terms (all terms are non-negative, so they repeat the first four).  Sums are per
+ *   workgroup, then over the workgroups in index order: no float atomics, the same bits in every run.
+ *   workspace: enslam_vis_panels_workspace bytes, 8-byte aligned; sheet 4-byte aligned.  Three launches.
+ *   ENSLAM_EINVAL without a launch: a NULL pointer where data is required, only one of the event images, H, W <= 0 (h, w
+ *   with events), negative gutter or title, a workspace too small or misaligned.  More than 2^31 sheet pixels:
+ *   ENSLAM_EUNSUPPORTED.
+ *
+ * enslam_ssim: mean structural similarity (Wang et al. 2004) of x, y float32 [H,W,C], C 1 or 3, data range 1: 11 x 11
+ *   normalised Gaussian window of sigma 1.5 (the outer product of the normalised 11-tap window), K1 = 0.01, K2 = 0.03,
+ *   population covariance, the mean over the (H - 10) x (W - 10) interior and the channels.  The five windowed moments are
+ *   float64.  One workgroup per ENSLAM_SSIM_TILE_H x ENSLAM_SSIM_TILE_W tile of the interior and channel; mean_out (device
+ *   float64 [1]) is the sum of the per-workgroup sums in index order, divided by the count; map_out (device float64
+ *   [H-10,W-10,C]) may be NULL.  workspace: enslam_ssim_workspace bytes, 8-byte aligned.  Two launches.
+ *   ENSLAM_EINVAL without a launch: NULL x, y, workspace or mean_out, H or W < 11, C not 1 or 3, a workspace too small.
+ *   More than 2^28 pixels: ENSLAM_EUNSUPPORTED. */
+#define ENSLAM_SSIM_TILE_H 16
+#define ENSLAM_SSIM_TILE_W 32
+int enslam_vis_panels_workspace(int32_t H, int32_t W, int32_t rows, int32_t gutter, int32_t title, int64_t *bytes_host);
+int enslam_vis_panels(const float *gt_depth, const float *gt_color, const float *depth, const float *color,
+                      const float *gt_event, const float *pred_event, int32_t H, int32_t W, int32_t h, int32_t w,
+                      int32_t gutter, int32_t title, void *workspace, int64_t workspace_bytes, uint8_t *sheet, double *stats,
+                      void *stream);
+int enslam_ssim_workspace(int32_t H, int32_t W, int32_t C, int64_t *bytes_host);
+int enslam_ssim(const float *x, const float *y, int32_t H, int32_t W, int32_t C, void *workspace, int64_t workspace_bytes,
+                double *mean_out, double *map_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 
     python tools/run_slam.py CONFIG [--default-config PATH] [--input_folder DIR] [--event_folder DIR] [--output DIR]
                                     [--max-frames N] [--prepare host|device] [--prefit ITERS] [--device cuda:0]
-                                    [--event-net PATH] [--net-backend hip|torch]
+                                    [--event-net PATH] [--net-backend hip|torch] [--vis]
 
 CONFIG may name parents with `inherit_from` (config.load_config); --default-config is the root under a chain that names
 none (the reference passes configs/nice_slam.yaml).  The reference's YAML files are not part of this repository: point at
@@ -47,6 +47,7 @@ def main(argv=None):
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--event-net', default=None)
     ap.add_argument('--net-backend', choices=('hip', 'torch'), default=None)
+    ap.add_argument('--vis', action='store_true')
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -71,7 +72,7 @@ def main(argv=None):
         extra['event_net'] = net.requires_grad_(False).to(args.device).eval()
         if args.net_backend is not None:
             cfg.setdefault('event', {})['net_backend'] = args.net_backend
-    slam = SLAM(slam_camera(cfg), ds, output, device=args.device, static_shapes=True, **extra)
+    slam = SLAM(slam_camera(cfg), ds, output, device=args.device, static_shapes=True, vis=args.vis, **extra)
     n = len(ds) if args.max_frames is None else min(args.max_frames, len(ds))
     if args.prefit > 0:
         slam.prefit_decoders(list(range(0, n, max(n // 6, 1))), iters=args.prefit)

@@ -9,7 +9,9 @@ the mapping window with mapping.keyframe_selection_method 'overlap' (mapper.keyf
 [--events simulate] writes the sequence with events simulated on the device (event_sim.EventSimulator over the trajectory,
 thresholds EVENT_C, default 0.2) instead of all-zero event images and sets event.activate_events; [--event-net PATH] loads a
 state_dict (tools/train_event_net.py) into a frozen eval-mode UNet_2heads(6, 2, 2) and hands it to the harness, which the
-event term needs; [--net-backend hip|torch] picks event.net_backend for it."""
+event term needs; [--net-backend hip|torch] picks event.net_backend for it; [--vis DIR] keeps the tracked run's per-iteration
+figures (frame_vis.Visualizer: DIR/tracking_vis, DIR/mapping_vis; VIS_FREQ and VIS_INSIDE_FREQ, default 5 and 10, set both
+stages' vis_freq / vis_inside_freq)."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -68,7 +70,7 @@ def mesh_metrics(slam, path, n_gt=200000, tsdf=False):
     return out
 
 
-def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=None, event_net=None, net_backend=None):
+def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=None, event_net=None, net_backend=None, vis=None):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -92,10 +94,15 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=Non
                 cfg['event'] = dict(cfg['event'], net_backend=net_backend)
         if overlap:
             cfg['mapping'] = dict(cfg['mapping'], keyframe_selection_method='overlap')
+        if vis is not None:
+            freq = dict(vis_freq=int(os.environ.get('VIS_FREQ', 5)), vis_inside_freq=int(os.environ.get('VIS_INSIDE_FREQ', 10)))
+            cfg['mapping'], cfg['tracking'] = dict(cfg['mapping'], **freq), dict(cfg['tracking'], **freq)
         ds = D.get_dataset(cfg, types.SimpleNamespace(input_folder=None, event_folder=None), 1, device=DEV)
         for tag, iters in ((('tracked', None),) if os.environ.get('SKIP_BASE') == '1' else (('tracked', None), ('const_speed_init', 0))):
             torch.manual_seed(0); np.random.seed(0)
-            slam = SLAM(cfg, ds, os.path.join(tmp, 'out_' + tag), device=DEV, static_shapes=True, verbose=os.environ.get('VERBOSE') == '1', **extra)
+            shown = vis is not None and tag == 'tracked'
+            slam = SLAM(cfg, ds, vis if shown else os.path.join(tmp, 'out_' + tag), device=DEV, static_shapes=True,
+                        verbose=os.environ.get('VERBOSE') == '1', **(dict(extra, vis=True) if shown else extra))
             fit = slam.prefit_decoders(list(range(0, n, max(n // 6, 1))), iters=int(os.environ.get('PREFIT', 400)))
             res = slam.run(tracking_iters=iters)
             ate = slam.evaluate(res['ckpt'])
@@ -125,7 +132,7 @@ if __name__ == '__main__':
     if tsdf:
         args.remove('--tsdf')
     opts = {}
-    for flag, key in (('--events', 'events'), ('--event-net', 'event_net'), ('--net-backend', 'net_backend')):
+    for flag, key in (('--events', 'events'), ('--event-net', 'event_net'), ('--net-backend', 'net_backend'), ('--vis', 'vis')):
         if flag in args:
             k = args.index(flag)
             opts[key] = args[k + 1]
