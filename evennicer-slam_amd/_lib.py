@@ -283,6 +283,19 @@ _SIGS = {
     "enslam_eventnet_conv3x3_wgrad": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                                      c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                      c_void_p, c_int64, c_void_p]),
+    "enslam_eventnet_bn_stats": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "enslam_eventnet_bn_apply": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int64, c_int32,
+                                                c_int32, c_void_p, c_void_p]),
+    "enslam_eventnet_bn_backward": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int64,
+                                                   c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "enslam_eventnet_bn_running": (ctypes.c_int, [POINTER(c_void_p), c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double,
+                                                  c_void_p]),
+    "enslam_eventnet_bn_workspace_floats": (c_size_t, [c_int32, c_int32, c_int32]),
+    "enslam_eventnet_bn_saved_offset": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "enslam_eventnet_train_forward": (ctypes.c_int, [POINTER(c_void_p), c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_eventnet_train_backward": (ctypes.c_int, [POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                      c_double, c_void_p, POINTER(c_void_p), c_void_p]),
     "enslam_event_sim_plan_bytes": (c_int64, []),
     "enslam_event_sim_max_substeps": (ctypes.c_int, []),
     "enslam_event_sim_images": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

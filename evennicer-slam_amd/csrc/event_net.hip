@@ -32,6 +32,9 @@
 //                    few output tiles split the PIXEL axis over blockIdx.z; conv3x3_wgrad_reduce_kernel sums the partials
 //                    in split order (no atomics).
 //   heads_wgrad      gradients of the heads block, a fixed-order two-stage reduction over the pixels.
+//
+// Training-mode BatchNorm and batches (the unfolded net, enslam_eventnet_bn_* / enslam_eventnet_train_*) are the last section
+// of this file, with their own notes.
 #include "../../include/enslam_hip.h"
 #include "common.hpp"
 #include <algorithm>
@@ -1049,6 +1052,655 @@ int enslam_eventnet_up2(const float* in, int32_t h, int32_t w, int32_t C, float*
     hipStream_t st = (hipStream_t)stream;
     if (backward) up2_bwd_kernel<<<blocks_of((int64_t)h * w * C), 256, 0, st>>>(in, h, w, C, out, 0);
     else up2_fwd_kernel<<<blocks_of((int64_t)4 * h * w * C), 256, 0, st>>>(in, h, w, C, out);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+}  // extern "C"
+
+// ===============================================================================================================
+// Training-mode BatchNorm and batches (enslam_eventnet_bn_*, enslam_eventnet_train_*): the unfolded network.  Every
+// convolution writes its raw output z [B*H*W][C]; BatchNorm's batch statistics couple the images of a batch, so its three
+// kernels see all M = B*H*W rows at once, while the convolution / pooling / up-sampling / weight-gradient launchers above
+// run once per image.
+//
+// The BatchNorm kernels are bandwidth-bound streams over a row-major [M][C] matrix.  A workgroup owns BN_ROWS consecutive rows
+// of a slab of up to BN_SLAB channels: a slab's row is cw / 4 float4 loads by consecutive threads (tpr threads per row), and
+// 256 / tpr rows are in flight per pass, so a wave's loads are contiguous runs of at least 32 bytes at C = 8, whole 256-byte
+// rows at C = 64 and 1 KiB runs at C = 1024.  The split of M (chunks of BN_ROWS rows) depends on M alone, and every sum runs in
+// a fixed order (thread-private over its rows, then over the row sub-sets in LDS, then over the chunks), all in float64: two
+// runs, and two boxes, are bit-equal.
+// ===============================================================================================================
+namespace {
+
+constexpr int BN_ROWS = 256;
+constexpr int BN_SLAB = 256;
+constexpr int BN_THREADS = 256;
+constexpr int EN_BN_CHANNELS = 5888;          // the 26 BatchNorms' channels in all
+
+struct BnGeom {
+    int c0, cw, tpr, rp, c4, rs, r0, r1;
+    bool active;
+};
+ENS_DEV BnGeom bn_geom(int M, int C) {
+    BnGeom g;
+    g.c0 = blockIdx.y * BN_SLAB;
+    g.cw = min(BN_SLAB, C - g.c0);
+    g.tpr = g.cw / 4;
+    g.rp = BN_THREADS / g.tpr;
+    g.active = (int)threadIdx.x < g.tpr * g.rp;
+    g.c4 = threadIdx.x % g.tpr;
+    g.rs = threadIdx.x / g.tpr;
+    g.r0 = blockIdx.x * BN_ROWS;
+    g.r1 = min(g.r0 + BN_ROWS, M);
+    return g;
+}
+// v summed over the workgroup's row sub-sets in ascending order; the result is valid in the threads with rs == 0
+ENS_DEV void bn_reduce(double (*red)[4], const BnGeom& g, double v[4]) {
+    __syncthreads();
+    if (g.active)
+        for (int e = 0; e < 4; ++e) red[threadIdx.x][e] = v[e];
+    __syncthreads();
+    if (g.active && g.rs == 0)
+        for (int e = 0; e < 4; ++e) {
+            double s = red[g.c4][e];
+            for (int k = 1; k < g.rp; ++k) s = s + red[k * g.tpr + g.c4][e];
+            v[e] = s;
+        }
+}
+
+// per chunk and channel: the chunk's mean and its centred sum of squares (two passes over the chunk, the second from cache).
+// part [chunks][2][C]
+__global__ __launch_bounds__(BN_THREADS) void bn_stats_chunk_kernel(const float* __restrict__ z, int M, int C,
+                                                                    double* __restrict__ part) {
+    __shared__ double red[BN_THREADS][4];
+    __shared__ double smean[BN_SLAB];
+    const BnGeom g = bn_geom(M, C);
+    const float* base = z + g.c0 + 4 * g.c4;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    if (g.active)
+        for (int r = g.r0 + g.rs; r < g.r1; r += g.rp) {
+            const f32x4 v = ld4(base + (int64_t)r * C);
+            for (int e = 0; e < 4; ++e) s[e] = s[e] + (double)v[e];
+        }
+    bn_reduce(red, g, s);
+    if (g.active && g.rs == 0)
+        for (int e = 0; e < 4; ++e) smean[4 * g.c4 + e] = s[e] / (double)(g.r1 - g.r0);
+    __syncthreads();
+    double m[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    if (g.active) {
+        for (int e = 0; e < 4; ++e) m[e] = smean[4 * g.c4 + e];
+        for (int r = g.r0 + g.rs; r < g.r1; r += g.rp) {
+            const f32x4 v = ld4(base + (int64_t)r * C);
+            for (int e = 0; e < 4; ++e) {
+                const double d = (double)v[e] - m[e];
+                q[e] = q[e] + d * d;
+            }
+        }
+    }
+    bn_reduce(red, g, q);
+    if (g.active && g.rs == 0)
+        for (int e = 0; e < 4; ++e) {
+            const int c = g.c0 + 4 * g.c4 + e;
+            part[((int64_t)blockIdx.x * 2) * C + c] = m[e];
+            part[((int64_t)blockIdx.x * 2 + 1) * C + c] = q[e];
+        }
+}
+
+// Chan's merge of the chunks in chunk order: mean, and the biased variance M2 / M
+__global__ __launch_bounds__(256) void bn_stats_finish_kernel(const double* __restrict__ part, int M, int C,
+                                                              double* __restrict__ mean, double* __restrict__ var) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const int chunks = (M + BN_ROWS - 1) / BN_ROWS;
+    double n = (double)min(BN_ROWS, M), mu = part[c], m2 = part[C + c];
+    for (int k = 1; k < chunks; ++k) {
+        const double nb = (double)(min((k + 1) * BN_ROWS, M) - k * BN_ROWS);
+        const double mb = part[((int64_t)k * 2) * C + c], qb = part[((int64_t)k * 2 + 1) * C + c];
+        const double nt = n + nb, delta = mb - mu;
+        mu = mu + delta * (nb / nt);
+        m2 = (m2 + qb) + (delta * delta) * (n * nb / nt);
+        n = nt;
+    }
+    mean[c] = mu;
+    var[c] = m2 / (double)M;
+}
+
+// y = relu?((float)(a * ((double)z - mean) + (double)beta)),  a = (double)gamma / sqrt(var + eps)
+__global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const float* __restrict__ z, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, const double* __restrict__ mean,
+                                                              const double* __restrict__ var, double eps, int M, int C, int relu,
+                                                              float* __restrict__ y) {
+    __shared__ double sa[BN_SLAB], sm[BN_SLAB], sb[BN_SLAB];
+    const BnGeom g = bn_geom(M, C);
+    if ((int)threadIdx.x < g.cw) {
+        const int c = g.c0 + threadIdx.x;
+        sa[threadIdx.x] = (double)gamma[c] / sqrt(var[c] + eps);
+        sm[threadIdx.x] = mean[c];
+        sb[threadIdx.x] = (double)beta[c];
+    }
+    __syncthreads();
+    if (!g.active) return;
+    double a[4], m[4], b[4];
+    for (int e = 0; e < 4; ++e) { a[e] = sa[4 * g.c4 + e]; m[e] = sm[4 * g.c4 + e]; b[e] = sb[4 * g.c4 + e]; }
+    for (int r = g.r0 + g.rs; r < g.r1; r += g.rp) {
+        const int64_t at = (int64_t)r * C + g.c0 + 4 * g.c4;
+        const f32x4 v = ld4(z + at);
+        f32x4 o;
+        for (int e = 0; e < 4; ++e) {
+            const float w = (float)(a[e] * ((double)v[e] - m[e]) + b[e]);
+            o[e] = relu ? (w > 0.f ? w : 0.f) : w;
+        }
+        *reinterpret_cast<f32x4*>(y + at) = o;
+    }
+}
+
+// per chunk and channel: sum gh and sum gh * xh,  gh = g_y where y > 0 (all of g_y without y),
+// xh = ((double)z - mean) * (1 / sqrt(var + eps)).  part [chunks][2][C]
+__global__ __launch_bounds__(BN_THREADS) void bn_bwd_chunk_kernel(const float* __restrict__ z, const float* __restrict__ y,
+                                                                  const float* __restrict__ g_y, const double* __restrict__ mean,
+                                                                  const double* __restrict__ var, double eps, int M, int C,
+                                                                  double* __restrict__ part) {
+    __shared__ double red[BN_THREADS][4];
+    __shared__ double sm[BN_SLAB], si[BN_SLAB];
+    const BnGeom g = bn_geom(M, C);
+    if ((int)threadIdx.x < g.cw) {
+        sm[threadIdx.x] = mean[g.c0 + threadIdx.x];
+        si[threadIdx.x] = 1.0 / sqrt(var[g.c0 + threadIdx.x] + eps);
+    }
+    __syncthreads();
+    double sb[4] = {0.0, 0.0, 0.0, 0.0}, sg[4] = {0.0, 0.0, 0.0, 0.0};
+    if (g.active) {
+        double m[4], inv[4];
+        for (int e = 0; e < 4; ++e) { m[e] = sm[4 * g.c4 + e]; inv[e] = si[4 * g.c4 + e]; }
+        for (int r = g.r0 + g.rs; r < g.r1; r += g.rp) {
+            const int64_t at = (int64_t)r * C + g.c0 + 4 * g.c4;
+            const f32x4 v = ld4(z + at), gv = ld4(g_y + at);
+            const f32x4 yv = y ? ld4(y + at) : splat4(1.f);
+            for (int e = 0; e < 4; ++e) {
+                const double gh = yv[e] > 0.f ? (double)gv[e] : 0.0;
+                const double xh = ((double)v[e] - m[e]) * inv[e];
+                sb[e] = sb[e] + gh;
+                sg[e] = sg[e] + gh * xh;
+            }
+        }
+    }
+    bn_reduce(red, g, sb);
+    bn_reduce(red, g, sg);
+    if (g.active && g.rs == 0)
+        for (int e = 0; e < 4; ++e) {
+            const int c = g.c0 + 4 * g.c4 + e;
+            part[((int64_t)blockIdx.x * 2) * C + c] = sb[e];
+            part[((int64_t)blockIdx.x * 2 + 1) * C + c] = sg[e];
+        }
+}
+
+// the chunks in chunk order: sums [2][C] float64 (dbeta, dgamma) and their float32 roundings
+__global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const double* __restrict__ part, int M, int C,
+                                                            double* __restrict__ sums, float* __restrict__ dgamma,
+                                                            float* __restrict__ dbeta) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const int chunks = (M + BN_ROWS - 1) / BN_ROWS;
+    double sb = part[c], sg = part[C + c];
+    for (int k = 1; k < chunks; ++k) {
+        sb = sb + part[((int64_t)k * 2) * C + c];
+        sg = sg + part[((int64_t)k * 2 + 1) * C + c];
+    }
+    sums[c] = sb;
+    sums[C + c] = sg;
+    dbeta[c] = (float)sb;
+    dgamma[c] = (float)sg;
+}
+
+// g_z = (float)(a * ((gh - dbeta / M) - xh * (dgamma / M))),  a = (double)gamma * (1 / sqrt(var + eps)); g_z may be g_y
+__global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const float* __restrict__ z, const float* __restrict__ y,
+                                                                  const float* g_y, const float* __restrict__ gamma,
+                                                                  const double* __restrict__ mean, const double* __restrict__ var,
+                                                                  double eps, const double* __restrict__ sums, int M, int C,
+                                                                  float* g_z) {
+    __shared__ double sm[BN_SLAB], si[BN_SLAB], sa[BN_SLAB], scb[BN_SLAB], scg[BN_SLAB];
+    const BnGeom g = bn_geom(M, C);
+    if ((int)threadIdx.x < g.cw) {
+        const int c = g.c0 + threadIdx.x;
+        const double inv = 1.0 / sqrt(var[c] + eps);
+        sm[threadIdx.x] = mean[c];
+        si[threadIdx.x] = inv;
+        sa[threadIdx.x] = (double)gamma[c] * inv;
+        scb[threadIdx.x] = sums[c] / (double)M;
+        scg[threadIdx.x] = sums[C + c] / (double)M;
+    }
+    __syncthreads();
+    if (!g.active) return;
+    double m[4], inv[4], a[4], cb[4], cg[4];
+    for (int e = 0; e < 4; ++e) {
+        const int k = 4 * g.c4 + e;
+        m[e] = sm[k]; inv[e] = si[k]; a[e] = sa[k]; cb[e] = scb[k]; cg[e] = scg[k];
+    }
+    for (int r = g.r0 + g.rs; r < g.r1; r += g.rp) {
+        const int64_t at = (int64_t)r * C + g.c0 + 4 * g.c4;
+        const f32x4 v = ld4(z + at), gv = *reinterpret_cast<const f32x4*>(g_y + at);
+        const f32x4 yv = y ? ld4(y + at) : splat4(1.f);
+        f32x4 o;
+        for (int e = 0; e < 4; ++e) {
+            const double gh = yv[e] > 0.f ? (double)gv[e] : 0.0;
+            const double xh = ((double)v[e] - m[e]) * inv[e];
+            o[e] = (float)(a[e] * ((gh - cb[e]) - xh * cg[e]));
+        }
+        *reinterpret_cast<f32x4*>(g_z + at) = o;
+    }
+}
+
+struct BnRunArgs {
+    float* rm[EN_NCONV];
+    float* rv[EN_NCONV];
+    int first[EN_NCONV];          // the layer's first channel in the concatenated batch statistics
+    int C[EN_NCONV], M[EN_NCONV];
+};
+// running <- (1 - m) running + m batch in float64, rounded once; the variance unbiased (var M / (M - 1)).  blockIdx.y: layer
+__global__ __launch_bounds__(256) void bn_running_kernel(BnRunArgs a, const double* __restrict__ mean,
+                                                         const double* __restrict__ var, double momentum) {
+    const int i = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.C[i]) return;
+    const double M = (double)a.M[i], bm = mean[a.first[i] + c], bv = var[a.first[i] + c] * (M / (M - 1.0));
+    a.rm[i][c] = (float)((1.0 - momentum) * (double)a.rm[i][c] + momentum * bm);
+    a.rv[i][c] = (float)((1.0 - momentum) * (double)a.rv[i][c] + momentum * bv);
+}
+
+bool bn_shape_ok(int64_t M, int C) { return M >= 2 && M <= (1 << 24); }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+int64_t bn_chunks(int64_t M) { return (M + BN_ROWS - 1) / BN_ROWS; }
+int64_t bn_part_doubles(int64_t M, int C) { return 2 * bn_chunks(M) * C; }
+dim3 bn_grid(int64_t M, int C) { return dim3((unsigned)bn_chunks(M), (unsigned)((C + BN_SLAB - 1) / BN_SLAB)); }
+
+void launch_bn_stats(const float* z, int M, int C, double* mean, double* var, double* part, hipStream_t st) {
+    bn_stats_chunk_kernel<<<bn_grid(M, C), BN_THREADS, 0, st>>>(z, M, C, part);
+    bn_stats_finish_kernel<<<(C + 255) / 256, 256, 0, st>>>(part, M, C, mean, var);
+}
+void launch_bn_apply(const float* z, const float* gamma, const float* beta, const double* mean, const double* var, double eps,
+                     int M, int C, int relu, float* y, hipStream_t st) {
+    bn_apply_kernel<<<bn_grid(M, C), BN_THREADS, 0, st>>>(z, gamma, beta, mean, var, eps, M, C, relu, y);
+}
+// scratch: part [2 chunks C] then sums [2 C]
+void launch_bn_backward(const float* z, const float* y, const float* g_y, const float* gamma, const double* mean,
+                        const double* var, double eps, int M, int C, float* g_z, float* dgamma, float* dbeta, double* scratch,
+                        hipStream_t st) {
+    double* sums = scratch + bn_part_doubles(M, C);
+    bn_bwd_chunk_kernel<<<bn_grid(M, C), BN_THREADS, 0, st>>>(z, y, g_y, mean, var, eps, M, C, scratch);
+    bn_bwd_finish_kernel<<<(C + 255) / 256, 256, 0, st>>>(scratch, M, C, sums, dgamma, dbeta);
+    bn_bwd_apply_kernel<<<bn_grid(M, C), BN_THREADS, 0, st>>>(z, y, g_y, gamma, mean, var, eps, sums, M, C, g_z);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the unfolded weights in the convolution launchers' layouts, and the weight gradient back in the parameter's layout
+// ---------------------------------------------------------------------------------------------------------------
+// fold_pack_kernel without the fold: Wf [9 cinp][cout] and Wt [9 cout][cinp] of w [cout][cin][3][3], copied bit for bit
+__global__ __launch_bounds__(256) void train_pack_kernel(FoldTable tb) {
+    __shared__ float tile[EN_FT * EN_FLD];
+    int bx, by;
+    const FoldArgs a = tb.a[fold_locate(tb, bx, by)];
+    const int t = threadIdx.x, ci0 = bx * EN_FT, co0 = by * EN_FT;
+    for (int e = t; e < EN_FT * EN_FT * 9; e += 256) {
+        const int row = e / (EN_FT * 9), col = e - row * (EN_FT * 9);
+        const int co = co0 + row, ci = ci0 + col / 9;
+        float v = 0.f;
+        if (co < a.cout && ci < a.cin) v = a.w[((int64_t)co * a.cin + ci0) * 9 + col];
+        tile[row * EN_FLD + col] = v;
+    }
+    __syncthreads();
+    for (int e = t; e < EN_FT * EN_FT * 9; e += 256) {
+        const int lo = e & (EN_FT - 1), mid = (e >> 5) & (EN_FT - 1), tap = e >> 10;
+        if (co0 + lo < a.cout && ci0 + mid < a.cinp)
+            a.wf[((int64_t)tap * a.cinp + ci0 + mid) * a.cout + co0 + lo] = tile[lo * EN_FLD + mid * 9 + tap];
+        if (co0 + mid < a.cout && ci0 + lo < a.cinp)
+            a.wt[((int64_t)tap * a.cout + co0 + mid) * a.cinp + ci0 + lo] = tile[mid * EN_FLD + lo * 9 + (8 - tap)];
+    }
+}
+
+// dw [cout][cin][3][3] from the gradient in Wf's layout [9 cinp][cout]; blockIdx.x: cin tile, blockIdx.y: cout tile
+__global__ __launch_bounds__(256) void train_unpack_dw_kernel(const float* __restrict__ gwf, int cin, int cinp, int cout,
+                                                              float* __restrict__ dw) {
+    __shared__ float tile[EN_FT * EN_FLD];
+    const int t = threadIdx.x, ci0 = blockIdx.x * EN_FT, co0 = blockIdx.y * EN_FT;
+    for (int e = t; e < EN_FT * EN_FT * 9; e += 256) {
+        const int lo = e & (EN_FT - 1), mid = (e >> 5) & (EN_FT - 1), tap = e >> 10;
+        float v = 0.f;
+        if (co0 + lo < cout && ci0 + mid < cinp) v = gwf[((int64_t)tap * cinp + ci0 + mid) * cout + co0 + lo];
+        tile[lo * EN_FLD + mid * 9 + tap] = v;
+    }
+    __syncthreads();
+    for (int e = t; e < EN_FT * EN_FT * 9; e += 256) {
+        const int row = e / (EN_FT * 9), col = e - row * (EN_FT * 9);
+        const int co = co0 + row, ci = ci0 + col / 9;
+        if (co < cout && ci < cin) dw[((int64_t)co * cin + ci0) * 9 + col] = tile[row * EN_FLD + col];
+    }
+}
+
+// acc += add: the per-image weight-gradient partials, summed in image order
+__global__ __launch_bounds__(256) void train_add_kernel(float* __restrict__ acc, const float* __restrict__ add, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) acc[i] = acc[i] + add[i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the training workspace (float offsets; every region a multiple of 64 floats, so the float64 regions are 8-byte aligned)
+// ---------------------------------------------------------------------------------------------------------------
+int conv_level(int i) { return i < 10 ? i / 2 : 3 - ((i - 10) % 8) / 2; }
+
+struct TrainPlan {
+    int B, H[5], W[5];
+    int64_t P[5];
+    int64_t x8, z[EN_NCONV], y[EN_NCONV], pool[5], up[2][4], probs, df[5], t[3], part, wscr, wscr_floats, gw, gwtmp, heads, hgrad,
+        wf[EN_NCONV], wt[EN_NCONV], dummy, stat, bnscr, total;
+    int first[EN_NCONV];          // first channel of each BatchNorm in the concatenated statistics
+};
+bool train_size_ok(int B, int H, int W) {
+    return B >= 1 && B <= 8 && H >= 16 && W >= 16 && (int64_t)B * H * W <= (1 << 21);
+}
+TrainPlan make_train_plan(int B, int H, int W) {
+    TrainPlan tp;
+    tp.B = B;
+    for (int l = 0; l < 5; ++l) {
+        tp.H[l] = l ? tp.H[l - 1] / 2 : H;
+        tp.W[l] = l ? tp.W[l - 1] / 2 : W;
+        tp.P[l] = (int64_t)tp.H[l] * tp.W[l];
+    }
+    int64_t q = 0, part = 0, wscr = 0, gw = 0, bnscr = 0;
+    auto take = [&](int64_t n) { const int64_t at = q; q += (n + 63) / 64 * 64; return at; };
+    tp.x8 = take(B * tp.P[0] * 8);
+    int ch = 0;
+    for (int i = 0; i < EN_NCONV; ++i) {
+        const int l = conv_level(i), cin = EN_CONV[i].cin, cout = EN_CONV[i].cout;
+        tp.z[i] = take(B * tp.P[l] * cout);
+        tp.y[i] = take(B * tp.P[l] * cout);
+        tp.wf[i] = take((int64_t)9 * cin * cout);
+        tp.wt[i] = take((int64_t)9 * cin * cout);
+        tp.first[i] = ch;
+        ch += cout;
+        part = std::max(part, std::max(split_floats(tp.P[l], cin, cout), split_floats(tp.P[l], cout, cin)));
+        wscr = std::max(wscr, wgrad_floats(tp.P[l], cin, cout));
+        gw = std::max(gw, (int64_t)9 * cin * cout);
+        bnscr = std::max(bnscr, bn_part_doubles(B * tp.P[l], cout) + 2 * cout);
+    }
+    for (int l = 0; l < 5; ++l) {
+        tp.pool[l] = l ? take(B * tp.P[l] * EN_ENC_C[l - 1]) : -1;
+        tp.df[l] = take(B * tp.P[l] * EN_ENC_C[l]);
+    }
+    for (int hd = 0; hd < 2; ++hd)
+        for (int j = 0; j < 4; ++j) tp.up[hd][j] = take(B * 4 * tp.P[4 - j] * EN_DEC_CD[j]);
+    tp.probs = take(B * 2 * tp.P[0]);
+    for (int k = 0; k < 3; ++k) tp.t[k] = take(B * tp.P[0] * 64);
+    tp.part = take(part);
+    int per_block;
+    wscr = std::max(wscr, (int64_t)B * heads_wgrad_blocks(tp.P[0], per_block) * 260);
+    tp.wscr_floats = wscr;
+    tp.wscr = take(wscr);
+    tp.gw = take(gw);
+    tp.gwtmp = take(gw);
+    tp.heads = take(EN_HEADS_FLOATS);
+    tp.hgrad = take(EN_HEADS_FLOATS);
+    tp.dummy = take(2 * 1024);
+    tp.stat = take(2 * 2 * EN_BN_CHANNELS);         // float64 mean [5888] | var [5888]
+    tp.bnscr = take(2 * bnscr);                      // float64
+    tp.total = q;
+    return tp;
+}
+
+int train_fold_table(const void* const* params, float* ws, const TrainPlan& tp, FoldTable& tb) {
+    int blocks = 0;
+    for (int i = 0; i < EN_NCONV; ++i) {
+        FoldArgs& a = tb.a[i];
+        a = FoldArgs{};
+        a.w = (const float*)params[3 * i];
+        a.wf = ws + tp.wf[i]; a.wt = ws + tp.wt[i];
+        a.cinp = EN_CONV[i].cin; a.cin = i ? a.cinp : 6; a.cout = EN_CONV[i].cout;
+        tb.first[i] = blocks;
+        blocks += ((a.cinp + EN_FT - 1) / EN_FT) * ((a.cout + EN_FT - 1) / EN_FT);
+    }
+    tb.first[EN_NCONV] = blocks;
+    return blocks;
+}
+
+}  // namespace
+
+extern "C" {
+
+int enslam_eventnet_bn_stats(const float* z, int64_t M, int32_t C, double* mean, double* var, double* scratch,
+                             int64_t scratch_doubles, void* stream) {
+    if (!z || !mean || !var || !scratch || !aligned16(z)) return ENSLAM_EINVAL;
+    if (!chan_ok(C)) return ENSLAM_EUNSUPPORTED;
+    if (!bn_shape_ok(M, C) || scratch_doubles < bn_part_doubles(M, C)) return ENSLAM_EINVAL;
+    launch_bn_stats(z, (int)M, C, mean, var, scratch, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+int enslam_eventnet_bn_apply(const float* z, const float* gamma, const float* beta, const double* mean, const double* var,
+                             double eps, int64_t M, int32_t C, int32_t relu, float* y, void* stream) {
+    if (!z || !gamma || !beta || !mean || !var || !y || !aligned16(z) || !aligned16(y)) return ENSLAM_EINVAL;
+    if (!chan_ok(C)) return ENSLAM_EUNSUPPORTED;
+    if (!bn_shape_ok(M, C) || !(eps >= 0.0)) return ENSLAM_EINVAL;
+    launch_bn_apply(z, gamma, beta, mean, var, eps, (int)M, C, relu, y, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+int enslam_eventnet_bn_backward(const float* z, const float* y, const float* g_y, const float* gamma, const double* mean,
+                                const double* var, double eps, int64_t M, int32_t C, float* g_z, float* dgamma, float* dbeta,
+                                double* scratch, int64_t scratch_doubles, void* stream) {
+    if (!z || !g_y || !gamma || !mean || !var || !g_z || !dgamma || !dbeta || !scratch) return ENSLAM_EINVAL;
+    if (!aligned16(z) || !aligned16(g_y) || !aligned16(g_z) || (y && !aligned16(y))) return ENSLAM_EINVAL;
+    if (!chan_ok(C)) return ENSLAM_EUNSUPPORTED;
+    if (!bn_shape_ok(M, C) || !(eps >= 0.0) || scratch_doubles < bn_part_doubles(M, C) + 2 * C) return ENSLAM_EINVAL;
+    launch_bn_backward(z, y, g_y, gamma, mean, var, eps, (int)M, C, g_z, dgamma, dbeta, scratch, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+int enslam_eventnet_bn_running(void* const* buffers, const double* batch_mean, const double* batch_var, int32_t B, int32_t H,
+                               int32_t W, double momentum, void* stream) {
+    if (!buffers || !batch_mean || !batch_var || !train_size_ok(B, H, W)) return ENSLAM_EINVAL;
+    if ((int64_t)B * (H / 16) * (W / 16) < 2 || !(momentum >= 0.0 && momentum <= 1.0)) return ENSLAM_EINVAL;
+    const TrainPlan tp = make_train_plan(B, H, W);
+    BnRunArgs a;
+    for (int i = 0; i < EN_NCONV; ++i) {
+        if (!buffers[2 * i] || !buffers[2 * i + 1]) return ENSLAM_EINVAL;
+        a.rm[i] = (float*)buffers[2 * i];
+        a.rv[i] = (float*)buffers[2 * i + 1];
+        a.first[i] = tp.first[i];
+        a.C[i] = EN_CONV[i].cout;
+        a.M[i] = (int)(B * tp.P[conv_level(i)]);
+    }
+    bn_running_kernel<<<dim3(2, EN_NCONV), 256, 0, (hipStream_t)stream>>>(a, batch_mean, batch_var, momentum);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+size_t enslam_eventnet_bn_workspace_floats(int32_t B, int32_t H, int32_t W) {
+    if (!train_size_ok(B, H, W) || (int64_t)B * (H / 16) * (W / 16) < 2) return 0;
+    return (size_t)make_train_plan(B, H, W).total;
+}
+
+int64_t enslam_eventnet_bn_saved_offset(int32_t B, int32_t H, int32_t W, int32_t conv) {
+    if (!train_size_ok(B, H, W) || (int64_t)B * (H / 16) * (W / 16) < 2 || conv < 0 || conv >= EN_NCONV) return -1;
+    return make_train_plan(B, H, W).y[conv];
+}
+
+int enslam_eventnet_train_forward(const void* const* params, const float* x, int32_t B, int32_t H, int32_t W, double eps,
+                                  float* workspace, float* events, float* probs, double* batch_mean, double* batch_var,
+                                  void* stream) {
+    if (!params || !x || !workspace || !events || !probs || !batch_mean || !batch_var) return ENSLAM_EINVAL;
+    for (int k = 0; k < 3 * EN_NCONV + 4; ++k)
+        if (!params[k]) return ENSLAM_EINVAL;
+    if (!train_size_ok(B, H, W) || (int64_t)B * (H / 16) * (W / 16) < 2 || !(eps >= 0.0)) return ENSLAM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const TrainPlan tp = make_train_plan(B, H, W);
+    float* ws = workspace;
+    double* mean = reinterpret_cast<double*>(ws + tp.stat);
+    double* var = mean + EN_BN_CHANNELS;
+    double* bnscr = reinterpret_cast<double*>(ws + tp.bnscr);
+    {
+        FoldTable tb;
+        const int blocks = train_fold_table(params, ws, tp, tb);
+        train_pack_kernel<<<blocks, 256, 0, st>>>(tb);
+        const void* const* h = params + 3 * EN_NCONV;
+        heads_pack_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>((float*)h[0], (float*)h[1], (float*)h[2], (float*)h[3], ws + tp.heads, 0);
+    }
+    // convolution i of every image, then BatchNorm over the whole batch: z[i] -> y[i]
+    auto layer = [&](int i, const float* s0, int C0, const float* s1, int C1, int sH1, int sW1) {
+        const int l = conv_level(i), cout = EN_CONV[i].cout;
+        for (int b = 0; b < B; ++b) {
+            ConvArgs a = {};
+            a.w = ws + tp.wf[i];
+            a.s0 = s0 + b * tp.P[l] * C0;
+            a.s1 = s1 ? s1 + (int64_t)b * sH1 * sW1 * C1 : nullptr;
+            a.d0 = ws + tp.z[i] + b * tp.P[l] * cout; a.part = ws + tp.part;
+            a.H = tp.H[l]; a.W = tp.W[l]; a.C0 = C0; a.C1 = C1; a.sH1 = sH1; a.sW1 = sW1;
+            a.N = a.N0 = cout;
+            launch_conv(a, st);
+        }
+        const int M = (int)(B * tp.P[l]);
+        launch_bn_stats(ws + tp.z[i], M, cout, mean + tp.first[i], var + tp.first[i], bnscr, st);
+        launch_bn_apply(ws + tp.z[i], (const float*)params[3 * i + 1], (const float*)params[3 * i + 2], mean + tp.first[i],
+                        var + tp.first[i], eps, M, cout, 1, ws + tp.y[i], st);
+    };
+    for (int b = 0; b < B; ++b)
+        en_pack_x_kernel<<<blocks_of(tp.P[0] * 8), 256, 0, st>>>(x + b * 6 * tp.P[0], (int)tp.P[0], ws + tp.x8 + b * tp.P[0] * 8);
+    for (int l = 0; l < 5; ++l) {
+        const float* in = ws + tp.x8;
+        int cin = 8;
+        if (l) {
+            cin = EN_ENC_C[l - 1];
+            for (int b = 0; b < B; ++b)
+                pool2_fwd_kernel<<<blocks_of(tp.P[l] * cin), 256, 0, st>>>(ws + tp.y[2 * l - 1] + b * tp.P[l - 1] * cin, tp.H[l - 1],
+                                                                           tp.W[l - 1], cin, ws + tp.pool[l] + b * tp.P[l] * cin);
+            in = ws + tp.pool[l];
+        }
+        layer(2 * l, in, cin, nullptr, 0, 0, 0);
+        layer(2 * l + 1, ws + tp.y[2 * l], EN_ENC_C[l], nullptr, 0, 0, 0);
+    }
+    for (int hd = 0; hd < 2; ++hd) {
+        const float* deep = ws + tp.y[9];
+        for (int j = 0; j < 4; ++j) {
+            const int ls = 3 - j, ld = ls + 1, cd = EN_DEC_CD[j], i0 = 10 + 8 * hd + 2 * j;
+            for (int b = 0; b < B; ++b)
+                up2_fwd_kernel<<<blocks_of(4 * tp.P[ld] * cd), 256, 0, st>>>(deep + b * tp.P[ld] * cd, tp.H[ld], tp.W[ld], cd,
+                                                                             ws + tp.up[hd][j] + b * 4 * tp.P[ld] * cd);
+            layer(i0, ws + tp.y[2 * ls + 1], cd, ws + tp.up[hd][j], cd, 2 * tp.H[ld], 2 * tp.W[ld]);
+            layer(i0 + 1, ws + tp.y[i0], cd, nullptr, 0, 0, 0);
+            deep = ws + tp.y[i0 + 1];
+        }
+    }
+    for (int b = 0; b < B; ++b)
+        heads_fwd_kernel<<<blocks_of(2 * tp.P[0]), 256, 0, st>>>(ws + tp.heads, ws + tp.y[17] + b * tp.P[0] * 64,
+                                                                 ws + tp.y[25] + b * tp.P[0] * 64, (int)tp.P[0],
+                                                                 events + b * 2 * tp.P[0], probs + b * 2 * tp.P[0],
+                                                                 ws + tp.probs + b * 2 * tp.P[0]);
+    (void)hipMemcpyAsync(batch_mean, mean, sizeof(double) * EN_BN_CHANNELS, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(batch_var, var, sizeof(double) * EN_BN_CHANNELS, hipMemcpyDeviceToDevice, st);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+int enslam_eventnet_train_backward(const void* const* params, float* workspace, const float* g_events, const float* g_probs,
+                                   int32_t B, int32_t H, int32_t W, double eps, float* g_x, void* const* grads, void* stream) {
+    if (!params || !workspace || !g_events || !g_probs || !grads) return ENSLAM_EINVAL;
+    for (int k = 0; k < 3 * EN_NCONV + 4; ++k)
+        if (!params[k]) return ENSLAM_EINVAL;
+    const bool heads_hot = grads[3 * EN_NCONV] != nullptr;
+    for (int k = 1; k < 4; ++k)
+        if ((grads[3 * EN_NCONV + k] != nullptr) != heads_hot) return ENSLAM_EINVAL;
+    if (!train_size_ok(B, H, W) || (int64_t)B * (H / 16) * (W / 16) < 2 || !(eps >= 0.0)) return ENSLAM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const TrainPlan tp = make_train_plan(B, H, W);
+    float* ws = workspace;
+    const double* mean = reinterpret_cast<const double*>(ws + tp.stat);
+    const double* var = mean + EN_BN_CHANNELS;
+    double* bnscr = reinterpret_cast<double*>(ws + tp.bnscr);
+    float *tA = ws + tp.t[0], *tB = ws + tp.t[1], *tC = ws + tp.t[2];
+    // BatchNorm + ReLU of convolution i backwards, in place: g (gradient of y[i]) becomes the gradient of z[i]
+    auto bn_bwd = [&](int i, float* g) {
+        const int l = conv_level(i), cout = EN_CONV[i].cout;
+        float* dg = grads[3 * i + 1] ? (float*)grads[3 * i + 1] : ws + tp.dummy;
+        float* db = grads[3 * i + 2] ? (float*)grads[3 * i + 2] : ws + tp.dummy + 1024;
+        launch_bn_backward(ws + tp.z[i], ws + tp.y[i], g, (const float*)params[3 * i + 1], mean + tp.first[i], var + tp.first[i],
+                           eps, (int)(B * tp.P[l]), cout, g, dg, db, bnscr, st);
+    };
+    // d(w of convolution i): per image in Wf's layout, summed in image order, then moved to the parameter's layout
+    auto wgrad = [&](int i, const float* s0, int C0, const float* s1, int C1, int sH1, int sW1, const float* g) {
+        if (!grads[3 * i]) return;
+        const int l = conv_level(i), cin = EN_CONV[i].cin, cout = EN_CONV[i].cout;
+        const int64_t n = (int64_t)9 * cin * cout;
+        for (int b = 0; b < B; ++b) {
+            WgradArgs a = {};
+            a.s0 = s0 + b * tp.P[l] * C0;
+            a.s1 = s1 ? s1 + (int64_t)b * sH1 * sW1 * C1 : nullptr;
+            a.g = g + b * tp.P[l] * cout;
+            a.dw = ws + (b ? tp.gwtmp : tp.gw); a.part = ws + tp.wscr;
+            a.H = tp.H[l]; a.W = tp.W[l]; a.C0 = C0; a.C1 = C1; a.sH1 = sH1; a.sW1 = sW1; a.N = cout;
+            launch_wgrad(a, st);
+            if (b) train_add_kernel<<<blocks_of(n), 256, 0, st>>>(ws + tp.gw, ws + tp.gwtmp, n);
+        }
+        train_unpack_dw_kernel<<<dim3((cin + EN_FT - 1) / EN_FT, (cout + EN_FT - 1) / EN_FT), 256, 0, st>>>(
+            ws + tp.gw, i ? cin : 6, cin, cout, (float*)grads[3 * i]);
+    };
+    // d(input of convolution i) from g = the gradient of z[i]: N0 channels to d0, the rest to d1
+    auto convT = [&](int i, const float* g, float* d0, int N0, int acc0, float* d1, int dH1, int dW1) {
+        const int l = conv_level(i), cin = EN_CONV[i].cin, cout = EN_CONV[i].cout;
+        for (int b = 0; b < B; ++b) {
+            ConvArgs a = {};
+            a.w = ws + tp.wt[i];
+            a.s0 = g + b * tp.P[l] * cout; a.C0 = cout;
+            a.d0 = d0 + b * tp.P[l] * N0;
+            a.d1 = d1 ? d1 + (int64_t)b * dH1 * dW1 * (cin - N0) : nullptr;
+            a.part = ws + tp.part;
+            a.H = tp.H[l]; a.W = tp.W[l]; a.N = cin; a.N0 = N0; a.dH1 = dH1; a.dW1 = dW1; a.acc0 = acc0;
+            launch_conv(a, st);
+        }
+    };
+    if (heads_hot) {
+        int per_block;
+        const int blocks = heads_wgrad_blocks(tp.P[0], per_block);
+        for (int b = 0; b < B; ++b)
+            heads_wgrad_kernel<<<blocks, 256, 0, st>>>(g_events + b * 2 * tp.P[0], g_probs + b * 2 * tp.P[0],
+                                                       ws + tp.probs + b * 2 * tp.P[0], ws + tp.y[17] + b * tp.P[0] * 64,
+                                                       ws + tp.y[25] + b * tp.P[0] * 64, (int)tp.P[0], per_block,
+                                                       ws + tp.wscr + (int64_t)b * blocks * 260);
+        heads_wgrad_reduce_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>(ws + tp.wscr, B * blocks, ws + tp.hgrad);
+        void* const* h = grads + 3 * EN_NCONV;
+        heads_pack_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>((float*)h[0], (float*)h[1], (float*)h[2], (float*)h[3], ws + tp.hgrad, 1);
+    }
+    for (int hd = 0; hd < 2; ++hd) {
+        for (int b = 0; b < B; ++b)
+            heads_bwd_kernel<<<blocks_of(tp.P[0] * 64), 256, 0, st>>>(ws + tp.heads, hd, (hd ? g_probs : g_events) + b * 2 * tp.P[0],
+                                                                      ws + tp.probs + b * 2 * tp.P[0], (int)tp.P[0],
+                                                                      tA + b * tp.P[0] * 64);
+        for (int j = 3; j >= 0; --j) {
+            const int ls = 3 - j, ld = ls + 1, cd = EN_DEC_CD[j];
+            const int i1 = 11 + 8 * hd + 2 * j, i0 = i1 - 1;
+            bn_bwd(i1, tA);
+            wgrad(i1, ws + tp.y[i0], cd, nullptr, 0, 0, 0, tA);
+            convT(i1, tA, tB, cd, 0, nullptr, 0, 0);
+            bn_bwd(i0, tB);
+            wgrad(i0, ws + tp.y[2 * ls + 1], cd, ws + tp.up[hd][j], cd, 2 * tp.H[ld], 2 * tp.W[ld], tB);
+            convT(i0, tB, ws + tp.df[ls], cd, hd, tC, 2 * tp.H[ld], 2 * tp.W[ld]);
+            float* dst = j ? tA : ws + tp.df[4];
+            for (int b = 0; b < B; ++b)
+                up2_bwd_kernel<<<blocks_of(tp.P[ld] * cd), 256, 0, st>>>(tC + b * 4 * tp.P[ld] * cd, tp.H[ld], tp.W[ld], cd,
+                                                                         dst + b * tp.P[ld] * cd, j ? 0 : hd);
+        }
+    }
+    for (int l = 4; l >= 0; --l) {
+        const int c = EN_ENC_C[l], cin = EN_CONV[2 * l].cin;
+        bn_bwd(2 * l + 1, ws + tp.df[l]);
+        wgrad(2 * l + 1, ws + tp.y[2 * l], c, nullptr, 0, 0, 0, ws + tp.df[l]);
+        convT(2 * l + 1, ws + tp.df[l], tA, c, 0, nullptr, 0, 0);
+        bn_bwd(2 * l, tA);
+        wgrad(2 * l, l ? ws + tp.pool[l] : ws + tp.x8, cin, nullptr, 0, 0, 0, tA);
+        if (l || g_x) convT(2 * l, tA, tB, cin, 0, nullptr, 0, 0);
+        if (l)
+            for (int b = 0; b < B; ++b)
+                pool2_bwd_kernel<<<blocks_of(tp.P[l - 1] * cin), 256, 0, st>>>(ws + tp.y[2 * l - 1] + b * tp.P[l - 1] * cin,
+                                                                               tp.H[l - 1], tp.W[l - 1], cin, tB + b * tp.P[l] * cin,
+                                                                               ws + tp.df[l - 1] + b * tp.P[l - 1] * cin, 1);
+    }
+    if (g_x)
+        for (int b = 0; b < B; ++b)
+            en_unpack_gx_kernel<<<blocks_of(tp.P[0] * 6), 256, 0, st>>>(tB + b * tp.P[0] * 8, (int)tp.P[0], g_x + b * 6 * tp.P[0]);
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
 

@@ -226,9 +226,10 @@ EVENTNET_CONVS = ((8, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 25
 EVENTNET_HEADS_FLOATS = 264
 
 
-def check_event_net(net, frozen=True):
+def check_event_net(net, frozen=True, eval_only=True):
     """Raise NotImplementedError unless `net` is what the device route implements: UNet_2heads(6, 2, 2), bilinear, the
-    reference's widths, eval mode and (`frozen`, the route of compile_event_net) every parameter frozen."""
+    reference's widths, eval mode (`eval_only`; the training-mode route of compile_event_net_batchnorm takes either) and
+    (`frozen`, the route of compile_event_net) every parameter frozen."""
     if not isinstance(net, UNet_2heads):
         raise NotImplementedError(f"the HIP event network implements UNet_2heads only, not {type(net).__name__}")
     if not net.bilinear:
@@ -240,7 +241,7 @@ def check_event_net(net, frozen=True):
     got = tuple((c.in_channels, c.out_channels) for c in convs)
     if got != ((6, 64),) + EVENTNET_CONVS[1:]:
         raise NotImplementedError(f"the HIP event network implements the widths {UNet_2heads.WIDTHS} only")
-    if net.training:
+    if eval_only and net.training:
         raise NotImplementedError("the HIP event network runs eval mode only (BatchNorm folds into the convolutions): call "
                                   "net.eval() first")
     hot = [n for n, p in net.named_parameters() if p.requires_grad] if frozen else []
@@ -462,3 +463,104 @@ def compile_event_net_trainable(net):
     and output shapes as the net, `parameters()` / `state_dict()` are the net's own (under `net.`), so
     `torch.optim.Adam(tnet.parameters())` trains it.  Raises NotImplementedError for anything it does not implement."""
     return HipUNet2HeadsTrainable(net)
+
+
+# ------------------------------------------------------------------------------------------------
+# the training-mode route: batch statistics in the forward, their terms in the backward, running statistics updated with
+# momentum, mini-batches (csrc/event_net.hip: enslam_eventnet_train_forward / _backward and the three BatchNorm kernels)
+# ------------------------------------------------------------------------------------------------
+EVENTNET_MAX_BATCH = 8
+
+
+def check_event_net_batchnorm(net):
+    """Raise NotImplementedError unless `net` is what the training-mode device route implements: UNet_2heads(6, 2, 2),
+    bilinear, the reference's widths, every BatchNorm affine with tracked running statistics and one momentum and eps."""
+    check_event_net(net, frozen=False, eval_only=False)
+    bns = [p.double_conv[i] for p in _conv_pairs(net) for i in (1, 4)]
+    if any(not bn.affine for bn in bns):
+        raise NotImplementedError("the training-mode HIP event network implements affine=True BatchNorm only")
+    if any(not bn.track_running_stats or bn.running_mean is None for bn in bns):
+        raise NotImplementedError("the training-mode HIP event network implements track_running_stats=True only")
+    if any(bn.momentum is None for bn in bns):
+        raise NotImplementedError("the training-mode HIP event network implements a fixed momentum only (momentum=None, "
+                                  "the cumulative average, is not built)")
+    if len({(float(bn.momentum), float(bn.eps)) for bn in bns}) != 1:
+        raise NotImplementedError("the training-mode HIP event network implements one momentum and eps for all BatchNorms")
+
+
+class HipUNet2HeadsBatchNorm(nn.Module):
+    """`UNet_2heads.forward` on the device route with live BatchNorm.  In training mode `forward(x[B,6,H,W]) -> (events,
+    probs)` for 1 <= B <= 8 normalises with the batch statistics, is differentiable in x and in every parameter of
+    `self.net` that requires a gradient, and updates running_mean / running_var / num_batches_tracked in place as
+    nn.BatchNorm2d does (under torch.no_grad() too).  In eval mode it IS HipUNet2HeadsTrainable on the same net (batch 1),
+    which re-folds when the buffers change and so serves the fresh statistics.  `.train()` / `.eval()` reach the net."""
+
+    def __init__(self, net):
+        super().__init__()
+        check_event_net_batchnorm(net)
+        self.net = net
+        self.training = net.training
+        self._eval = {}               # the eval route, a dict so that the net is registered once
+        self._workspaces = {}
+
+    def _params(self):
+        pairs = [(p.double_conv[i], p.double_conv[i + 1]) for p in _conv_pairs(self.net) for i in (0, 3)]
+        params = [t for conv, bn in pairs for t in (conv.weight, bn.weight, bn.bias)]
+        params += [self.net.outc_1.conv.weight, self.net.outc_2.conv.weight, self.net.outc_1.conv.bias, self.net.outc_2.conv.bias]
+        return params, [bn for _, bn in pairs]
+
+    def workspace(self, B, H, W, device):
+        """The EventNetBnWorkspace of this input size (allocated on first use and kept)."""
+        from . import functional as EF
+        key = (int(B), int(H), int(W), torch.device(device))
+        ws = self._workspaces.get(key)
+        if ws is None:
+            ws = self._workspaces[key] = EF.EventNetBnWorkspace(key[0], key[1], key[2], key[3])
+        return ws
+
+    def forward(self, x):
+        from . import functional as EF
+        if not self.net.training:
+            if 'net' not in self._eval:
+                self._eval['net'] = HipUNet2HeadsTrainable(self.net)
+            return self._eval['net'](x)
+        check_event_net_batchnorm(self.net)
+        if not x.is_cuda:
+            raise NotImplementedError(f"the HIP event network needs its input on a HIP device (got {x.device}); use the torch "
+                                      "module on the CPU")
+        if x.dim() != 4 or x.shape[1] != 6 or x.shape[2] < 16 or x.shape[3] < 16:
+            raise NotImplementedError(f"the HIP event network takes [B,6,H,W] with H, W >= 16 (got {tuple(x.shape)})")
+        B, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+        if B < 1 or B > EVENTNET_MAX_BATCH:
+            raise NotImplementedError(f"the training-mode HIP event network runs batches of 1 to {EVENTNET_MAX_BATCH} (got "
+                                      f"an input of shape {tuple(x.shape)})")
+        if EF._capturing():
+            raise NotImplementedError("the training-mode HIP event network does not support graph capture of a training step; "
+                                      "capture the frozen route (compile_event_net) instead")
+        if B * (H // 16) * (W // 16) < 2:                     # the bottom level: torch's own refusal, in its words
+            raise ValueError("Expected more than 1 value per channel when training, got input size "
+                             f"torch.Size([{B}, 512, {H // 16}, {W // 16}])")
+        params, bns = self._params()
+        if any(conv_bias is not None for conv_bias in (p.double_conv[i].bias for p in _conv_pairs(self.net) for i in (0, 3))):
+            raise NotImplementedError("the training-mode HIP event network implements bias-free convolutions only")
+        if any(t.device != x.device or t.dtype is not torch.float32 or not t.is_contiguous() for t in params):
+            raise NotImplementedError("the training-mode HIP event network needs contiguous float32 parameters on the input's "
+                                      "device")
+        buffers = [t for bn in bns for t in (bn.running_mean, bn.running_var)]
+        if any(t.device != x.device or t.dtype is not torch.float32 or not t.is_contiguous() for t in buffers):
+            raise NotImplementedError("the training-mode HIP event network needs contiguous float32 running statistics on the "
+                                      "input's device")
+        ws = self.workspace(B, H, W, x.device)
+        out = EF.eventnet_bn_net_apply(x, params, ws, float(bns[0].eps), float(bns[0].momentum), buffers)
+        for t in buffers:                                     # the kernel wrote them: the eval route re-folds on a new version
+            torch.autograd.graph.increment_version(t)
+        with torch.no_grad():
+            torch._foreach_add_([bn.num_batches_tracked for bn in bns], 1)
+        return out
+
+
+def compile_event_net_batchnorm(net):
+    """The device route of a `UNet_2heads(6, 2, 2)` with training-mode BatchNorm and mini-batches: same call signature as
+    the net, `parameters()` / `buffers()` / `state_dict()` are the net's own (under `net.`), `.train()` / `.eval()` are
+    forwarded.  Raises NotImplementedError for anything it does not implement."""
+    return HipUNet2HeadsBatchNorm(net)

@@ -2530,8 +2530,11 @@ class EventNetWorkspace:
 # Calls made so far (tests read it):
 #   'wgrad'        backward passes that ran the convolutions' weight gradients;
 #   'heads_wgrad'  backward passes that built the heads block's gradient alone;
-#   'fold_pack'    packed images built on the device from live parameters.
-eventnet_launches = {'forward': 0, 'backward': 0, 'wgrad': 0, 'heads_wgrad': 0, 'fold_pack': 0}
+#   'fold_pack'    packed images built on the device from live parameters;
+#   'train_forward' / 'train_backward'  whole-net calls of the training-mode BatchNorm route, 'bn_running' its running-
+#                  statistics updates; 'bn_stats' / 'bn_apply' / 'bn_backward' the single-operation entries.
+eventnet_launches = {'forward': 0, 'backward': 0, 'wgrad': 0, 'heads_wgrad': 0, 'fold_pack': 0, 'train_forward': 0,
+                     'train_backward': 0, 'bn_running': 0, 'bn_stats': 0, 'bn_apply': 0, 'bn_backward': 0}
 
 
 def eventnet_forward(packed, x, ws):
@@ -2712,6 +2715,170 @@ def eventnet_fold_pack(params, consts):
     """params: [w, gamma, beta] x 26 + [W1, W2, b1, b2], float32 contiguous on the device; consts: [sq, shift] x 26, float64 on
     the device.  The packed image, differentiable in the parameters."""
     return _EventNetFoldPackFn.apply(len(consts), *consts, *params)
+
+
+# training-mode BatchNorm and batches (enslam_eventnet_bn_* / enslam_eventnet_train_*; event.compile_event_net_batchnorm)
+EVENTNET_BN_COUT = (64, 64, 128, 128, 256, 256, 512, 512, 512, 512) + (512, 256, 256, 128, 128, 64, 64, 64) * 2
+EVENTNET_BN_CHANNELS = sum(EVENTNET_BN_COUT)         # 5888: the length of the concatenated batch statistics
+EVENTNET_BN_ROWS = 256                               # rows per chunk of the BatchNorm kernels (BN_ROWS of csrc/event_net.hip)
+
+
+def eventnet_conv_level(i):
+    """The resolution level (0 = full size) of convolution i in packing order."""
+    return i // 2 if i < 10 else 3 - ((i - 10) % 8) // 2
+
+
+def _bn_scratch(M, C, device, backward=False):
+    chunks = (M + EVENTNET_BN_ROWS - 1) // EVENTNET_BN_ROWS
+    return torch.empty(2 * chunks * C + (2 * C if backward else 0), dtype=torch.float64, device=device)
+
+
+def eventnet_bn_stats(z):
+    """(mean, var) float64 [C] of z float32 [M, C]: the batch mean and the biased variance."""
+    _require_hip(z, "the BatchNorm input")
+    z = _f32c(z)
+    M, C = z.shape
+    mean = torch.empty(C, dtype=torch.float64, device=z.device)
+    var = torch.empty_like(mean)
+    scratch = _bn_scratch(M, C, z.device)
+    L.check(L.lib().enslam_eventnet_bn_stats(_ptr(z), M, C, _ptr(mean), _ptr(var), _ptr(scratch), scratch.numel(), _stream()),
+            "enslam_eventnet_bn_stats")
+    eventnet_launches['bn_stats'] += 1
+    return mean, var
+
+
+def eventnet_bn_apply(z, gamma, beta, mean, var, eps, relu=True):
+    """y float32 [M, C] = relu(gamma (z - mean) / sqrt(var + eps) + beta) with float64 mean / var [C]."""
+    _require_hip(z, "the BatchNorm input")
+    z = _f32c(z)
+    M, C = z.shape
+    y = torch.empty_like(z)
+    L.check(L.lib().enslam_eventnet_bn_apply(_ptr(z), _ptr(_f32c(gamma)), _ptr(_f32c(beta)), _ptr(mean), _ptr(var), float(eps), M,
+                                             C, int(bool(relu)), _ptr(y), _stream()), "enslam_eventnet_bn_apply")
+    eventnet_launches['bn_apply'] += 1
+    return y
+
+
+def eventnet_bn_backward(z, y, g_y, gamma, mean, var, eps):
+    """(g_z [M, C], dgamma [C], dbeta [C]) float32 of BatchNorm (+ ReLU where y, its output, is given; y None: no ReLU)."""
+    _require_hip(z, "the BatchNorm input")
+    z, g_y = _f32c(z), _f32c(g_y)
+    y = _f32c(y) if y is not None else None
+    M, C = z.shape
+    g_z = torch.empty_like(z)
+    dgamma = torch.empty(C, dtype=torch.float32, device=z.device)
+    dbeta = torch.empty_like(dgamma)
+    scratch = _bn_scratch(M, C, z.device, backward=True)
+    L.check(L.lib().enslam_eventnet_bn_backward(_ptr(z), _ptr(y), _ptr(g_y), _ptr(_f32c(gamma)), _ptr(mean), _ptr(var),
+                                                float(eps), M, C, _ptr(g_z), _ptr(dgamma), _ptr(dbeta), _ptr(scratch),
+                                                scratch.numel(), _stream()), "enslam_eventnet_bn_backward")
+    eventnet_launches['bn_backward'] += 1
+    return g_z, dgamma, dbeta
+
+
+def eventnet_bn_running(buffers, batch_mean, batch_var, B, H, W, momentum):
+    """In place on `buffers` ([running_mean, running_var] x 26, float32 on the device): torch's running-statistics rule with
+    the batch statistics float64 [5888] of a training-mode forward of a [B,6,H,W] input."""
+    L.check(L.lib().enslam_eventnet_bn_running(_ptr_array(buffers), _ptr(batch_mean), _ptr(batch_var), B, H, W, float(momentum),
+                                               _stream()), "enslam_eventnet_bn_running")
+    eventnet_launches['bn_running'] += 1
+
+
+class EventNetBnWorkspace:
+    """The device workspace of the training-mode route for one input size [B,6,H,W]: per convolution the raw output and the
+    BatchNorm + ReLU output, the packed weights, the batch statistics, gradient and reduction scratch.  `generation` counts
+    the forwards that have written it, so a backward can tell whether it still holds ITS forward."""
+
+    def __init__(self, B, H, W, device):
+        n = L.lib().enslam_eventnet_bn_workspace_floats(B, H, W)
+        if n == 0:
+            raise L.EnslamError(f"event network (training mode): unsupported input size {B} x {H} x {W}")
+        self.B, self.H, self.W = B, H, W
+        self.buf = torch.empty(n, dtype=torch.float32, device=device)
+        self.batch_mean = torch.empty(EVENTNET_BN_CHANNELS, dtype=torch.float64, device=device)
+        self.batch_var = torch.empty_like(self.batch_mean)
+        self.generation = 0
+
+    def saved(self, i):
+        """Read-only view [B, H_i, W_i, C_i] of convolution i's post-ReLU output from the last forward."""
+        if not 0 <= i < 26:
+            raise IndexError(f"the event network has 26 convolutions (got {i})")
+        at = L.lib().enslam_eventnet_bn_saved_offset(self.B, self.H, self.W, i)
+        lvl, C = eventnet_conv_level(i), EVENTNET_BN_COUT[i]
+        h, w = self.H >> lvl, self.W >> lvl
+        return self.buf[at:at + self.B * h * w * C].view(self.B, h, w, C).detach()
+
+
+def eventnet_train_forward(params, x, ws, eps):
+    """x float32 contiguous [B,6,H,W] -> (events, probs) [B,2,H,W] of the training-mode net; leaves the activations and the
+    batch statistics in `ws`.  params: [w, gamma, beta] x 26 + [W1, W2, b1, b2], float32 contiguous on the device."""
+    events = torch.empty((ws.B, 2, ws.H, ws.W), dtype=torch.float32, device=x.device)
+    probs = torch.empty_like(events)
+    L.check(L.lib().enslam_eventnet_train_forward(_ptr_array(params), _ptr(x), ws.B, ws.H, ws.W, float(eps), _ptr(ws.buf),
+                                                  _ptr(events), _ptr(probs), _ptr(ws.batch_mean), _ptr(ws.batch_var), _stream()),
+            "enslam_eventnet_train_forward")
+    ws.generation += 1
+    eventnet_launches['train_forward'] += 1
+    return events, probs
+
+
+def eventnet_train_backward(params, ws, g_events, g_probs, eps, needs, want_gx=True):
+    """(g_x or None, [gradient or None per parameter]): `needs` says which of the 82 parameters want one.  The gradients are
+    views of one allocation; a convolution weight that wants none costs no weight-gradient launch."""
+    dev = g_events.device
+    g_x = torch.empty((ws.B, 6, ws.H, ws.W), dtype=torch.float32, device=dev) if want_gx else None
+    needs = list(needs)
+    alloc = needs[:78] + [any(needs[78:])] * 4           # the heads' four come together
+    sizes = [p.numel() if a else 0 for p, a in zip(params, alloc)]
+    buf = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+    base, at, addr, grads = buf.data_ptr(), 0, [], []
+    for p, n, a in zip(params, sizes, alloc):
+        addr.append(base + 4 * at if a else None)
+        grads.append(buf[at:at + n].view(p.shape) if a else None)
+        at += n
+    L.check(L.lib().enslam_eventnet_train_backward(_ptr_array(params), _ptr(ws.buf), _ptr(g_events), _ptr(g_probs), ws.B, ws.H,
+                                                   ws.W, float(eps), _ptr(g_x), (ctypes.c_void_p * len(addr))(*addr), _stream()),
+            "enslam_eventnet_train_backward")
+    eventnet_launches['train_backward'] += 1
+    return g_x, [g if need else None for g, need in zip(grads, needs)]
+
+
+class _EventNetBnFn(torch.autograd.Function):
+    """The whole training-mode net: inputs x and the 82 parameters, differentiable in all of them.  With `buffers` (the 52
+    running statistics) the forward also applies torch's running-statistics rule to them, in place."""
+
+    @staticmethod
+    def forward(ctx, x, ws, eps, momentum, buffers, *params):
+        xc = _f32c(x)
+        pc = [p.detach() for p in params]
+        events, probs = eventnet_train_forward(pc, xc, ws, eps)
+        if buffers is not None:
+            eventnet_bn_running(buffers, ws.batch_mean, ws.batch_var, ws.B, ws.H, ws.W, momentum)
+        ctx.ws, ctx.eps, ctx.generation = ws, eps, ws.generation
+        ctx.save_for_backward(xc, *params)
+        return events, probs
+
+    @staticmethod
+    def backward(ctx, g_events, g_probs):
+        need_x, needs = ctx.needs_input_grad[0], ctx.needs_input_grad[5:]
+        if not (need_x or any(needs)):
+            return (None,) * (5 + len(needs))
+        if _capturing():
+            raise NotImplementedError("the training-mode HIP event network does not support graph capture of a training step")
+        xc, pc = ctx.saved_tensors[0], [p.detach() for p in ctx.saved_tensors[1:]]
+        ws = ctx.ws
+        if ws.generation != ctx.generation:              # another forward of this size ran in between: restore the activations
+            eventnet_train_forward(pc, xc, ws, ctx.eps)
+        g_x, grads = eventnet_train_backward(pc, ws, _f32c(g_events), _f32c(g_probs), ctx.eps, needs, want_gx=need_x)
+        return (g_x, None, None, None, None) + tuple(grads)
+
+
+def eventnet_bn_net_apply(x, params, ws, eps, momentum, buffers):
+    """(events, probs) [B,2,H,W] of x [B,6,H,W] through the training-mode net on the device: batch statistics in the forward,
+    their terms in the backward.  params: [w, gamma, beta] x 26 + [W1, W2, b1, b2], contiguous float32 on the device;
+    buffers: [running_mean, running_var] x 26 updated in place with `momentum`, or None to leave them alone."""
+    _require_hip(x, "the event network's input")
+    return _EventNetBnFn.apply(x, ws, eps, momentum, buffers, *params)
 
 
 # ------------------------------------------------------------------------------------------------

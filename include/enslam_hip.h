@@ -889,6 +889,59 @@ int enslam_eventnet_conv3x3_wgrad(int32_t H, int32_t W, int32_t C0, int32_t C1, 
                                   int32_t Cn, const float *a0, const float *a1, const float *g, const float *saved, float *dw,
                                   float *db, float *scratch, int64_t scratch_floats, void *stream);
 
+/* Training-mode BatchNorm and batches for the event network (csrc/event_net.hip): the unfolded UNet_2heads(6, 2, 2) with
+ * batch statistics in the forward, their terms in the backward and torch's running-statistics rule.  Activations are
+ * channels-last [M][C] float32 with M = B H W rows (image-major); C a multiple of 8, at most 1024 (else ENSLAM_EUNSUPPORTED);
+ * 2 <= M <= 2^24 (else ENSLAM_EINVAL: one row has no variance); activation pointers 16-byte aligned.  No atomics, no
+ * allocation, no synchronisation; M is split into chunks of 256 rows whatever the device, every sum is float64 in a fixed
+ * order (a thread's rows ascending, the 256 / min(C, 256) * 4 row sub-sets of a chunk ascending, the chunks ascending), so
+ * two runs are bit-equal.
+ *   bn_stats     mean [C], var [C] float64: per chunk of n_k rows  mean_k = (sum z) / n_k  and  M2_k = sum (z - mean_k)^2
+ *                (z widened to float64 first), merged in chunk order with Chan's formula  delta = mean_k - mean,
+ *                mean += delta n_k / n,  M2 += M2_k + delta^2 n_prev n_k / n;  var = M2 / M (biased).
+ *                scratch: float64 [2 ceil(M / 256) C].
+ *   bn_apply     per channel in float64  a = (double)gamma / sqrt(var + eps);  per element
+ *                y = (float)(a * ((double)z - mean) + (double)beta),  then max(y, 0) when relu != 0: float64 operations, one
+ *                rounding to float32.
+ *   bn_backward  per channel  inv = 1 / sqrt(var + eps);  per element  gh = g_y where y > 0, else 0 (y NULL: gh = g_y) and
+ *                xh = ((double)z - mean) * inv;  dbeta = sum gh,  dgamma = sum gh * xh  in float64, leaving as float32 [C];
+ *                g_z = (float)(((double)gamma * inv) * ((gh - dbeta / M) - xh * (dgamma / M)))  with the float64 sums.
+ *                g_z may be g_y itself.  scratch: float64 [2 ceil(M / 256) C + 2 C].
+ *   bn_running   all 26 BatchNorms in one launch: buffers holds, per convolution in packing order, the device addresses of
+ *                running_mean and running_var (float32 [cout], 52 addresses); batch_mean / batch_var float64 [5888] are the
+ *                train_forward outputs (the layers' channels concatenated in packing order).  In float64, rounded once:
+ *                running <- (1 - momentum) running + momentum batch, the variance unbiased (var M / (M - 1), M = B H_l W_l).
+ * train_forward / train_backward run the whole net in training mode for a batch 1 <= B <= 8 (B H W <= 2^21, H, W >= 16 and
+ * B (H / 16) (W / 16) >= 2, else ENSLAM_EINVAL: the bottom level would normalise one value per channel).
+ *   params     per convolution in packing order three device addresses: w float32 [cout][cin][3][3] (the first cin is 6),
+ *              gamma, beta float32 [cout]; then the heads' W1, W2, b1, b2 (82 addresses).  The weights are packed into the
+ *              convolution kernels' layouts on the device, once per forward, inside the workspace.
+ *   workspace  float32 [enslam_eventnet_bn_workspace_floats(B, H, W)] (0: unsupported): per convolution z and
+ *              y = relu(bn(z)) [B H_l W_l][cout], the packed weights, the batch statistics, gradient and reduction scratch.
+ *              The backward reads what the LAST forward on this workspace left, the packed weights included.
+ *              enslam_eventnet_bn_saved_offset is the float offset of convolution `conv`'s y in it (-1: bad argument).
+ *   forward    x [B,6,H,W] -> events, probs [B,2,H,W]; batch_mean, batch_var float64 [5888] for bn_running.
+ *   backward   g_events, g_probs [B,2,H,W] -> g_x [B,6,H,W] (may be NULL) and grads: per convolution dw, dgamma, dbeta, then
+ *              the heads' four (82 addresses, float32, shaped like the parameters, overwritten).  A NULL dw skips that
+ *              convolution's weight gradient, a NULL dgamma / dbeta drops the value; the heads' four are all NULL or all
+ *              given.  Per-image weight-gradient partials are summed in image order. */
+int enslam_eventnet_bn_stats(const float *z, int64_t M, int32_t C, double *mean, double *var, double *scratch,
+                             int64_t scratch_doubles, void *stream);
+int enslam_eventnet_bn_apply(const float *z, const float *gamma, const float *beta, const double *mean, const double *var,
+                             double eps, int64_t M, int32_t C, int32_t relu, float *y, void *stream);
+int enslam_eventnet_bn_backward(const float *z, const float *y, const float *g_y, const float *gamma, const double *mean,
+                                const double *var, double eps, int64_t M, int32_t C, float *g_z, float *dgamma, float *dbeta,
+                                double *scratch, int64_t scratch_doubles, void *stream);
+int enslam_eventnet_bn_running(void *const *buffers, const double *batch_mean, const double *batch_var, int32_t B, int32_t H,
+                               int32_t W, double momentum, void *stream);
+size_t enslam_eventnet_bn_workspace_floats(int32_t B, int32_t H, int32_t W);     /* 0: unsupported size */
+int64_t enslam_eventnet_bn_saved_offset(int32_t B, int32_t H, int32_t W, int32_t conv);
+int enslam_eventnet_train_forward(const void *const *params, const float *x, int32_t B, int32_t H, int32_t W, double eps,
+                                  float *workspace, float *events, float *probs, double *batch_mean, double *batch_var,
+                                  void *stream);
+int enslam_eventnet_train_backward(const void *const *params, float *workspace, const float *g_events, const float *g_probs,
+                                   int32_t B, int32_t H, int32_t W, double eps, float *g_x, void *const *grads, void *stream);
+
 /* Event-camera simulator (event_sim.py, csrc/event_sim.hip): a contrast-threshold sensor in the style of ESIM / vid2e.
  * All arithmetic is float64.
  *   luminance  Y = (0.299 R + 0.587 G) + 0.114 B of values in [0, 1] (a grey image is its own Y); L = log(Y + eps)

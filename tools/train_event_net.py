@@ -3,7 +3,7 @@ sequence carries: (previous colour, current colour) -> ground-truth event image 
 
     python tools/train_event_net.py CONFIG [--default-config PATH] [--input_folder DIR] [--event_folder DIR] --out PATH
                                            [--backend hip|torch] [--device cuda:0] [--epochs N] [--lr LR] [--scale-factor S]
-                                           [--calibrate N] [--max-frames N] [--seed K]
+                                           [--calibrate N] [--max-frames N] [--seed K] [--bn frozen|batch] [--batch-size N]
 
 For every frame with a predecessor the pair is the one the tracker forms (tracker.TrackerIteration.prepare_event_frame):
 both ground-truth colour images and the event image / mask resized with `resize_nearest` to the event resolution
@@ -14,7 +14,14 @@ tracker uses is an eval-mode one); --calibrate N sets them first from N pairs wi
 under no_grad (a cumulative average), which a freshly initialised network needs: its activations otherwise shrink by
 about 0.4 per layer.  --backend hip trains through event.compile_event_net_trainable (csrc/event_net.hip), torch through
 the PyTorch module.  Saves the net's state_dict (what `UNet_2heads.load_state_dict` and tools/run_slam.py --event-net
-take) and prints one JSON line: pairs, steps, the mean loss of the first and of the last epoch, seconds per step."""
+take) and prints one JSON line: pairs, steps, the mean loss of the first and of the last epoch, seconds per step.
+
+--bn batch trains with live BatchNorm instead: batch statistics in the forward, their terms in the backward, running
+statistics updated with momentum and saved with the state_dict (--calibrate keeps working and is simply unnecessary).
+--backend hip then trains through event.compile_event_net_batchnorm in training mode, torch through the plain module in
+.train().  --batch-size N (above 1 only with --bn batch, at most 8 on the hip backend) puts N pairs into a step: the loss is
+the mean of the pairs' event terms plus the cross entropy over the batch; an epoch's incomplete last batch is dropped
+(BatchNorm refuses a batch whose deepest level holds one value per channel)."""
 import argparse
 import json
 import os
@@ -60,6 +67,21 @@ def pair_loss(model, pair, ecfg):
     return le * ecfg.get('balancer', 1.0) + F.cross_entropy(probs, gt_mask)
 
 
+def batch_loss(model, batch, ecfg):
+    """pair_loss of a list of pairs run as one batch: the mean of the pairs' event terms plus the cross entropy over the
+    batch (one pair: pair_loss itself)."""
+    import torch
+    import torch.nn.functional as F
+    from evennicer_slam_amd.event import event_loss
+    if len(batch) == 1:
+        return pair_loss(model, batch[0], ecfg)
+    events, probs = model(torch.cat([x for x, _, _ in batch], dim=0))
+    full = (events * probs[:, 1][:, None]).permute(0, 2, 3, 1)
+    terms = [event_loss(gt, full[b], ecfg.get('blur', True), ecfg.get('kernel_sizes', (9,)), ecfg.get('unblurred_weight', 0.0),
+                        ecfg.get('kernel_weights', (1.0,)))[0] for b, (_, gt, _) in enumerate(batch)]
+    return torch.stack(terms).mean() * ecfg.get('balancer', 1.0) + F.cross_entropy(probs, torch.cat([m for _, _, m in batch], dim=0))
+
+
 def calibrate(net, pairs, n):
     """BatchNorm running statistics := the cumulative average over the first n pairs, run in batches (training mode, no
     gradients)."""
@@ -96,7 +118,11 @@ def main(argv=None):
     ap.add_argument('--calibrate', type=int, default=0)
     ap.add_argument('--max-frames', type=int, default=None)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--bn', choices=('frozen', 'batch'), default='frozen')
+    ap.add_argument('--batch-size', type=int, default=1)
     args = ap.parse_args(argv)
+    if args.batch_size < 1 or (args.batch_size > 1 and args.bn != 'batch'):
+        ap.error("--batch-size above 1 needs --bn batch (the frozen route runs one pair per step)")
 
     import torch
     from evennicer_slam_amd import datasets as D
@@ -115,7 +141,13 @@ def main(argv=None):
     net = EV.UNet_2heads(6, 2, 2).to(args.device).eval()
     if args.calibrate > 0:
         calibrate(net, pairs, args.calibrate)
-    model = EV.compile_event_net_trainable(net) if args.backend == 'hip' else net
+    if args.bn == 'batch':
+        if len(pairs) < args.batch_size:
+            raise SystemExit(f"--batch-size {args.batch_size} needs at least that many pairs (the sequence has {len(pairs)})")
+        model = EV.compile_event_net_batchnorm(net) if args.backend == 'hip' else net
+        model.train()
+    else:
+        model = EV.compile_event_net_trainable(net) if args.backend == 'hip' else net
     opt = torch.optim.Adam(net.parameters(), lr=args.lr)
     order = torch.Generator().manual_seed(args.seed)
     epoch_means, steps = [], 0
@@ -124,9 +156,10 @@ def main(argv=None):
     t0 = time.perf_counter()
     for _ in range(args.epochs):
         losses = []
-        for k in torch.randperm(len(pairs), generator=order).tolist():
+        perm = torch.randperm(len(pairs), generator=order).tolist()
+        for at in range(0, len(perm) - args.batch_size + 1, args.batch_size):
             opt.zero_grad(set_to_none=True)
-            loss = pair_loss(model, pairs[k], ecfg)
+            loss = batch_loss(model, [pairs[k] for k in perm[at:at + args.batch_size]], ecfg)
             loss.backward()
             opt.step()
             losses.append(loss.detach())
@@ -136,7 +169,7 @@ def main(argv=None):
     seconds = time.perf_counter() - t0
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     torch.save({k: v.detach().cpu() for k, v in net.state_dict().items()}, args.out)
-    out = dict(out=args.out, backend=args.backend, pairs=len(pairs), steps=steps, event_size=list(pairs[0][0].shape[2:]),
+    out = dict(out=args.out, backend=args.backend, bn=args.bn, batch_size=args.batch_size, pairs=len(pairs), steps=steps, event_size=list(pairs[0][0].shape[2:]),
                first_loss=epoch_means[0], last_loss=epoch_means[-1], seconds_per_step=seconds / max(steps, 1))
     print(json.dumps(out), flush=True)
     return out
