@@ -179,6 +179,9 @@ int ens_launch_render_fwd(int stage, int ntl, int64_t n_units, const float* ro, 
                           const double* pts, int64_t n_points, int apply_mask, const DevScene& sc, double* depth,
                           double* var, float* rgb, float* raw, float* act_ws, int act_light, hipStream_t st,
                           const LossSpec* ls = nullptr, const WorkList* wl = nullptr, const TrackerSpec* ts = nullptr);
+// forward-only colour-stage calls of this many 16-sample tiles and more take the weight-stationary kernel (5 tiles per wave
+// and more: below that the ring kernel's residency rounds win)
+constexpr int64_t FWD_RES_MIN_TILES = 16384;
 int ens_launch_composite_fwd(int n_rays, int S, const float* raw, const double* z, double* depth, double* var,
                              float* rgb, float* weights, hipStream_t st, const LossSpec* ls = nullptr,
                              const WorkList* wl = nullptr);

@@ -644,7 +644,7 @@ __global__ __launch_bounds__(256, 3) void render_fwd_ring_kernel(int64_t n_tiles
 // ------------------------------------------------------------------------------------------------
 constexpr int fwd_res_lds_bytes() { return (XyzLay{32}.fwd_floats() + XyzLay{64}.fwd_floats()) * 4; }
 constexpr int FWD_RES_WAVES = 12;
-constexpr int64_t FWD_RES_MIN_TILES = 16384;        // (5 tiles per wave and more: below that the ring kernel's residency rounds win)
+// (FWD_RES_MIN_TILES, the tile count from which this kernel is taken, lives in kernels.hpp: enslam_fwd_res_min_tiles reports it)
 
 ENS_DEV void res_load(float* dst_lds, const float* __restrict__ src, int n4, int wave, int lane) {      // all 12 waves, 1 KB per wave instruction
     for (int j = 0; j * (64 * FWD_RES_WAVES) < n4; ++j) {

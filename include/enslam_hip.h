@@ -318,6 +318,10 @@ int enslam_tracker_rays(int32_t n, const float *camera_tensor, const int64_t *pi
  * constant.  inside NULL: every ray.  tmp_scratch: float64 [n_rays].  *loss must be 0 on entry.
  *   Replaces Tracker.optimize_cam_in_batch lines 176-195 around Renderer.render_batch_ray. */
 int enslam_tracker_tail_max_rays(void);
+/* The number of 16-sample tiles from which a forward-only colour-stage call (enslam_eval_points, or enslam_render_fwd with
+ * raw_out and act_ws NULL) runs on the weight-stationary decoder kernel; below it the call runs on the ring kernel.  The
+ * two kernels give the same bits. */
+int64_t enslam_fwd_res_min_tiles(void);
 int enslam_render_tracker_loss_fwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float *rays_o, const float *rays_d,
                                    const double *z_vals, const enslam_scene *scene, double *depth, double *var, float *rgb,
                                    float *raw_out, float *act_ws, int32_t act_light, const float *gt_depth,
