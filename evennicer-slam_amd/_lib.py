@@ -236,6 +236,7 @@ _SIGS = {
                                            c_int32, c_void_p]),
     "enslam_tracker_tail_max_rays": (ctypes.c_int, []),
     "enslam_fwd_res_min_tiles": (c_int64, []),
+    "enslam_bwd_max_workgroups": (ctypes.c_int, []),
     "enslam_render_tracker_loss_fwd": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(Scene),
                                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                                       ctypes.c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

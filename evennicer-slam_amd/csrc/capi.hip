@@ -767,6 +767,7 @@ int enslam_render_tracker_loss_fwd(int32_t stage, int32_t n_rays, int32_t n_samp
 }
 int enslam_tracker_tail_max_rays(void) { return ENS_TRACKER_TAIL_MAX_RAYS; }
 int64_t enslam_fwd_res_min_tiles(void) { return FWD_RES_MIN_TILES; }
+int enslam_bwd_max_workgroups(void) { return ens_bwd_max_workgroups(); }
 
 int enslam_tracker_rays(int32_t n, const float* camera_tensor, const int64_t* pixel_index, int32_t H0, int32_t W0, int32_t window_w,
                         int32_t image_w, int32_t image_h, const float* depth_image, const void* color_image, int32_t color_is_f64, float fx, float fy,

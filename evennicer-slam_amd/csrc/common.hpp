@@ -87,6 +87,7 @@ struct FeatLay {                // MLP_no_xyz (coarse): decoder.py:206-274
 constexpr int ACT_DEP_TILES_MAX = 19;                       // 14 + ct + 1, ct <= 4
 constexpr int ACT_H4 = ACT_DEP_TILES_MAX * 256;             // float offset of h4 (2 tiles)
 constexpr int ACT_MASK = ACT_H4 + 2 * 256;                  // float offset of the mask words (128 words)
+constexpr unsigned ACT_INSIDE = 1u << 8;                    // mask word 1, bit 8: the sample lies strictly inside the bound (Renderer.py:44-47)
 constexpr int ACT_VOX = ACT_MASK + 128;                     // float offset of the 16 cell records (vox_record)
 constexpr int ACT_STRIDE = ACT_VOX + 64;                    // floats per (tile, decoder slot)
 // light workspace (no decoder-parameter gradients will be asked for): coordinates tile | mask words | cell records

@@ -38,6 +38,15 @@ ENS_DEV TileGeo tile_geo(int64_t tile, int ntl, int S, const float* ro, const fl
     return g;
 }
 
+// Renderer.py:44-58: the occupancy of a sample that is not strictly inside the bound is overwritten by 100, so no occupancy
+// gradient flows through it whatever d_raw holds there (its colour gradient does flow).  The forward's own comparison.
+ENS_DEV bool sample_inside(const double (&pw)[3], const DevScene& sc) {
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) in = in && (pw[a] < sc.hi[a]) && (pw[a] > sc.lo[a]);
+    return in;
+}
+
 // Coordinate gradient through the trilinear weights (ATen grid_sampler_3d_backward, gix/giy/giz) for the lane's
 // 8 channels; partial over channels -> caller reduces over the 4 q lanes.
 ENS_DEV void coord_grad_partial(const Vox& v, const DevGrid& g, int q, const f32x4& d0, const f32x4& d1, float& gx,

@@ -461,6 +461,7 @@ ENS_DEV void xyz_role(const BwdArgs& A, int kind, int wg, int n_wg, float* smem)
         const TileGeo G = tile_geo(tile, A.ntl, S, A.ro, A.rd, A.z, p);
         f32x4 draw = *reinterpret_cast<const f32x4*>(A.d_raw + G.sidx * 4) * draw_scale_of(A);
         if (!tvalid) draw = splat4(0.f);
+        if constexpr (NOUT == 1) { if (!sample_inside(G.pw, A.sc)) draw[3] = 0.f; }     // no occupancy gradient from a masked sample
         float dj[NE];                                               // d(loss)/d(output j) of this lane's sample
         if constexpr (NOUT == 4) { dj[0] = draw[0]; dj[1] = draw[1]; dj[2] = draw[2]; } else { dj[0] = draw[3]; }
         bool nz = false;
@@ -470,7 +471,8 @@ ENS_DEV void xyz_role(const BwdArgs& A, int kind, int wg, int n_wg, float* smem)
         // One barrier: each wave posts its flag in a word of the round's parity set.
         {
             const int par = (int)(round_no & 1);
-            if (lane == 0) ens_vote[par][wave] = __any(nz) ? 1 : 0;
+            const int live = __any(nz) ? 1 : 0;                      // over the whole wave: taken inside the branch it saw lane 0 alone
+            if (lane == 0) ens_vote[par][wave] = live;
             ++round_no;
             __syncthreads();
             const int any4 = ens_vote[par][0] | ens_vote[par][1] | ens_vote[par][2] | ens_vote[par][3];
@@ -853,6 +855,7 @@ ENS_DEV void xyz_role_saved(const BwdArgs& A, int kind, int wg, int n_wg, float*
             mw_n = *reinterpret_cast<const uint2*>(A.act_ws + ((int64_t)t1 * ACT_SLOTS + slot_idx) * WSS + WSM + lane * 2);
         }
         if (!tvalid) draw = splat4(0.f);
+        if constexpr (NOUT == 1) { if (!(mw.y & ACT_INSIDE)) draw[3] = 0.f; }           // no occupancy gradient from a masked sample
         float dj[NE];                                               // d(loss)/d(output j) of this lane's sample
         if constexpr (NOUT == 4) { dj[0] = draw[0]; dj[1] = draw[1]; dj[2] = draw[2]; } else { dj[0] = draw[3]; }
         bool nz = false;
@@ -865,7 +868,8 @@ ENS_DEV void xyz_role_saved(const BwdArgs& A, int kind, int wg, int n_wg, float*
         float* dgw = handoff ? A.dgrid_ws + ((int64_t)tile * ACT_SLOTS + slot_idx) * DG_STRIDE : nullptr;
         {   // skip the round when nothing flows into any of its 4 tiles (one barrier; waves stay in lockstep)
             const int par = (int)(round_no & 1);
-            if (lane == 0) ens_vote[par][wave] = __any(nz) ? 1 : 0;
+            const int live = __any(nz) ? 1 : 0;                      // over the whole wave: taken inside the branch it saw lane 0 alone
+            if (lane == 0) ens_vote[par][wave] = live;
             ++round_no;
             if constexpr (SPLIT) wg_barrier_lds(); else __syncthreads();
             const int any4 = ens_vote[par][0] | ens_vote[par][1] | ens_vote[par][2] | ens_vote[par][3];
@@ -1380,6 +1384,7 @@ ENS_DEV void feat_role(const BwdArgs& A, int wg, int n_wg, float* smem) {
         const TileGeo G = tile_geo(tile, A.ntl, S, A.ro, A.rd, A.z, p);
         f32x4 draw = *reinterpret_cast<const f32x4*>(A.d_raw + G.sidx * 4) * draw_scale_of(A);
         if (!tvalid) draw = splat4(0.f);
+        if (!sample_inside(G.pw, A.sc)) draw[3] = 0.f;                                  // no occupancy gradient from a masked sample
         f32x4 dout = splat4(0.f);
         if (q == 0) dout[0] = draw[3];
         const int active = __any(dout[0] != 0.f) ? 1 : 0;
@@ -1464,8 +1469,10 @@ ENS_DEV void feat_role(const BwdArgs& A, int wg, int n_wg, float* smem) {
             if (q != 0) { dpx = dpy = dpz = 0.f; }
             if (tvalid) add_ray_grad(dpx, dpy, dpz, G.zf, G.ray, A.g_ro, A.g_rd, lane);
         }
+        // all waves are done reading this round's P tiles.  Every wave of the workgroup takes this barrier, with a tile of its own
+        // or not: inside the tvalid branch the waves of a ragged last round fell out of step with the others
+        if (want_g && want_w) __syncthreads();
         if (want_g && tvalid) {
-            if (want_w) __syncthreads();                 // all waves are done reading this round's P tiles
             float* stg = my + SL::P0 * 256;
             *reinterpret_cast<f32x4*>(stg + p * 32 + 4 * q) = dc[0];
             *reinterpret_cast<f32x4*>(stg + p * 32 + 16 + 4 * q) = dc[1];

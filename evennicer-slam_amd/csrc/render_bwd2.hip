@@ -401,6 +401,7 @@ ENS_DEV void chain2_role(const BwdArgs& A, int kind, int wg, int n_wg, float* sm
         // The prefetched values are taken into their own registers HERE, in front of this tile's atomics (left to the compiler
         // the copies sink behind them, and the wait for the loads becomes a wait for float atomics issued a moment ago)
         asm volatile("" : "+v"(draw), "+v"(mw.x), "+v"(mw.y), "+v"(rec), "+v"(pc), "+v"(bq) :: "memory");
+        if constexpr (NOUT == 1) { if (!(mw.y & ACT_INSIDE)) draw[3] = 0.f; }           // no occupancy gradient from a masked sample
         S2(0)       // prefetched loads have arrived
         if (it + stride < c1) fetch(tile_cur);
         ScatterSt sst;
@@ -749,7 +750,8 @@ ENS_DEV void dw2_body(const BwdArgs& A, int kind, int wg, int n_wg, float* smem,
                 for (int r = 0; r < 4; ++r) lds_st1(dep[r] + o, r1[R][r]);
             } else if (wave == 4) {
                 // the output gradient as a register tile: sample p, "feature" 4q + r = output row (colour: r, g, b; else occupancy)
-                const f32x4 d = r1[R] * dscale;
+                f32x4 d = r1[R] * dscale;
+                if constexpr (NOUT == 1) { if (!(mwr[R].y & ACT_INSIDE)) d[3] = 0.f; }   // no occupancy gradient from a masked sample
                 f32x4 x = splat4(0.f);
                 if (q == 0) x = NOUT == 4 ? f32x4{d[0], d[1], d[2], 0.f} : f32x4{d[3], 0.f, 0.f, 0.f};
                 const unsigned o = sb + (unsigned)D::DO * 1024u;

@@ -82,7 +82,7 @@ ENS_DEV void xyz_layer(const float* __restrict__ pk, const f32x4 (&emb)[NTL][6],
 #pragma unroll
     for (int tl = 0; tl < NTL; ++tl) {
         const unsigned bits = fwd_pos_bits(acc[tl][0]) | (fwd_pos_bits(acc[tl][1]) << 4);
-        if constexpr (I < 4) mb[tl][0] |= bits << (8 * I); else mb[tl][1] = bits;
+        if constexpr (I < 4) mb[tl][0] |= bits << (8 * I); else mb[tl][1] |= bits;      // (word 1 arrives holding ACT_INSIDE)
     }
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
@@ -118,7 +118,8 @@ ENS_DEV void xyz_layer(const float* __restrict__ pk, const f32x4 (&emb)[NTL][6],
 // ws[tl]: activation-workspace block of (tile tl, this decoder) or nullptr (nothing saved)
 template <int CT, int NTL>
 ENS_DEV void mlp_xyz_fwd(const float* __restrict__ pk, const float (&pc)[NTL], const f32x4 (&c)[NTL][CT],
-                         f32x4 (&o)[NTL], float* const (&ws)[NTL], bool wl, float* stage, int lane, int p, int q) {
+                         f32x4 (&o)[NTL], float* const (&ws)[NTL], bool wl, float* stage, int lane, int p, int q,
+                         const unsigned (&inside)[NTL]) {
     constexpr XyzLay L{CT * 16};
     f32x4 emb[NTL][6];
 #pragma unroll
@@ -144,7 +145,7 @@ ENS_DEV void mlp_xyz_fwd(const float* __restrict__ pk, const float (&pc)[NTL], c
     f32x4 h[NTL][2];
     unsigned mb[NTL][2];
 #pragma unroll
-    for (int tl = 0; tl < NTL; ++tl) mb[tl][0] = mb[tl][1] = 0u;
+    for (int tl = 0; tl < NTL; ++tl) { mb[tl][0] = 0u; mb[tl][1] = inside[tl]; }
     xyz_layer<0, CT, NTL>(pk, emb, c, h, mb, ws, wl, stage, lane, p, q);
     xyz_layer<1, CT, NTL>(pk, emb, c, h, mb, ws, wl, stage, lane, p, q);
     xyz_layer<2, CT, NTL>(pk, emb, c, h, mb, ws, wl, stage, lane, p, q);
@@ -247,6 +248,16 @@ __global__ __launch_bounds__(64, NTL == 1 ? 3 : 1) void render_fwd_kernel(int64_
         pc[tl] = q == 0 ? (float)pw[tl][0] : (q == 1 ? (float)pw[tl][1] : (q == 2 ? (float)pw[tl][2] : 0.f));
     }
 
+    // ACT_INSIDE of the lane's sample p of every tile: it rides in the mask words, and the backward takes no occupancy gradient
+    // from a sample without it (Renderer.py:58 overwrites that occupancy)
+    unsigned inside[NTL];
+#pragma unroll
+    for (int tl = 0; tl < NTL; ++tl) {
+        bool in = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) in = in && (pw[tl][a] < sc.hi[a]) && (pw[tl][a] > sc.lo[a]);
+        inside[tl] = in ? ACT_INSIDE : 0u;
+    }
     f32x4 occ[NTL], col[NTL];
 #pragma unroll
     for (int tl = 0; tl < NTL; ++tl) { occ[tl] = splat4(0.f); col[tl] = splat4(0.f); }
@@ -278,7 +289,7 @@ __global__ __launch_bounds__(64, NTL == 1 ? 3 : 1) void render_fwd_kernel(int64_
             gather8(v, sc.grid[1], q, cm[tl][0], cm[tl][1]);
             if (ws0[tl] != nullptr && q == 0) *reinterpret_cast<f32x4*>(ws0[tl] + WSV + p * 4) = vox_record(v, sc.grid[1]);
         }
-        mlp_xyz_fwd<2, NTL>(sc.packed[1], pc, cm, occ, ws0, wl != 0, ws_stage, lane, p, q);
+        mlp_xyz_fwd<2, NTL>(sc.packed[1], pc, cm, occ, ws0, wl != 0, ws_stage, lane, p, q, inside);
         if constexpr (STAGE >= 2) {
             f32x4 cf[NTL][4];
 #pragma unroll
@@ -290,7 +301,7 @@ __global__ __launch_bounds__(64, NTL == 1 ? 3 : 1) void render_fwd_kernel(int64_
                 cf[tl][3] = cm[tl][1];
             }
             f32x4 of[NTL];
-            mlp_xyz_fwd<4, NTL>(sc.packed[2], pc, cf, of, ws1, wl != 0, ws_stage, lane, p, q);
+            mlp_xyz_fwd<4, NTL>(sc.packed[2], pc, cf, of, ws1, wl != 0, ws_stage, lane, p, q, inside);
 #pragma unroll
             for (int tl = 0; tl < NTL; ++tl) occ[tl][0] = of[tl][0] + occ[tl][0];   // fine_occ + middle_occ
         }
@@ -302,7 +313,7 @@ __global__ __launch_bounds__(64, NTL == 1 ? 3 : 1) void render_fwd_kernel(int64_
                 gather8(v, sc.grid[3], q, cc[tl][0], cc[tl][1]);
                 if (ws2[tl] != nullptr && q == 0) *reinterpret_cast<f32x4*>(ws2[tl] + WSV + p * 4) = vox_record(v, sc.grid[3]);
             }
-            mlp_xyz_fwd<2, NTL>(sc.packed[3], pc, cc, col, ws2, wl != 0, ws_stage, lane, p, q);
+            mlp_xyz_fwd<2, NTL>(sc.packed[3], pc, cc, col, ws2, wl != 0, ws_stage, lane, p, q, inside);
         }
     }
 
@@ -375,7 +386,7 @@ constexpr int fwd_ring_lds_bytes(int stage) { return (2 * fwd_ring_floats(stage)
 template <int CT, int C0, int RB, int NEXT_CD, int RES = -1>
 ENS_DEV void mlp_xyz_ring(const float* __restrict__ pk, const float* __restrict__ pk_next, float* ring, float pc,
                           const f32x4 (&c)[CT], f32x4& o, float* ws, bool wl, float* stage, unsigned wt, unsigned wq, int wave, int lane, int p, int q,
-                          StampCtx& sx) {
+                          StampCtx& sx, unsigned inside = 0u) {
     constexpr XyzLay L{CT * 16};
     constexpr int CD = CT * 16;
     f32x4 emb[6];
@@ -402,7 +413,7 @@ ENS_DEV void mlp_xyz_ring(const float* __restrict__ pk, const float* __restrict_
     FST(sx, 2)      // workspace stores of emb / c / coordinates
     f32x4 h[5][2];
     f32x4 wo_a0 = splat4(0.f), wo_a1 = splat4(0.f), wo_b = splat4(0.f);
-    unsigned mb0 = 0u, mb1 = 0u;
+    unsigned mb0 = 0u, mb1 = inside;                                // (ACT_INSIDE of the lane's sample rides in word 1)
     auto layer = [&](auto ic) {
         constexpr int i = decltype(ic)::value;
         constexpr int RO = RES >= 0 ? RES + 4 * L.oW(i)
@@ -432,7 +443,7 @@ ENS_DEV void mlp_xyz_ring(const float* __restrict__ pk, const float* __restrict_
         }
         if (ws != nullptr) {                 // ReLU masks for the backward (forward-only calls skip the 8 % of vector work)
             const unsigned bits = fwd_pos_bits(acc[0]) | (fwd_pos_bits(acc[1]) << 4);
-            if constexpr (i < 4) mb0 |= bits << (8 * i); else mb1 = bits;
+            if constexpr (i < 4) mb0 |= bits << (8 * i); else mb1 |= bits;
         }
         acc[0] = relu4(acc[0]) + lds4(wq + OBC);
         acc[1] = relu4(acc[1]) + lds4(wq + OBC + 64);
@@ -583,7 +594,7 @@ __global__ __launch_bounds__(256, 3) void render_fwd_ring_kernel(int64_t n_tiles
         __syncthreads();                                                                   // chunk 0 landed
         FST(sx, 5)
         mlp_xyz_ring<2, 0, RB, (STAGE >= 2 ? 64 : 0)>(sc.packed[1], STAGE >= 2 ? sc.packed[2] : nullptr, ring, pc, cm, occ, wsb,
-                                                       wl, stage, wt, wq, wave, lane, p, q, sx);
+                                                       wl, stage, wt, wq, wave, lane, p, q, sx, inb ? ACT_INSIDE : 0u);
         if constexpr (STAGE >= 2) {
             f32x4 cf[4];
             {
@@ -597,7 +608,7 @@ __global__ __launch_bounds__(256, 3) void render_fwd_ring_kernel(int64_t n_tiles
             f32x4 of;
             mlp_xyz_ring<4, 5, RB, ((STAGE == 3 && !SPLIT) ? 32 : 0)>(sc.packed[2], (STAGE == 3 && !SPLIT) ? sc.packed[3] : nullptr,
                                                                      ring, pc, cf, of, wsb ? wsb + WSS : nullptr, wl, stage, wt,
-                                                                     wq, wave, lane, p, q, sx);
+                                                                     wq, wave, lane, p, q, sx, inb ? ACT_INSIDE : 0u);
             occ[0] = of[0] + occ[0];                                                        // fine_occ + middle_occ
         }
     }
@@ -615,7 +626,7 @@ __global__ __launch_bounds__(256, 3) void render_fwd_ring_kernel(int64_t n_tiles
                 FST(sx, 5)
             }
             mlp_xyz_ring<2, 10, RB, 0>(sc.packed[3], nullptr, ring, pc, cc, col, wsb ? wsb + 2 * WSS : nullptr, wl, stage,
-                                       wt, wq, wave, lane, p, q, sx);
+                                       wt, wq, wave, lane, p, q, sx, inb ? ACT_INSIDE : 0u);
         }
     }
     if (q == 0 && tvalid && (points == nullptr || sidx < n_points)) {                   // rows 0..3 live on q == 0 lanes

@@ -322,6 +322,10 @@ int enslam_tracker_tail_max_rays(void);
  * raw_out and act_ws NULL) runs on the weight-stationary decoder kernel; below it the call runs on the ring kernel.  The
  * two kernels give the same bits. */
 int64_t enslam_fwd_res_min_tiles(void);
+/* The workgroup count of the persistent decoder backward (one per compute unit): the upper bound of the workgroups of one
+ * decoder role, i.e. of the rows of a partial buffer (enslam_bwd_partial_floats).  A batch of more than 4 * this many
+ * 16-sample tiles makes a role walk several rounds. */
+int enslam_bwd_max_workgroups(void);
 int enslam_render_tracker_loss_fwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float *rays_o, const float *rays_d,
                                    const double *z_vals, const enslam_scene *scene, double *depth, double *var, float *rgb,
                                    float *raw_out, float *act_ws, int32_t act_light, const float *gt_depth,
