@@ -241,6 +241,9 @@ _SIGS = {
                                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                                       ctypes.c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                       c_void_p]),
+    "enslam_tracker_tail": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           ctypes.c_float, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int32, c_void_p]),
     "enslam_plan_struct_bytes": (c_int64, [c_int32]),
     "enslam_plan_layout": (ctypes.c_int, [POINTER(StepPlan), POINTER(StepLayout)]),
     "enslam_plan_forward": (ctypes.c_int, [POINTER(StepPlan), POINTER(StepLayout), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -765,6 +765,24 @@ int enslam_render_tracker_loss_fwd(int32_t stage, int32_t n_rays, int32_t n_samp
                                          raw_out, act_ws, act_light != 0, (hipStream_t)stream, &ls, work_list ? &wl : nullptr, &ts);
     return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EUNSUPPORTED : ENSLAM_ELAUNCH);
 }
+int enslam_tracker_tail(int32_t n_rays, int32_t n_samples, const float* raw, const double* z_vals, double* depth, double* var,
+                        float* rgb, const float* gt_depth, const float* gt_color, float w_color, const uint8_t* inside,
+                        int32_t handle_dynamic, double* tmp_scratch, double* loss, float* d_raw_unit, int32_t* work_list,
+                        int32_t* work_count, int32_t loss_only, void* stream) {
+    if (n_rays < 0 || n_samples < 1 || n_samples > 64) return ENSLAM_EINVAL;
+    if (n_rays == 0) return ENSLAM_OK;
+    if (n_rays > ENS_TRACKER_TAIL_MAX_RAYS) return ENSLAM_EUNSUPPORTED;
+    if (!raw || !z_vals || !depth || !var || !rgb || !gt_depth || !loss || !tmp_scratch) return ENSLAM_EINVAL;
+    if (loss_only != 0 && handle_dynamic == 0) return ENSLAM_EINVAL;
+    const LossSpec ls{gt_depth, gt_color, w_color, loss, nullptr, d_raw_unit};
+    const TrackerSpec ts{inside, handle_dynamic != 0 ? 1 : 0, tmp_scratch};
+    WorkList wl;
+    if (!work_list_of(work_list, work_count, wl) || (work_list && !d_raw_unit)) return ENSLAM_EINVAL;
+    if (work_list && n_samples % 16 != 0) return ENSLAM_EINVAL;      // the list holds whole 16-sample tiles only
+    const int rc = ens_launch_tracker_tail(n_rays, n_samples, raw, z_vals, depth, var, rgb, ls, ts, work_list ? &wl : nullptr,
+                                           (hipStream_t)stream, loss_only != 0);
+    return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EINVAL : ENSLAM_ELAUNCH);
+}
 int enslam_tracker_tail_max_rays(void) { return ENS_TRACKER_TAIL_MAX_RAYS; }
 int64_t enslam_fwd_res_min_tiles(void) { return FWD_RES_MIN_TILES; }
 int enslam_bwd_max_workgroups(void) { return ens_bwd_max_workgroups(); }

@@ -187,7 +187,8 @@ int ens_launch_composite_fwd(int n_rays, int S, const float* raw, const double* 
                              const WorkList* wl = nullptr);
 constexpr int ENS_TRACKER_TAIL_MAX_RAYS = 4096;       // one workgroup sorts the batch in LDS for the median
 int ens_launch_tracker_tail(int n_rays, int S, const float* raw, const double* z, double* depth, double* var, float* rgb,
-                            const LossSpec& ls, const TrackerSpec& ts, const WorkList* wl, hipStream_t st);
+                            const LossSpec& ls, const TrackerSpec& ts, const WorkList* wl, hipStream_t st,
+                            bool loss_only = false);   // loss_only (handle_dynamic only): depth, var, rgb, tmp as the caller left them
 int ens_launch_tracker_rays(int n, const float* ct, const int64_t* idx, int H0, int W0, int ww, int Wimg, int Himg, const float* depth,
                             const void* color, int color_f64, float fx, float fy, float cx, float cy, const double* bound,
                             float* oi, float* oj, float* ro, float* rd, float* gd, float* gc, uint8_t* inside, float* dmax,

@@ -1081,15 +1081,16 @@ int ens_launch_composite_fwd(int n_rays, int S, const float* raw, const double* 
 }
 
 int ens_launch_tracker_tail(int n_rays, int S, const float* raw, const double* z, double* depth, double* var, float* rgb,
-                            const LossSpec& ls, const TrackerSpec& ts, const WorkList* wl, hipStream_t st) {
+                            const LossSpec& ls, const TrackerSpec& ts, const WorkList* wl, hipStream_t st, bool loss_only) {
     if (n_rays <= 0) return 0;
     if (n_rays > ENS_TRACKER_TAIL_MAX_RAYS || S < 1 || S > 64 || !ls.gd || !ls.loss || !ts.tmp) return -1;
+    if (loss_only && !ts.dynamic) return -1;
     WorkList wk{nullptr, nullptr};
     if (wl != nullptr && ls.d_raw_unit != nullptr) wk = *wl;
     if (wk.tiles != nullptr && S % 16 != 0) return -1;
     const dim3 grid((n_rays + 15) / 16), block(1024);
     if (ts.dynamic) {
-        tracker_composite_kernel<<<grid, block, 0, st>>>(n_rays, S, raw, z, depth, var, rgb, ls.gd, ts);
+        if (!loss_only) tracker_composite_kernel<<<grid, block, 0, st>>>(n_rays, S, raw, z, depth, var, rgb, ls.gd, ts);
         tracker_loss_kernel<false><<<grid, block, 0, st>>>(n_rays, S, raw, z, depth, var, rgb, ls, ts, wk);
     } else {
         tracker_loss_kernel<true><<<grid, block, 0, st>>>(n_rays, S, raw, z, depth, var, rgb, ls, ts, wk);

@@ -333,6 +333,20 @@ int enslam_render_tracker_loss_fwd(int32_t stage, int32_t n_rays, int32_t n_samp
                                    double *tmp_scratch, double *loss, float *d_raw_unit, int32_t *work_list,
                                    int32_t *work_count, void *stream);
 
+/* The tail of enslam_render_tracker_loss_fwd on its own, on a raw [n_rays, n_samples, 4] of the caller's (1 <= n_samples <= 64;
+ * a work list needs n_samples % 16 == 0, else ENSLAM_EINVAL; more than enslam_tracker_tail_max_rays() rays:
+ * ENSLAM_EUNSUPPORTED): the same launches with the same arguments, outputs and *loss == 0 on entry as there.
+ * loss_only != 0 (valid with handle_dynamic != 0 only, else ENSLAM_EINVAL): the compositing launch is skipped and the second
+ * launch (median, mask, loss, unit gradients, work list) runs on the depth, var, rgb and tmp_scratch the caller filled.
+ * A NaN in tmp is outside the contract: its ray is not kept (tmp < 10 * median is false), up to 1024 rays it counts among the
+ * inside rays but ranks above every finite value like +inf (torch.median would return NaN; with one or two inside rays the
+ * NaN itself can become the median, and then nothing is kept), and above 1024 rays the sorting network's order, hence the
+ * median, is unspecified. */
+int enslam_tracker_tail(int32_t n_rays, int32_t n_samples, const float *raw, const double *z_vals, double *depth, double *var,
+                        float *rgb, const float *gt_depth, const float *gt_color, float w_color, const uint8_t *inside,
+                        int32_t handle_dynamic, double *tmp_scratch, double *loss, float *d_raw_unit, int32_t *work_list,
+                        int32_t *work_count, int32_t loss_only, void *stream);
+
 /* Sample distances along rays (mark_scene / mark_flags non-NULL: also does enslam_mark_blocks' work for stage mark_stage
  * on the samples it has just placed -- one launch less per render call).
  *   Replaces Renderer.render_batch_ray lines 83-171
