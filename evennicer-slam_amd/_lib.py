@@ -307,6 +307,18 @@ _SIGS = {
                                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "enslam_event_sim_boxroom": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_void_p]),
+    "enslam_event_stream_images_count": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_event_stream_images_emit": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double,
+                                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_event_stream_boxroom_count": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                         c_void_p]),
+    "enslam_event_stream_boxroom_emit": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                        c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                                        c_void_p, c_void_p]),
+    "enslam_event_accumulate": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_double), c_void_p,
+                                               c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "enslam_vis_panels_workspace": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "enslam_vis_panels": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                          c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -19,164 +19,14 @@
 // Precision: float64 throughout, every operation in the order the model states (-ffp-contract=off: no fused multiply-adds).
 // What is not pinned bit for bit is the device's sin and log (an ulp or two of the host's); the grey table and the host-level
 // option keep them out of the images route where a test wants bit equality.
-// The per-pixel helpers are host-callable too, so that a CPU build can step through one pixel.
+// The per-pixel helpers live in event_sim_core.hpp, shared with event_stream.hip (the same sensor with time-stamped events);
+// they are host-callable too, so that a CPU build can step through one pixel.
 #include "../../include/enslam_hip.h"
 #include "common.hpp"
 
+#include "event_sim_core.hpp"
+
 namespace {
-
-constexpr int ES_BLOCK = 256;
-constexpr int ES_MAX_SUBSTEPS = 64;
-constexpr int64_t ES_MAX_PIXELS = (int64_t)1 << 28;
-
-#define ES_HD __host__ __device__ __forceinline__
-
-struct EsSensor {                   // one pixel's state across the sub-steps of an interval
-    double ref, pos, neg;
-};
-
-// the per-pixel update of the model at one sub-step
-ES_HD void es_update(EsSensor& S, double L, double cp, double cn) {
-    const double d = L - S.ref;
-    if (d >= cp) {
-        const double n = floor(d / cp);
-        S.pos += n;
-        S.ref += n * cp;
-    } else if (-d >= cn) {
-        const double n = floor(-d / cn);
-        S.neg += n;
-        S.ref -= n * cn;
-    }
-}
-
-ES_HD uint8_t es_sat(double n) { return n >= 255.0 ? (uint8_t)255 : (uint8_t)n; }
-
-ES_HD double es_luminance(double r, double g, double b) { return (0.299 * r + 0.587 * g) + 0.114 * b; }
-
-struct EsCommon {
-    int32_t H, W, K, init;
-    double eps, c_pos, c_neg;
-    const double* c_pos_map;
-    const double* c_neg_map;
-    double* L_ref;
-    uint8_t* events;
-};
-
-struct EsImageArgs {
-    EsCommon c;
-    int32_t channels;
-    const uint8_t* prev;
-    const uint8_t* cur;
-    const double* lut;
-    const double* L_prev;
-    const double* L_cur;
-};
-
-struct EsRoomArgs {
-    EsCommon c;
-    double fx, fy, cx, cy;
-    double room_lo[3], room_hi[3], box_lo[3], box_hi[3];
-    double freq[9], phase[3];
-    int32_t has_box;
-    const double* poses;            // [K,12]
-    double* color_out;              // [H,W,3] or NULL
-    float* depth_out;               // [H,W] or NULL
-};
-
-ES_HD double es_image_level(const EsImageArgs& A, const uint8_t* img, int64_t o) {
-    if (A.channels == 1) return A.lut[img[o]];
-    const uint8_t* s = img + 3 * o;
-    return log(es_luminance((double)s[0] / 255.0, (double)s[1] / 255.0, (double)s[2] / 255.0) + A.c.eps);
-}
-
-// sensor state in, sensor state and counts out: shared tail of both kernels
-ES_HD void es_load(const EsCommon& C, int64_t o, EsSensor& S, double& cp, double& cn) {
-    S.ref = C.init ? 0.0 : C.L_ref[o];
-    S.pos = 0.0;
-    S.neg = 0.0;
-    cp = C.c_pos_map ? C.c_pos_map[o] : C.c_pos;
-    cn = C.c_neg_map ? C.c_neg_map[o] : C.c_neg;
-}
-
-ES_HD void es_store(const EsCommon& C, int64_t o, const EsSensor& S, double L_last) {
-    C.L_ref[o] = C.init ? L_last : S.ref;
-    if (C.events) {
-        const unsigned neg = C.init ? 0u : es_sat(S.neg), pos = C.init ? 0u : es_sat(S.pos);
-        reinterpret_cast<uint16_t*>(C.events)[o] = (uint16_t)(neg | (pos << 8));       // (-, +) as one 2-byte store
-    }
-}
-
-ES_HD void es_image_pixel(const EsImageArgs& A, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    const double La = A.L_prev ? A.L_prev[o] : es_image_level(A, A.prev, o);
-    const double Lb = A.L_cur ? A.L_cur[o] : es_image_level(A, A.cur, o);
-    EsSensor S;
-    double cp, cn, L = Lb;
-    es_load(A.c, o, S, cp, cn);
-    const double dL = Lb - La;
-    for (int s = 1; s <= A.c.K; ++s) {
-        L = La + ((double)s / (double)A.c.K) * dL;
-        if (!A.c.init) es_update(S, L, cp, cn);
-    }
-    es_store(A.c, o, S, L);
-}
-
-// BoxRoom.render of one pixel under the pose P (the 12 values of c2w[:3,:4], row-major): colour and the ray parameter
-ES_HD void es_room_pixel(const EsRoomArgs& A, const double* __restrict__ P, int y, int x, double (&col)[3], double& t) {
-    const double dir[3] = {((double)x - A.cx) / A.fx, -((double)y - A.cy) / A.fy, -1.0};
-    double o[3], d[3], dc[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        d[a] = (dir[0] * P[4 * a] + dir[1] * P[4 * a + 1]) + dir[2] * P[4 * a + 2];
-        o[a] = P[4 * a + 3];
-        dc[a] = fabs(d[a]) < 1e-12 ? 1e-12 : d[a];              // BoxRoom.intersect's clamp (the hit point uses d itself)
-    }
-    double t_wall = 0.0, t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double u = (A.room_lo[a] - o[a]) / dc[a], v = (A.room_hi[a] - o[a]) / dc[a];
-        const double far = u > v ? u : v;
-        t_wall = a == 0 ? far : (far < t_wall ? far : t_wall);
-    }
-    t = t_wall;
-    if (A.has_box) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double u = (A.box_lo[a] - o[a]) / dc[a], v = (A.box_hi[a] - o[a]) / dc[a];
-            const double lo = u < v ? u : v, hi = u > v ? u : v;
-            t1 = a == 0 ? lo : (lo > t1 ? lo : t1);
-            t2 = a == 0 ? hi : (hi < t2 ? hi : t2);
-        }
-        if (t1 < t2 && t1 > 0.0 && t1 < t_wall) t = t1;
-    }
-    double p[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) p[a] = o[a] + d[a] * t;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double arg = ((p[0] * A.freq[3 * c] + p[1] * A.freq[3 * c + 1]) + p[2] * A.freq[3 * c + 2]) + A.phase[c];
-        col[c] = 0.5 + 0.45 * sin(arg);
-    }
-}
-
-ES_HD void es_room_pixel_interval(const EsRoomArgs& A, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    EsSensor S;
-    double cp, cn, L = 0.0, col[3] = {0.0, 0.0, 0.0}, t = 0.0;
-    es_load(A.c, o, S, cp, cn);
-#pragma clang loop unroll(disable)
-    for (int s = 0; s < A.c.K; ++s) {
-        es_room_pixel(A, A.poses + 12 * s, y, x, col, t);
-        L = log(es_luminance(col[0], col[1], col[2]) + A.c.eps);
-        if (!A.c.init) es_update(S, L, cp, cn);
-    }
-    es_store(A.c, o, S, L);
-    if (A.color_out) {
-        double* co = A.color_out + 3 * o;
-        co[0] = col[0]; co[1] = col[1]; co[2] = col[2];
-        A.depth_out[o] = (float)t;
-    }
-}
 
 __global__ __launch_bounds__(ES_BLOCK) void event_sim_images_kernel(EsImageArgs A) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -190,29 +40,6 @@ __global__ __launch_bounds__(ES_BLOCK) void event_sim_boxroom_kernel(EsRoomArgs 
     es_room_pixel_interval(A, y, x);
 }
 
-bool es_pos_finite(double x) { return x > 0.0 && x - x == 0.0; }
-bool es_finite(double x) { return x == x && x - x == 0.0; }
-
-// Checks what both routes share and fills C.  No device work.
-int es_common(const enslam_event_sim_plan* plan, const double* c_pos_map, const double* c_neg_map, double* L_ref,
-              uint8_t* events, EsCommon& C) {
-    if (!plan || !L_ref) return ENSLAM_EINVAL;
-    const enslam_event_sim_plan& P = *plan;
-    if (!events && !P.init) return ENSLAM_EINVAL;
-    if ((uintptr_t)events & 1) return ENSLAM_EINVAL;           // a pixel's two counts are stored as one 16-bit word
-    if (P.H <= 0 || P.W <= 0 || P.K <= 0) return ENSLAM_EINVAL;
-    if (!es_pos_finite(P.eps)) return ENSLAM_EINVAL;
-    if (!P.init && ((!c_pos_map && !es_pos_finite(P.c_pos)) || (!c_neg_map && !es_pos_finite(P.c_neg)))) return ENSLAM_EINVAL;
-    if (P.K > ES_MAX_SUBSTEPS || (int64_t)P.H * P.W > ES_MAX_PIXELS) return ENSLAM_EUNSUPPORTED;
-    C.H = P.H; C.W = P.W; C.K = P.K; C.init = P.init != 0;
-    C.eps = P.eps; C.c_pos = P.c_pos; C.c_neg = P.c_neg;
-    C.c_pos_map = c_pos_map; C.c_neg_map = c_neg_map;
-    C.L_ref = L_ref; C.events = events;
-    return ENSLAM_OK;
-}
-
-dim3 es_grid(const EsCommon& C) { return dim3((unsigned)((C.W + 63) / 64), (unsigned)((C.H + 3) / 4)); }
-
 }  // namespace
 
 extern "C" {
@@ -225,16 +52,8 @@ int enslam_event_sim_images(const enslam_event_sim_plan* plan, const uint8_t* pr
                             const double* L_prev, const double* L_cur, const double* c_pos_map, const double* c_neg_map,
                             double* L_ref, uint8_t* events, void* stream) {
     EsImageArgs A;
-    const int rc = es_common(plan, c_pos_map, c_neg_map, L_ref, events, A.c);
+    const int rc = es_image_args(plan, prev, cur, lut, L_prev, L_cur, c_pos_map, c_neg_map, L_ref, events, A);
     if (rc != ENSLAM_OK) return rc;
-    if ((L_prev == nullptr) != (L_cur == nullptr)) return ENSLAM_EINVAL;
-    if (!L_prev) {
-        if (!prev || !cur) return ENSLAM_EINVAL;
-        if (plan->channels != 1 && plan->channels != 3) return ENSLAM_EINVAL;
-        if (plan->channels == 1 && !lut) return ENSLAM_EINVAL;
-    }
-    A.channels = plan->channels;
-    A.prev = prev; A.cur = cur; A.lut = lut; A.L_prev = L_prev; A.L_cur = L_cur;
     event_sim_images_kernel<<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A);
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
@@ -243,20 +62,8 @@ int enslam_event_sim_boxroom(const enslam_event_sim_plan* plan, const double* po
                              const double* c_neg_map, double* L_ref, uint8_t* events, double* color_out, float* depth_out,
                              void* stream) {
     EsRoomArgs A;
-    const int rc = es_common(plan, c_pos_map, c_neg_map, L_ref, events, A.c);
+    const int rc = es_room_args(plan, poses, c_pos_map, c_neg_map, L_ref, events, color_out, depth_out, A);
     if (rc != ENSLAM_OK) return rc;
-    if (!poses || (color_out == nullptr) != (depth_out == nullptr)) return ENSLAM_EINVAL;
-    const enslam_event_sim_plan& P = *plan;
-    if (!es_finite(P.fx) || !es_finite(P.fy) || !es_finite(P.cx) || !es_finite(P.cy) || P.fx == 0.0 || P.fy == 0.0)
-        return ENSLAM_EINVAL;
-    A.fx = P.fx; A.fy = P.fy; A.cx = P.cx; A.cy = P.cy;
-    for (int a = 0; a < 3; ++a) {
-        A.room_lo[a] = P.room_lo[a]; A.room_hi[a] = P.room_hi[a]; A.box_lo[a] = P.box_lo[a]; A.box_hi[a] = P.box_hi[a];
-        A.phase[a] = P.phase[a];
-    }
-    for (int k = 0; k < 9; ++k) A.freq[k] = P.freq[k];
-    A.has_box = P.has_box != 0;
-    A.poses = poses; A.color_out = color_out; A.depth_out = depth_out;
     event_sim_boxroom_kernel<<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A);
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }

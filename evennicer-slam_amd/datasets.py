@@ -26,6 +26,10 @@ frames per image interval, poses from traj_density{d}.txt), `TUM_RGBD` (rgb.txt 
 nearest time stamp), `ScanNet` (frames/{color,depth,pose}, numeric file order) and `Azure` (scene/trajectory.log).  `CoFusion`
 is not built: its depth is OpenEXR and no EXR decoder is installed.
 
+`data.event_stream` + `data.frame_stamps` (opt-in, the three `*_event` readers): the event image of a frame is accumulated from a
+time-stamped stream (event_stream.accumulate) between the frame times instead of read from `<event_folder>`, and built as the
+uint8 array the png would decode to; see `BaseDataset._init_event_stream`.
+
 `data.prepare` (attribute `prepare`): 'host' (default) prepares a frame with numpy / torch on the CPU as described above and
 uploads the result; 'device' uploads the RAW decoded arrays and prepares them in one launch of csrc/frame_prep.hip
 (functional.frame_prepare) -- the same stages in the same order and precision, an eighth of the upload."""
@@ -97,6 +101,49 @@ class BaseDataset(torch.utils.data.Dataset):
                                 crop_size=self.crop_size, crop_edge=self.crop_edge, event_order=event_order,
                                 undistort_events=undistort_events, device=self.device)
 
+    def _init_event_stream(self, cfg, density=1):
+        """The opt-in keys `data.event_stream` (a stream: `.npz` of event_stream.EventStream.save, or the text layout `t x y p`)
+        and `data.frame_stamps` (a text file whose first field per non-comment line is a frame time).  With both set the
+        event image of an item is accumulated from the stream (event_stream.accumulate: the HIP kernel on a HIP device,
+        numpy on the CPU) instead of read from a png; it is built as the uint8 [H,W,3] array the png would decode to, at the
+        size of the raw colour frame, so everything behind the decode is shared.  Returns False when neither key is set."""
+        path, stamps = cfg['data'].get('event_stream'), cfg['data'].get('frame_stamps')
+        self._stream = None
+        if path is None and stamps is None:
+            return False
+        if path is None or stamps is None:
+            raise ValueError("data.event_stream and data.frame_stamps come together")
+        from . import event_stream as ES
+        times = ES.read_stamps(stamps)
+        assert len(times) >= self.n_img, "Number of frame stamps is below that of GT images!"
+        self._edges = ES.frame_edges(times[:self.n_img], 1, density)
+        dev = self.device if torch.device(self.device).type == 'cuda' else 'cpu'
+        self._stream = ES.load_stream(path, device=dev).time_sorted()
+        # events of bin b are the slice [cuts[b], cuts[b + 1]) of the sorted stream: edges[b] < t <= edges[b + 1]
+        self._cuts = torch.searchsorted(self._stream.t, torch.from_numpy(self._edges).to(dev), right=True).tolist()
+        self.event_paths = None
+        self.n_event = len(self._edges) - 1
+        return True
+
+    def _event_image(self, index, order):
+        """uint8 [H,W,3]: the decoded event png of item `index` >= 1, or the same array accumulated from the stream;
+        order 'replica' = channels (0, -, +), 'rpg' = (+, -, 0)."""
+        if self._stream is None:
+            return _imread_rgb(self.event_paths[index - 1])
+        from . import event_stream as ES
+        from PIL import Image
+        with Image.open(self.color_paths[0]) as im:
+            W, H = im.size
+        i0, i1 = self._cuts[index - 1], self._cuts[index]
+        part = ES.EventStream(*(a[i0:i1] for a in self._stream.arrays()))
+        ev = ES.accumulate(part, self._edges[index - 1:index + 1], H, W)[0].cpu().numpy()
+        rgb = np.zeros((H, W, 3), dtype=np.uint8)
+        if order == 'replica':
+            rgb[..., 1:] = ev
+        else:
+            rgb[..., 0], rgb[..., 1] = ev[..., 1], ev[..., 0]
+        return rgb
+
     def _color_depth(self, index):
         color = _imread_rgb(self.color_paths[index])
         if self.distortion is not None:                             # only the colour image, not the depth (:84-88)
@@ -159,21 +206,22 @@ class Replica(BaseDataset):
 class Replica_event(Replica):
     def __init__(self, cfg, args, scale, device='cuda:0'):
         super().__init__(cfg, args, scale, device)
-        self.event_folder = cfg['data']['event_folder'] if getattr(args, 'event_folder', None) is None else args.event_folder
-        self.event_paths = sorted(glob.glob(f'{self.event_folder}/*frame*.png'))
-        self.n_event = len(self.event_paths)
+        if not self._init_event_stream(cfg):
+            self.event_folder = cfg['data']['event_folder'] if getattr(args, 'event_folder', None) is None else args.event_folder
+            self.event_paths = sorted(glob.glob(f'{self.event_folder}/*frame*.png'))
+            self.n_event = len(self.event_paths)
         assert self.n_event == self.n_img - 1, "Number of GT events does not match that of GT images!"
 
     def __getitem__(self, index):
         if self._on_device():                                       # the event image keeps its lens model here (as below)
-            event = _imread_rgb(self.event_paths[index - 1]) if index >= 1 else None
+            event = self._event_image(index, 'replica') if index >= 1 else None
             color, depth, event, mask = self._prepare_device(_imread_rgb(self.color_paths[index]),
                                                              _imread_depth(self.depth_paths[index]), event, events=True)
             return index, color, depth, event, mask, self._pose(index).to(self.device)
         color, depth = self._color_depth(index)
         H, W = depth.shape
         if index >= 1:
-            event = _imread_rgb(self.event_paths[index - 1])        # png (0, -, +)
+            event = self._event_image(index, 'replica')             # png (0, -, +)
         else:
             event = np.zeros((H, W, 3), dtype=np.uint8)             # all black for the first frame
         event = torch.from_numpy(_resize_bilinear(event, (H, W)))
@@ -238,9 +286,10 @@ class RPG_event(RPG):
 
     def __init__(self, cfg, args, scale, device='cuda:0'):
         super().__init__(cfg, args, scale, device)
-        self.event_folder = cfg['data']['event_folder'] if getattr(args, 'event_folder', None) is None else args.event_folder
-        self.event_paths = sorted(glob.glob(f'{self.event_folder}/*.png'))
-        self.n_event = len(self.event_paths)
+        if not self._init_event_stream(cfg):
+            self.event_folder = cfg['data']['event_folder'] if getattr(args, 'event_folder', None) is None else args.event_folder
+            self.event_paths = sorted(glob.glob(f'{self.event_folder}/*.png'))
+            self.n_event = len(self.event_paths)
         assert self.n_event == self.n_img - 1, "Number of GT events does not match that of GT images!"
 
     def __getitem__(self, index):
@@ -252,13 +301,13 @@ class RPG_event(RPG):
         with Image.open(self.color_paths[image]) as im:
             grey = np.array(im.convert('L'))                        # cv2.IMREAD_GRAYSCALE, then GRAY2BGR (:252-253)
         if self._on_device():
-            event = _imread_rgb(self.event_paths[index - 1]) if index >= 1 else None
+            event = self._event_image(index, 'rpg') if index >= 1 else None
             color, depth, event, mask = self._prepare_device(grey, _imread_depth(self.depth_paths[image]), event, events=True,
                                                              event_order='rpg', undistort_events=True)
             return index, color, depth, event, mask, self._pose(index).to(self.device)
         color = np.repeat(grey[:, :, None], 3, axis=2)
         depth = _imread_depth(self.depth_paths[image]).astype(np.float32) / self.png_depth_scale
-        event = _imread_rgb(self.event_paths[index - 1]) if index >= 1 else np.zeros_like(color)    # RGB = (+, -, 0)
+        event = self._event_image(index, 'rpg') if index >= 1 else np.zeros_like(color)            # RGB = (+, -, 0)
         if self.distortion is not None:                             # colour and events, not the depth (:262-266)
             K = (self.fx, self.fy, self.cx, self.cy)
             color, event = undistort(color, K, self.distortion), undistort(event, K, self.distortion)
@@ -281,10 +330,11 @@ class RPG_event_dense(RPG):
 
     def __init__(self, cfg, args, scale, device='cuda:0'):
         super().__init__(cfg, args, scale, device)
-        self.event_folder = cfg['data']['event_folder'] if getattr(args, 'event_folder', None) is None else args.event_folder
-        self.event_paths = sorted(glob.glob(f'{self.event_folder}/*.png'))
         self.density = int(cfg['data']['density'])
-        self.n_event = len(self.event_paths)
+        if not self._init_event_stream(cfg, self.density):
+            self.event_folder = cfg['data']['event_folder'] if getattr(args, 'event_folder', None) is None else args.event_folder
+            self.event_paths = sorted(glob.glob(f'{self.event_folder}/*.png'))
+            self.n_event = len(self.event_paths)
         assert self.n_event == (self.n_img - 1) * self.density, "Number of GT events does not match that of GT images!"
         with open(f'{self.input_folder}/traj_density{self.density}.txt', "r") as f:
             lines = f.readlines()

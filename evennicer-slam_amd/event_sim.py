@@ -28,8 +28,20 @@ methods run a numpy route of the same definition, operation for operation, so se
 two agree bit for bit wherever no transcendental function of the device decides (grey images, or `host_log=True`); the
 device's log and sin are an ulp or two from numpy's, which moves a count only where d / C sits that close to an integer.
 
-Not modelled: refractory period, leak and shot noise, per-event time stamps, bandwidth-limited pixels, learned
-frame interpolation."""
+Time stamps (`stamps=(t_a, t_b)` on step_images / step_scene; csrc/event_stream.hip; include/enslam_hip.h states it too).
+The counts and L_ref stay those of the closed form above.  At sub-step s let L_prev be the level seen at sub-step s - 1 (for
+s = 1 the previous frame's level: L_a of the images route, the room rendered at the previous frame's pose), L_s this
+sub-step's level and R the value of L_ref before the update.  The n events the pixel fires there are k = 1..n:
+
+    X_k = R + k * C_pos (positive) or R - k * C_neg (negative), the product, then the sum
+    f_k = (X_k - L_prev) / (L_s - L_prev), then limited to [0, 1] (below 0 or not a number: 0; above 1: 1)
+    t_k = t_a + (((s - 1) + f_k) / K) * (t_b - t_a), in exactly this operation order
+
+Linear level-crossing interpolation, as ESIM does it.  The limit is needed: over the image cases of tests/event_sim_cases.py
+f reaches 1 + 2.2e-16 at one event and drops to 1.5e-16 at another, whose t_k rounds to t_a.  The stream leaves in
+pixel-major order (row-major pixels, time-ordered within a pixel) as an event_stream.EventStream.
+
+Not modelled: refractory period, leak and shot noise, bandwidth-limited pixels, learned frame interpolation."""
 import numpy as np
 import torch
 
@@ -75,6 +87,53 @@ def sensor_update(L, ref, pos, neg, c_pos, c_neg):
 def saturate(neg, pos):
     """uint8 [H,W,2] = (-, +) of two float64 count arrays"""
     return np.stack([np.minimum(neg, 255.0), np.minimum(pos, 255.0)], axis=-1).astype(np.uint8)
+
+
+def stream_substep(s, K, t_a, t_b, R, n_pos, n_neg, c_pos, c_neg, L_prev, L):
+    """The time-stamped events of sub-step s (1-based) of K, numpy route of the model above: R is L_ref before the update,
+    n_pos / n_neg the counts the update added (float64 [H,W]), L_prev and L the levels at the previous and at this sub-step.
+    Returns (pixel int64 [n], t float64 [n], p uint8 [n]) in pixel order, k ascending within a pixel."""
+    shape = R.shape
+    n = (n_pos + n_neg).reshape(-1)
+    idx = np.nonzero(n > 0)[0]
+    reps = n[idx].astype(np.int64)
+    pix = np.repeat(idx, reps)
+    first = np.cumsum(reps) - reps
+    k = (np.arange(pix.size, dtype=np.int64) - np.repeat(first, reps) + 1).astype(np.float64)
+    up = (n_pos.reshape(-1) > 0)[pix]
+    cp = np.broadcast_to(np.asarray(c_pos, dtype=np.float64), shape).reshape(-1)[pix]
+    cn = np.broadcast_to(np.asarray(c_neg, dtype=np.float64), shape).reshape(-1)[pix]
+    step = k * np.where(up, cp, cn)
+    r = R.reshape(-1)[pix]
+    X = np.where(up, r + step, r - step)
+    lp = L_prev.reshape(-1)[pix]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        f = (X - lp) / (L.reshape(-1)[pix] - lp)
+    f = np.where(f >= 0.0, f, 0.0)
+    f = np.where(f > 1.0, 1.0, f)
+    u = ((s - 1) + f) / K
+    return pix, t_a + u * (t_b - t_a), up.astype(np.uint8)
+
+
+def _stream_of(parts, W, device='cpu'):
+    """EventStream of per-sub-step (pixel, t, p) lists: a stable sort by pixel keeps the sub-step order within a pixel"""
+    from .event_stream import EventStream
+    pix = np.concatenate([q[0] for q in parts]) if parts else np.zeros(0, dtype=np.int64)
+    t = np.concatenate([q[1] for q in parts]) if parts else np.zeros(0)
+    p = np.concatenate([q[2] for q in parts]) if parts else np.zeros(0, dtype=np.uint8)
+    order = np.argsort(pix, kind='stable')
+    pix = pix[order]
+    return EventStream(t[order], (pix % W).astype(np.uint16), (pix // W).astype(np.uint16), p[order]).to(device)
+
+
+def _stamps(stamps):
+    try:
+        t_a, t_b = (float(v) for v in stamps)
+    except (TypeError, ValueError):
+        raise EnslamError("EventSimulator: stamps must be the pair (t_a, t_b) of the interval's frame times") from None
+    if not (t_a <= t_b and abs(t_a) < float('inf') and abs(t_b) < float('inf')):
+        raise EnslamError(f"EventSimulator: stamps must be finite with t_a <= t_b (got {t_a}, {t_b})")
+    return t_a, t_b
 
 
 def render_boxroom(room, c2w, cam):
@@ -238,34 +297,81 @@ class EventSimulator:
         return self
 
     # ---- one interval ------------------------------------------------------------------------------------------------------
-    def step_images(self, prev, cur, host_log=False):
+    def step_images(self, prev, cur, host_log=False, stamps=None):
         """Events uint8 [H,W,2] = (-, +) between two decoded images (numpy arrays, or tensors on the device).  host_log: on a
         device, take the two level images from the host (numpy's log) instead of the kernel's -- bit-equal to the CPU route
-        for RGB images too, at the price of two float64 uploads."""
+        for RGB images too, at the price of two float64 uploads.  stamps = (t_a, t_b), the times of the two frames: returns
+        (events, EventStream) -- the same image and state, and the time-stamped events in pixel-major order."""
         self._need_state()
+        if stamps is not None:
+            stamps = _stamps(stamps)
         if not self.on_device:
             La, Lb = self._host_level(prev), self._host_level(cur)
             ref = self._ref.numpy()
             pos, neg = np.zeros_like(ref), np.zeros_like(ref)
             cp, cn = self._thresholds()
             dL = Lb - La
+            parts, L_before = [], La
             for s in range(1, self.substeps + 1):
-                sensor_update(La + (s / self.substeps) * dL, ref, pos, neg, cp, cn)
-            return torch.from_numpy(saturate(neg, pos))
+                L = La + (s / self.substeps) * dL
+                if stamps is None:
+                    sensor_update(L, ref, pos, neg, cp, cn)
+                    continue
+                R, pos0, neg0 = ref.copy(), pos.copy(), neg.copy()
+                sensor_update(L, ref, pos, neg, cp, cn)
+                parts.append(stream_substep(s, self.substeps, stamps[0], stamps[1], R, pos - pos0, neg - neg0, cp, cn, L_before, L))
+                L_before = L
+            events = torch.from_numpy(saturate(neg, pos))
+            return events if stamps is None else (events, _stream_of(parts, self.W))
         if host_log:
             levels = tuple(torch.from_numpy(self._host_level(im)).to(self.device) for im in (prev, cur))
+            if stamps is not None:
+                return self._with_stream(self._EF.event_stream_images(None, None, self._ref, stamps, substeps=self.substeps,
+                                                                      levels=levels, **self._kw()))
             return self._EF.event_sim_images(None, None, self._ref, substeps=self.substeps, levels=levels, **self._kw())
         a, b = self._image(prev), self._image(cur)
         if a.shape != b.shape:
             raise EnslamError(f"EventSimulator: the two images differ in shape ({tuple(a.shape)}, {tuple(b.shape)})")
+        if stamps is not None:
+            return self._with_stream(self._EF.event_stream_images(a, b, self._ref, stamps, substeps=self.substeps, lut=self._lut,
+                                                                  **self._kw()))
         return self._EF.event_sim_images(a, b, self._ref, substeps=self.substeps, lut=self._lut, **self._kw())
 
-    def step_scene(self, room, c2w_prev, c2w_cur, cam, want_frame=False):
+    @staticmethod
+    def _with_stream(out):
+        from .event_stream import EventStream
+        events, arrays = out
+        return events, EventStream(*arrays)
+
+    def step_scene(self, room, c2w_prev, c2w_cur, cam, want_frame=False, stamps=None):
         """Events of the interval between two views of `room`; with want_frame also (color float64 [H,W,3], depth float32
-        [H,W]) of c2w_cur, what room.render(c2w_cur, cam) returns."""
+        [H,W]) of c2w_cur, what room.render(c2w_cur, cam) returns.  stamps = (t_a, t_b), the times of the two views: returns
+        (events, EventStream) -- the room is then rendered at c2w_prev as well, for the level the first sub-step starts from
+        (want_frame is not combined with it)."""
         self._need_state()
         self._check_cam(cam)
         poses = interpolate_poses(_pose64(c2w_prev), _pose64(c2w_cur), self.substeps)
+        if stamps is not None:
+            if want_frame:
+                raise EnslamError("EventSimulator.step_scene: stamps and want_frame are not combined")
+            stamps = _stamps(stamps)
+            first = np.eye(4, dtype=np.float64)
+            first[:3, :] = _pose64(c2w_prev)[:3, :]
+            with_prev = np.concatenate([first[None], poses], axis=0)
+            if self.on_device:
+                return self._with_stream(self._EF.event_stream_boxroom(room, with_prev, cam, self._ref, stamps, **self._kw()))
+            ref = self._ref.numpy()
+            pos, neg = np.zeros_like(ref), np.zeros_like(ref)
+            cp, cn = self._thresholds()
+            parts = []
+            L_before = np.log(luminance(render_boxroom(room, with_prev[0], cam)[0]) + self.eps)
+            for s, P in enumerate(poses, start=1):
+                L = np.log(luminance(render_boxroom(room, P, cam)[0]) + self.eps)
+                R, pos0, neg0 = ref.copy(), pos.copy(), neg.copy()
+                sensor_update(L, ref, pos, neg, cp, cn)
+                parts.append(stream_substep(s, self.substeps, stamps[0], stamps[1], R, pos - pos0, neg - neg0, cp, cn, L_before, L))
+                L_before = L
+            return torch.from_numpy(saturate(neg, pos)), _stream_of(parts, self.W)
         if self.on_device:
             return self._EF.event_sim_boxroom(room, poses, cam, self._ref, want_frame=want_frame, **self._kw())
         ref = self._ref.numpy()

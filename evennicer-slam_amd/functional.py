@@ -3009,6 +3009,175 @@ def event_sim_boxroom(room, poses, cam, state, eps=1e-3, c_pos=0.2, c_neg=0.2, c
 
 
 # ------------------------------------------------------------------------------------------------
+# Time-stamped event streams (csrc/event_stream.hip; event_sim.EventSimulator and event_stream.accumulate drive it)
+# ------------------------------------------------------------------------------------------------
+EVENT_ACCUMULATE_MAX_CELLS = 1 << 25        # B * H * W of one enslam_event_accumulate call (256 MiB of uint32 counts)
+
+
+def _event_stamps(what, stamps):
+    try:
+        t_a, t_b = (float(v) for v in stamps)
+    except (TypeError, ValueError):
+        raise L.EnslamError(f"{what}: stamps must be the pair (t_a, t_b) of the interval's frame times") from None
+    if not (t_a <= t_b and abs(t_a) < float('inf') and abs(t_b) < float('inf')):
+        raise L.EnslamError(f"{what}: stamps must be finite with t_a <= t_b (got {t_a}, {t_b})")
+    return t_a, t_b
+
+
+def _event_stream_run(what, count, emit, state, H, W, stamps):
+    """count -> prefix sum -> one read-back of the total -> emit; returns (events, (t, x, y, p))"""
+    if H > 65536 or W > 65536:
+        raise L.EnslamError(f"{what}: event coordinates are uint16, the sensor is {H} x {W}")
+    dev = state.device
+    with torch.cuda.device(dev):
+        counts = torch.empty((H, W), dtype=torch.int64, device=dev)
+        L.check(count(counts), what + " (count)")
+        ends = torch.cumsum(counts.view(-1), 0)
+        total = int(ends[-1].item())                            # the one read-back of the interval
+        if total > 2 ** 31 - 1:
+            raise L.EnslamError(f"{what}: {total} events in one interval (at most 2^31 - 1)")
+        events = torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
+        t = torch.empty(total, dtype=torch.float64, device=dev)
+        x, y = (torch.empty(total, dtype=torch.uint16, device=dev) for _ in range(2))
+        p = torch.empty(total, dtype=torch.uint8, device=dev)
+        L.check(emit(events, ends, total, stamps[0], stamps[1], t, x, y, p), what + " (emit)")
+    return events, (t, x, y, p)
+
+
+def event_stream_images(prev, cur, state, stamps, substeps=8, eps=1e-3, c_pos=0.2, c_neg=0.2, lut=None, levels=None,
+                        c_pos_map=None, c_neg_map=None):
+    """One interval of the image route with time stamps (enslam_event_stream_images_*, enslam_hip.h): the arguments of
+    `event_sim_images` plus stamps = (t_a, t_b), the times of the two frames.  Returns (events, (t, x, y, p)): the uint8
+    [H,W,2] image `event_sim_images` returns (and the same update of `state`), and the events as device tensors -- t float64,
+    x, y uint16, p uint8 (1 = positive) -- in pixel-major order, time-ordered within a pixel."""
+    what = "event_stream_images"
+    if not torch.is_tensor(state):
+        raise L.EnslamError(f"{what}: state must be a tensor")
+    H, W = (int(v) for v in state.shape) if state.dim() == 2 else (0, 0)
+    _event_sim_checks(what, H, W, substeps, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, False)
+    stamps = _event_stamps(what, stamps)
+    dev = state.device
+    channels = 1
+    if levels is not None:
+        if len(levels) != 2:
+            raise L.EnslamError(f"{what}: levels must be the pair (L_prev, L_cur)")
+        for name, t in zip(('L_prev', 'L_cur'), levels):
+            _event_sim_tensor(what, name, t, torch.float64, (H, W), dev)
+        prev = cur = None
+    else:
+        if not torch.is_tensor(prev) or not torch.is_tensor(cur):
+            raise L.EnslamError(f"{what}: prev and cur must be tensors (or pass `levels`)")
+        for name, t in (('prev', prev), ('cur', cur)):
+            if t.dim() not in (2, 3) or t.shape != cur.shape:
+                raise L.EnslamError(f"{what}: prev and cur must be uint8 tensors of one shape [H,W] or [H,W,C]")
+            shape = (H, W) if t.dim() == 2 else (H, W, int(t.shape[2]))
+            if t.dim() == 3 and shape[2] not in (1, 3):
+                raise L.EnslamError(f"{what}: images must have 1 or 3 channels (got {shape[2]})")
+            _event_sim_tensor(what, name, t, torch.uint8, shape, dev)
+        channels = 3 if cur.dim() == 3 and cur.shape[2] == 3 else 1
+        if channels == 1:
+            if lut is None:
+                raise L.EnslamError(f"{what}: grey images need the host-computed table `lut` (float64 [256])")
+            _event_sim_tensor(what, 'lut', lut, torch.float64, (256,), dev)
+    plan = event_sim_plan(H, W, substeps, eps, c_pos, c_neg, channels=channels)
+    la, lb = levels if levels is not None else (None, None)
+    src = (ctypes.byref(plan), _ptr(prev), _ptr(cur), _ptr(lut), _ptr(la), _ptr(lb), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state))
+    lib = L.lib()
+    return _event_stream_run(
+        what, lambda counts: lib.enslam_event_stream_images_count(*src, _ptr(counts), _stream()),
+        lambda events, ends, total, t_a, t_b, t, x, y, p: lib.enslam_event_stream_images_emit(
+            *src, _ptr(events), _ptr(ends), total, t_a, t_b, _ptr(t), _ptr(x), _ptr(y), _ptr(p), _stream()),
+        state, H, W, stamps)
+
+
+def event_stream_boxroom(room, poses, cam, state, stamps, eps=1e-3, c_pos=0.2, c_neg=0.2, c_pos_map=None, c_neg_map=None):
+    """One interval of the analytic route with time stamps (enslam_event_stream_boxroom_*, enslam_hip.h).  poses: float64
+    [K+1,3|4,4] -- row 0 the PREVIOUS frame's pose (rendered for the level the first sub-step starts from), rows 1..K the
+    sub-steps, the last one the frame the interval ends at; stamps = (t_a, t_b).  Returns (events, (t, x, y, p)) as
+    `event_stream_images`; `state` is updated as `event_sim_boxroom` updates it."""
+    what = "event_stream_boxroom"
+    if not torch.is_tensor(state):
+        raise L.EnslamError(f"{what}: state must be a tensor")
+    H, W = int(cam['H']), int(cam['W'])
+    dev = state.device
+    p = poses if torch.is_tensor(poses) else torch.as_tensor(poses)
+    if p.dim() != 3 or p.shape[0] < 2 or p.shape[1] not in (3, 4) or p.shape[2] != 4 or p.dtype != torch.float64:
+        raise L.EnslamError(f"{what}: poses must be float64 [K+1,3|4,4], the previous frame's first (got {p.dtype} {tuple(p.shape)})")
+    K = int(p.shape[0]) - 1
+    _event_sim_checks(what, H, W, K, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, False)
+    stamps = _event_stamps(what, stamps)
+    if torch.is_tensor(poses):
+        _require_hip(poses, f"{what}: a pose tensor")
+    if not (float(cam['fx']) != 0 and float(cam['fy']) != 0):
+        raise L.EnslamError(f"{what}: fx and fy must not be zero")
+    p = p[:, :3, :].to(dev).contiguous()
+    sub = p[1:]                                                 # contiguous: the K sub-step poses of the count pass
+    plan = event_sim_plan(H, W, K, eps, c_pos, c_neg, cam=cam, room=room)
+    maps = (_ptr(c_pos_map), _ptr(c_neg_map), _ptr(state))
+    lib = L.lib()
+    return _event_stream_run(
+        what, lambda counts: lib.enslam_event_stream_boxroom_count(ctypes.byref(plan), _ptr(sub), *maps, _ptr(counts), _stream()),
+        lambda events, ends, total, t_a, t_b, t, x, y, q: lib.enslam_event_stream_boxroom_emit(
+            ctypes.byref(plan), _ptr(p), *maps, _ptr(events), _ptr(ends), total, t_a, t_b, _ptr(t), _ptr(x), _ptr(y), _ptr(q),
+            _stream()),
+        state, H, W, stamps)
+
+
+def event_accumulate(t, x, y, p, edges, H, W, want_unsaturated=False):
+    """Bin a stream into count images (enslam_event_accumulate, enslam_hip.h).  t float64 [N], x, y uint16 [N], p uint8 [N] on
+    one HIP device, in any order; edges: B + 1 ascending float64 times (a host sequence or array).  Event t goes to bin b
+    where edges[b] < t <= edges[b+1].  Returns (counts uint8 [B,H,W,2] = (-, +) saturated at 255, dropped) -- dropped a pair
+    of Python ints (outside every bin, outside the sensor) -- and with want_unsaturated also the uint32 counts as a third
+    item.  The bins are processed in chunks of at most EVENT_ACCUMULATE_MAX_CELLS / (H W) so that the uint32 workspace stays
+    bounded; the result does not depend on the chunking."""
+    what = "event_accumulate"
+    for name, a, dtype in (('t', t, torch.float64), ('x', x, torch.uint16), ('y', y, torch.uint16), ('p', p, torch.uint8)):
+        if not torch.is_tensor(a):
+            raise L.EnslamError(f"{what}: {name} must be a tensor (got {type(a).__name__})")
+        _require_hip(a, f"{what}: {name}")
+        if a.dtype != dtype or a.dim() != 1 or a.shape != t.shape or not a.is_contiguous() or a.device != t.device:
+            raise L.EnslamError(f"{what}: {name} must be a contiguous {dtype} tensor [N] on the device of t (got {a.dtype} "
+                                f"{tuple(a.shape)} on {a.device})")
+    import numpy as np
+    e = np.ascontiguousarray(np.asarray(edges.cpu() if torch.is_tensor(edges) else edges, dtype=np.float64))
+    H, W = int(H), int(W)
+    if e.ndim != 1 or e.size < 2:
+        raise L.EnslamError(f"{what}: edges must be B + 1 >= 2 ascending times (got shape {e.shape})")
+    if H <= 0 or W <= 0:
+        raise L.EnslamError(f"{what}: the sensor must have pixels (got {H} x {W})")
+    if not bool(np.all(e[:-1] <= e[1:])):
+        raise L.EnslamError(f"{what}: edges must be ascending and hold no NaN")
+    B, N, dev = int(e.size) - 1, int(t.shape[0]), t.device
+    if H * W > EVENT_ACCUMULATE_MAX_CELLS:
+        raise L.EnslamError(f"{what}: a sensor of {H} x {W} pixels is above the {EVENT_ACCUMULATE_MAX_CELLS} cells of one call")
+    per = max(EVENT_ACCUMULATE_MAX_CELLS // (H * W), 1)
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        counts = torch.empty((B, H, W, 2), dtype=torch.uint8, device=dev)
+        full = torch.empty((B, H, W, 2), dtype=torch.uint32, device=dev) if want_unsaturated else None
+        edges_dev = torch.from_numpy(e).to(dev)
+        dropped = torch.empty((-(-B // per), 2), dtype=torch.int64, device=dev)
+        acc = None
+        for c, b0 in enumerate(range(0, B, per)):
+            b1 = min(b0 + per, B)
+            if want_unsaturated:
+                acc = full[b0:b1]
+            elif acc is None or acc.shape[0] != b1 - b0:        # the workspace of one chunk, reused by the next
+                acc = torch.empty((b1 - b0, H, W, 2), dtype=torch.uint32, device=dev)
+            host = e[b0:b1 + 1]
+            L.check(lib.enslam_event_accumulate(_ptr(t), _ptr(x), _ptr(y), _ptr(p), N,
+                                                host.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                edges_dev.data_ptr() + 8 * b0, b1 - b0, H, W, _ptr(acc), _ptr(counts[b0:b1]),
+                                                _ptr(dropped[c]), _stream()), "enslam_event_accumulate")
+        d = dropped.cpu().tolist()
+    chunks = len(d)
+    sensor = d[0][1]
+    # an event inside the range misses all chunks but its own, one outside misses every chunk
+    by_time = sum(row[0] for row in d) - (N - sensor) * (chunks - 1)
+    return (counts, (by_time, sensor), full) if want_unsaturated else (counts, (by_time, sensor))
+
+
+# ------------------------------------------------------------------------------------------------
 # Frame report (csrc/frame_report.hip; frame_vis.Visualizer and frame_vis.render_metrics drive it)
 # ------------------------------------------------------------------------------------------------
 SSIM_TILE = (16, 32)                    # ENSLAM_SSIM_TILE_H, ENSLAM_SSIM_TILE_W: output pixels of one workgroup

@@ -166,11 +166,13 @@ def demo_config(inp, evf, cam, device='cuda:0', env=None):
     }
 
 
-def write_demo_sequence(root, n, cam, step=0.012, yaw_deg=0.5, events=None, sim=None):
+def write_demo_sequence(root, n, cam, step=0.012, yaw_deg=0.5, events=None, sim=None, stamps=None, streams=None):
     """n frames of a BoxRoom inside the demo bound along `trajectory`, written in the Replica_event layout.
     events: None writes all-zero event images; 'simulate' fills them from `event_sim.EventSimulator.step_scene` along the
     trajectory with `sim` (default: a simulator with default parameters on the CPU, its numpy route; pass one on a HIP device
     to run the kernel, which then renders the frames as well -- one launch per frame).
+    stamps (n frame times) with events = 'simulate': the intervals are simulated with time stamps and the list `streams`
+    receives one event_stream.EventStream per interval (pixel-major); the frames then come from BoxRoom.render.
     Returns ((input_folder, event_folder), poses)."""
     from . import datasets as D
     from .scene import scene_bound
@@ -191,6 +193,12 @@ def write_demo_sequence(root, n, cam, step=0.012, yaw_deg=0.5, events=None, sim=
         elif i == 0:
             col, dep = room.render(c2w.double(), cam)
             sim.reset((room, c2w.double(), cam))
+        elif stamps is not None:
+            col, dep = room.render(c2w.double(), cam)
+            ev, stream = sim.step_scene(room, poses[i - 1].double(), c2w.double(), cam, stamps=(stamps[i - 1], stamps[i]))
+            evs.append(ev.cpu().numpy())
+            if streams is not None:
+                streams.append(stream)
         elif sim.on_device:
             ev, col, dep = sim.step_scene(room, poses[i - 1].double(), c2w.double(), cam, want_frame=True)
             evs.append(ev.cpu().numpy())

@@ -1014,6 +1014,64 @@ int enslam_event_sim_boxroom(const enslam_event_sim_plan *plan, const double *po
                              const double *c_neg_map, double *L_ref, uint8_t *events, double *color_out, float *depth_out,
                              void *stream);
 
+/* Time-stamped event streams (event_stream.py, csrc/event_stream.hip): the simulator's events with time stamps, and the
+ * accumulator that bins any stream into the count images above.  All arithmetic is float64, no fused multiply-adds.
+ *
+ * Stream: struct-of-arrays of N events -- t float64 seconds, x, y uint16, p uint8 (1 = positive).
+ *
+ * Model.  The sensor is the one above, unchanged: the counts and the new L_ref of an interval are those of its closed form.
+ *   The interval [t_a, t_b] is visited at sub-steps s = 1..K.  At sub-step s let L_prev be the level seen at sub-step s - 1
+ *   (for s = 1 the previous frame's level), L_s this sub-step's level and R the value of L_ref before the update.  When the
+ *   pixel fires n events there, they are the events k = 1..n:
+ *     X_k = R + k * C_pos for positive events, R - k * C_neg for negative ones (the product, then the sum)
+ *     f_k = (X_k - L_prev) / (L_s - L_prev), then limited to [0, 1]: below 0 or not a number gives 0, above 1 gives 1
+ *     t_k = t_a + (((s - 1) + f_k) / K) * (t_b - t_a), in exactly this operation order
+ *   The limit is needed: rounding puts f a few 1e-16 outside [0, 1] at single events.  Images route: L_prev at s = 1 is L_a.
+ *   Analytic route: `poses` has K + 1 rows, row 0 the previous frame's pose, which the kernel renders for L_prev only.
+ *   Order of the output: pixel-major -- row-major pixels, time-ordered within a pixel (sub-step, then k).
+ *
+ * Two launches per interval, one thread per pixel, no atomics (bit-reproducible):
+ *   enslam_event_stream_*_count: the arguments of enslam_event_sim_* without the outputs; counts (device int64 [H,W]) receives
+ *     the unsaturated number of events per pixel (limited to 2^33 per pixel); L_ref is only read.  The boxroom entry takes
+ *     the K sub-step poses [K,12] (as enslam_event_sim_boxroom).
+ *   enslam_event_stream_*_emit: `ends` (device int64 [H,W]) is the INCLUSIVE prefix sum of `counts` in row-major order, `total`
+ *     its last element, read back by the caller, = the capacity of t, x, y, p (which may be NULL when total = 0).  Writes every
+ *     pixel's run at its offset, the saturated events image and the new L_ref -- both bit-equal to enslam_event_sim_*'s on
+ *     the same inputs.  The boxroom entry takes K + 1 poses [K+1,12]; plan.K stays K.  No store leaves a pixel's own run or
+ *     the capacity, whatever `ends` holds.
+ *   ENSLAM_EINVAL without a launch: what enslam_event_sim_* refuses, plan.init != 0, NULL counts / ends, total < 0, a NULL
+ *     stream array with total > 0, t_a or t_b not finite or t_b < t_a.  ENSLAM_EUNSUPPORTED: total above 2^31 - 1, H or W
+ *     above 65536, and what enslam_event_sim_* does not support.
+ *
+ * enslam_event_accumulate: N events in any order into B time bins given by ascending edges [B+1] (equal neighbours make an
+ *   empty bin; edges[0] may be -inf).  An event goes to bin b where edges[b] < t <= edges[b+1]: an event at a frame's own time
+ *   belongs to the interval that ends there, as f = 1 does above.  Events with x >= W or y >= H are dropped and counted in
+ *   dropped[1] (checked before any address is formed, and before the time is looked at); the others outside every bin (or
+ *   with a t that is not a number) are dropped and counted in dropped[0].  p != 0 counts as positive.
+ *   acc (device uint32 [B,H,W,2] = (-, +), 8-byte aligned) receives the unsaturated counts, counts (device uint8 [B,H,W,2],
+ *   2-byte aligned) the counts saturated at 255, dropped (device uint64 [2]) the two counters; all three are overwritten.
+ *   edges_host (host) is checked, edges (device, the same values) is what the kernel reads.  One thread per event, binary
+ *   search of the edges (in LDS while B + 1 <= 2048), integer atomic adds: independent of the order of the events and
+ *   bit-reproducible.  Two memsets and one launch when N = 0, two launches otherwise.
+ *   ENSLAM_EINVAL without a launch: NULL edges_host, edges, acc, counts or dropped, N < 0, a NULL stream array with N > 0, B, H
+ *   or W <= 0, misaligned acc / counts / dropped, edges that descend or hold a NaN.  ENSLAM_EUNSUPPORTED: N above 2^31 - 1 or
+ *   B * H * W above 2^30 (the Python wrapper splits the bins). */
+int enslam_event_stream_images_count(const enslam_event_sim_plan *plan, const uint8_t *prev, const uint8_t *cur,
+                                     const double *lut, const double *L_prev, const double *L_cur, const double *c_pos_map,
+                                     const double *c_neg_map, const double *L_ref, int64_t *counts, void *stream);
+int enslam_event_stream_images_emit(const enslam_event_sim_plan *plan, const uint8_t *prev, const uint8_t *cur,
+                                    const double *lut, const double *L_prev, const double *L_cur, const double *c_pos_map,
+                                    const double *c_neg_map, double *L_ref, uint8_t *events, const int64_t *ends, int64_t total,
+                                    double t_a, double t_b, double *t, uint16_t *x, uint16_t *y, uint8_t *p, void *stream);
+int enslam_event_stream_boxroom_count(const enslam_event_sim_plan *plan, const double *poses, const double *c_pos_map,
+                                      const double *c_neg_map, const double *L_ref, int64_t *counts, void *stream);
+int enslam_event_stream_boxroom_emit(const enslam_event_sim_plan *plan, const double *poses, const double *c_pos_map,
+                                     const double *c_neg_map, double *L_ref, uint8_t *events, const int64_t *ends, int64_t total,
+                                     double t_a, double t_b, double *t, uint16_t *x, uint16_t *y, uint8_t *p, void *stream);
+int enslam_event_accumulate(const double *t, const uint16_t *x, const uint16_t *y, const uint8_t *p, int64_t N,
+                            const double *edges_host, const double *edges, int32_t B, int32_t H, int32_t W, uint32_t *acc,
+                            uint8_t *counts, uint64_t *dropped, void *stream);
+
 /* Per-iteration frame report (frame_vis.py, csrc/frame_report.hip): the figure of the reference's src/utils/Visualizer.py
  * as one uint8 sheet, the frame's error sums, and the mean SSIM of two images.
  *

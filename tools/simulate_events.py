@@ -4,6 +4,7 @@
                                     [--layout replica_event|rpg_event] [--max-frames N] [--host-log]
     python tools/simulate_events.py --demo N --out DIR
     common: [--device cuda:0|cpu] [--c-pos C] [--c-neg C] [--sigma-c S] [--substeps K] [--eps E] [--seed N]
+            [--stream OUT [--stamps FILE | --fps F]]
 
 With a reference-format YAML chain (config.load_config; --input_folder overrides data.input_folder) the colour images of
 any sequence the readers support are read RAW -- decoded, nothing else: grey for the rpg* layouts, RGB otherwise -- and the
@@ -14,6 +15,11 @@ follows the configuration's dataset.  Point `data.event_folder` (or --event_fold
 
 --demo N writes the analytic room of synthetic.write_demo_sequence with simulated events (frames, depth, poses and events)
 under --out; on a HIP device the kernel renders the frames as well.
+
+--stream OUT also writes the simulated events with their time stamps (linear level-crossing interpolation inside each
+sub-step, event_sim.py), sorted by time: OUT ending in .npz as event_stream.EventStream.save writes it, any other name as text,
+one event per line `t x y p`.  The frame times come from --stamps (first field per non-comment line) or are i / --fps (30).
+tools/events_to_frames.py bins such a stream back into event images, at any gap or density.
 
 --device cpu runs the numpy route of the same model.  Prints one JSON line: frames, the share of pixels with an event, the
 mean counts per polarity and pixel, the share of saturated pixels, and seconds per frame (wall time of the whole loop,
@@ -71,6 +77,9 @@ def main(argv=None):
     ap.add_argument('--substeps', type=int, default=8)
     ap.add_argument('--eps', type=float, default=1e-3)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--stream', default=None)
+    ap.add_argument('--stamps', default=None)
+    ap.add_argument('--fps', type=float, default=30.0)
     args = ap.parse_args(argv)
     if (args.demo is None) == (args.config is None):
         ap.error("give either a CONFIG or --demo N")
@@ -81,13 +90,27 @@ def main(argv=None):
 
     sync = torch.cuda.synchronize if torch.device(args.device).type == 'cuda' else (lambda: None)
     out = dict(out=args.out, device=args.device)
+    streams = []
+
+    def frame_times(n):
+        if args.stream is None:
+            return None
+        if args.stamps is not None:
+            from evennicer_slam_amd.event_stream import read_stamps
+            times = read_stamps(args.stamps)
+            if len(times) < n:
+                raise SystemExit(f"{args.stamps}: {len(times)} frame times for {n} frames")
+            return times[:n].tolist()
+        return [i / args.fps for i in range(n)]
+
     if args.demo is not None:
         from evennicer_slam_amd.synthetic import write_demo_sequence
         if args.demo < 2:
             ap.error("--demo needs at least 2 frames")
         sim = simulator(args, DEMO_CAM['H'], DEMO_CAM['W'])
         t0 = time.perf_counter()
-        (inp, evf), _ = write_demo_sequence(args.out, args.demo, DEMO_CAM, events='simulate', sim=sim)
+        (inp, evf), _ = write_demo_sequence(args.out, args.demo, DEMO_CAM, events='simulate', sim=sim,
+                                            stamps=frame_times(args.demo), streams=streams)
         sync()
         seconds = time.perf_counter() - t0
         events = [D._imread_rgb(os.path.join(evf, p))[:, :, 1:] for p in sorted(os.listdir(evf))]
@@ -109,9 +132,15 @@ def main(argv=None):
         prev = raw_color(paths[0], grey)
         sim = simulator(args, prev.shape[0], prev.shape[1]).reset(prev, host_log=args.host_log)
         events = []
+        times = frame_times(len(paths))
         for i in range(1, len(paths)):
             cur = raw_color(paths[i], grey)
-            ev = sim.step_images(prev, cur, host_log=args.host_log).cpu().numpy()
+            if times is None:
+                ev = sim.step_images(prev, cur, host_log=args.host_log).cpu().numpy()
+            else:
+                ev, stream = sim.step_images(prev, cur, host_log=args.host_log, stamps=(times[i - 1], times[i]))
+                ev = ev.cpu().numpy()
+                streams.append(stream.to('cpu'))
             D.save_event_image(args.out, i, ev, layout)
             events.append(ev)
             prev = cur
@@ -119,6 +148,14 @@ def main(argv=None):
         seconds = time.perf_counter() - t0
         out.update(input_folder=ds.input_folder, event_folder=args.out, frames=len(paths), layout=layout)
     out.update(event_images=len(events), **event_stats(events), seconds_per_frame=seconds / max(len(events), 1))
+    if args.stream is not None:
+        from evennicer_slam_amd.event_stream import EventStream, write_events_txt
+        whole = EventStream.concatenate([s.to('cpu') for s in streams]).time_sorted()
+        if args.stream.endswith('.npz'):
+            whole.save(args.stream)
+        else:
+            write_events_txt(args.stream, whole)
+        out.update(stream=args.stream, stream_events=len(whole))
     print(json.dumps(out), flush=True)
     return out
 
