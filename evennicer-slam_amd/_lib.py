@@ -66,6 +66,11 @@ class EventSimPlan(ctypes.Structure):         # enslam_event_sim_plan
                 ("box_lo", c_double * 3), ("box_hi", c_double * 3), ("freq", c_double * 9), ("phase", c_double * 3)]
 
 
+class EventNoiseParams(ctypes.Structure):     # enslam_event_noise
+    _fields_ = [("refractory", c_double), ("leak", c_double), ("shot", c_double), ("seed", ctypes.c_uint64),
+                ("interval", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class EnslamError(RuntimeError):
     pass
 
@@ -319,6 +324,19 @@ _SIGS = {
                                                         c_void_p, c_void_p]),
     "enslam_event_accumulate": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_double), c_void_p,
                                                c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_event_noise_bytes": (c_int64, []),
+    "enslam_event_noisy_images_count": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_void_p, POINTER(EventNoiseParams),
+                                                       c_double, c_double, c_void_p, c_void_p]),
+    "enslam_event_noisy_images_emit": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double,
+                                                      c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      POINTER(EventNoiseParams), c_void_p, c_void_p]),
+    "enslam_event_noisy_boxroom_count": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                        POINTER(EventNoiseParams), c_double, c_double, c_void_p, c_void_p]),
+    "enslam_event_noisy_boxroom_emit": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, POINTER(EventNoiseParams), c_void_p, c_void_p]),
     "enslam_vis_panels_workspace": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "enslam_vis_panels": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                          c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
@@ -355,6 +373,8 @@ def lib():
             raise EnslamError("libenslam_hip.so: enslam_frame_plan does not have the size this binding declares")
         if hasattr(handle, "enslam_event_sim_plan_bytes") and handle.enslam_event_sim_plan_bytes() != ctypes.sizeof(EventSimPlan):
             raise EnslamError("libenslam_hip.so: enslam_event_sim_plan does not have the size this binding declares")
+        if hasattr(handle, "enslam_event_noise_bytes") and handle.enslam_event_noise_bytes() != ctypes.sizeof(EventNoiseParams):
+            raise EnslamError("libenslam_hip.so: enslam_event_noise does not have the size this binding declares")
         _lib = handle
     return _lib
 

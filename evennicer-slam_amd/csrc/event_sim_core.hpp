@@ -1,6 +1,6 @@
-// The per-pixel arithmetic of the event-camera simulator, shared by event_sim.hip (count images) and event_stream.hip
-// (time-stamped events): the sensor update, the level of an image pixel and the analytic room, each written once so that
-// both files round alike.  enslam_hip.h holds the model.  The helpers are host-callable too, so that a CPU build can step
+// The per-pixel arithmetic of the event-camera simulator, shared by event_sim.hip (count images), event_stream.hip
+// (time-stamped events) and event_noise.hip (the noisy sensor): the sensor update, the level of an image pixel, the analytic
+// room, and the fraction and time of a crossing, each written once so that all files round alike.  enslam_hip.h holds the model.  The helpers are host-callable too, so that a CPU build can step
 // through one pixel.
 #pragma once
 #include <cmath>
@@ -220,6 +220,84 @@ inline int es_room_args(const enslam_event_sim_plan* plan, const double* poses, 
     for (int k = 0; k < 9; ++k) A.freq[k] = P.freq[k];
     A.has_box = P.has_box != 0;
     A.poses = poses; A.color_out = color_out; A.depth_out = depth_out;
+    return ENSLAM_OK;
+}
+
+// ---- time-stamped events: shared by event_stream.hip and event_noise.hip ------------------------------------------------------
+constexpr int64_t ES_COUNT_CAP = (int64_t)1 << 33;      // per-pixel total written by a count pass is limited to this: 2^28
+                                                        // pixels cannot overflow the int64 prefix sum, and one pixel at the
+                                                        // cap already puts the total above what emit accepts
+constexpr int64_t ES_MAX_EVENTS = 2147483647;           // 2^31 - 1
+
+struct EsStreamOut {
+    const int64_t* ends;            // [H*W] inclusive prefix sum of the count pass
+    int64_t capacity;               // events the four arrays hold
+    double t_a, t_b;
+    double* t;
+    uint16_t* x;
+    uint16_t* y;
+    uint8_t* p;
+};
+
+ES_HD int64_t es_total(const EsSensor& S) {
+    const double n = S.pos + S.neg;
+    return n >= (double)ES_COUNT_CAP ? ES_COUNT_CAP : (int64_t)n;
+}
+
+// the pixel's run [begin, end) in the stream arrays
+ES_HD void es_run(const EsStreamOut& O, int64_t o, int64_t& begin, int64_t& end) {
+    begin = o ? O.ends[o - 1] : 0;
+    end = O.ends[o];
+    if (end > O.capacity) end = O.capacity;
+    if (begin < 0) begin = 0;
+}
+
+// Event k of a sub-step crosses X_k = R +- k * C at f_k = (X_k - L_prev) / D, D = L - L_prev, limited to [0, 1] (a quotient
+// that is not a number counts as 0).
+ES_HD double es_cross_fraction(double R, double k, double c, bool up, double L_prev, double D) {
+    const double step = k * c;
+    const double X = up ? R + step : R - step;
+    double f = (X - L_prev) / D;
+    if (!(f >= 0.0)) f = 0.0;
+    if (f > 1.0) f = 1.0;
+    return f;
+}
+
+// the time of the fraction f of sub-step s (1-based) of K: t_a + (((s - 1) + f) / K) * (t_b - t_a)
+ES_HD double es_stamp(const EsStreamOut& O, int s, int K, double f) {
+    const double u = ((double)(s - 1) + f) / (double)K;
+    return O.t_a + u * (O.t_b - O.t_a);
+}
+
+ES_HD void es_put(const EsStreamOut& O, int64_t at, double t, int y, int x, bool up) {
+    O.t[at] = t;
+    O.x[at] = (uint16_t)x;
+    O.y[at] = (uint16_t)y;
+    O.p[at] = up ? (uint8_t)1 : (uint8_t)0;
+}
+
+ES_HD double es_room_level(const EsRoomArgs& A, const double* __restrict__ P, int y, int x) {
+    double col[3] = {0.0, 0.0, 0.0}, t = 0.0;
+    es_room_pixel(A, P, y, x, col, t);
+    return log(es_luminance(col[0], col[1], col[2]) + A.c.eps);
+}
+
+// what the stream entries add to the plan's checks: no first-frame mode, coordinates that fit uint16
+inline int es_stream_plan(const enslam_event_sim_plan* plan) {
+    if (!plan) return ENSLAM_EINVAL;
+    if (plan->init) return ENSLAM_EINVAL;
+    if (plan->H > 65536 || plan->W > 65536) return ENSLAM_EUNSUPPORTED;
+    return ENSLAM_OK;
+}
+
+inline int es_stream_out(const int64_t* ends, int64_t total, double t_a, double t_b, double* t, uint16_t* x, uint16_t* y,
+                         uint8_t* p, EsStreamOut& O) {
+    if (!ends || total < 0) return ENSLAM_EINVAL;
+    if (total > 0 && (!t || !x || !y || !p)) return ENSLAM_EINVAL;
+    if (!es_finite(t_a) || !es_finite(t_b) || t_b < t_a) return ENSLAM_EINVAL;
+    if (total > ES_MAX_EVENTS) return ENSLAM_EUNSUPPORTED;
+    O.ends = ends; O.capacity = total; O.t_a = t_a; O.t_b = t_b;
+    O.t = t; O.x = x; O.y = y; O.p = p;
     return ENSLAM_OK;
 }
 

@@ -25,40 +25,12 @@
 
 namespace {
 
-constexpr int64_t ES_COUNT_CAP = (int64_t)1 << 33;      // per-pixel total written by the count pass is limited to this: 2^28
-                                                        // pixels cannot overflow the int64 prefix sum, and one pixel at the
-                                                        // cap already puts the total above what emit accepts
-constexpr int64_t ES_MAX_EVENTS = 2147483647;           // 2^31 - 1
 constexpr int EA_BLOCK = 256;
 constexpr int EA_LDS_EDGES = 2048;                      // 16 KiB of float64 edges
 constexpr int64_t EA_MAX_CELLS = (int64_t)1 << 30;      // B * H * W
 
-struct EsStreamOut {
-    const int64_t* ends;            // [H*W] inclusive prefix sum of the count pass
-    int64_t capacity;               // events the four arrays hold
-    double t_a, t_b;
-    double* t;
-    uint16_t* x;
-    uint16_t* y;
-    uint8_t* p;
-};
-
-ES_HD int64_t es_total(const EsSensor& S) {
-    const double n = S.pos + S.neg;
-    return n >= (double)ES_COUNT_CAP ? ES_COUNT_CAP : (int64_t)n;
-}
-
-// the pixel's run [begin, end) in the stream arrays
-ES_HD void es_run(const EsStreamOut& O, int64_t o, int64_t& begin, int64_t& end) {
-    begin = o ? O.ends[o - 1] : 0;
-    end = O.ends[o];
-    if (end > O.capacity) end = O.capacity;
-    if (begin < 0) begin = 0;
-}
-
 // The events of one sub-step s (1-based) of K: R is L_ref before es_update, S the state after it, pos0 / neg0 the counts
-// before it.  Event k crosses X_k = R +- k * C at f_k = (X_k - L_prev) / (L - L_prev), limited to [0, 1] (a quotient that is
-// not a number counts as 0), at time t_a + (((s - 1) + f_k) / K) * (t_b - t_a).
+// before it.  Event k crosses X_k = R +- k * C at f_k (es_cross_fraction) and leaves at es_stamp of it: event_sim_core.hpp.
 ES_HD void es_emit_substep(const EsStreamOut& O, int64_t& at, int64_t end, int y, int x, int s, int K, double R,
                            const EsSensor& S, double pos0, double neg0, double cp, double cn, double L_prev, double L) {
     const double n_pos = S.pos - pos0, n_neg = S.neg - neg0;
@@ -66,16 +38,7 @@ ES_HD void es_emit_substep(const EsStreamOut& O, int64_t& at, int64_t end, int y
     const double n = up ? n_pos : n_neg, c = up ? cp : cn;
     const double D = L - L_prev;
     for (double k = 1.0; k <= n && at < end; k += 1.0) {
-        const double step = k * c;
-        const double X = up ? R + step : R - step;
-        double f = (X - L_prev) / D;
-        if (!(f >= 0.0)) f = 0.0;
-        if (f > 1.0) f = 1.0;
-        const double u = ((double)(s - 1) + f) / (double)K;
-        O.t[at] = O.t_a + u * (O.t_b - O.t_a);
-        O.x[at] = (uint16_t)x;
-        O.y[at] = (uint16_t)y;
-        O.p[at] = up ? (uint8_t)1 : (uint8_t)0;
+        es_put(O, at, es_stamp(O, s, K, es_cross_fraction(R, k, c, up, L_prev, D)), y, x, up);
         ++at;
     }
 }
@@ -113,12 +76,6 @@ ES_HD void es_image_pixel_emit(const EsImageArgs& A, const EsStreamOut& O, int y
         L_before = L;
     }
     es_store(A.c, o, S, L);
-}
-
-ES_HD double es_room_level(const EsRoomArgs& A, const double* __restrict__ P, int y, int x) {
-    double col[3] = {0.0, 0.0, 0.0}, t = 0.0;
-    es_room_pixel(A, P, y, x, col, t);
-    return log(es_luminance(col[0], col[1], col[2]) + A.c.eps);
 }
 
 // poses: [K,12], the sub-steps
@@ -174,25 +131,6 @@ __global__ __launch_bounds__(ES_BLOCK) void event_stream_boxroom_emit_kernel(EsR
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= A.c.W || y >= A.c.H) return;
     es_room_pixel_emit(A, O, y, x);
-}
-
-// what the stream entries add to the plan's checks: no first-frame mode, coordinates that fit uint16
-int es_stream_plan(const enslam_event_sim_plan* plan) {
-    if (!plan) return ENSLAM_EINVAL;
-    if (plan->init) return ENSLAM_EINVAL;
-    if (plan->H > 65536 || plan->W > 65536) return ENSLAM_EUNSUPPORTED;
-    return ENSLAM_OK;
-}
-
-int es_stream_out(const int64_t* ends, int64_t total, double t_a, double t_b, double* t, uint16_t* x, uint16_t* y, uint8_t* p,
-                  EsStreamOut& O) {
-    if (!ends || total < 0) return ENSLAM_EINVAL;
-    if (total > 0 && (!t || !x || !y || !p)) return ENSLAM_EINVAL;
-    if (!es_finite(t_a) || !es_finite(t_b) || t_b < t_a) return ENSLAM_EINVAL;
-    if (total > ES_MAX_EVENTS) return ENSLAM_EUNSUPPORTED;
-    O.ends = ends; O.capacity = total; O.t_a = t_a; O.t_b = t_b;
-    O.t = t; O.x = x; O.y = y; O.p = p;
-    return ENSLAM_OK;
 }
 
 struct EaArgs {

@@ -41,7 +41,34 @@ Linear level-crossing interpolation, as ESIM does it.  The limit is needed: over
 f reaches 1 + 2.2e-16 at one event and drops to 1.5e-16 at another, whose t_k rounds to t_a.  The stream leaves in
 pixel-major order (row-major pixels, time-ordered within a pixel) as an event_stream.EventStream.
 
-Not modelled: refractory period, leak and shot noise, bandwidth-limited pixels, learned frame interpolation."""
+Sensor noise (`EventSimulator(..., noise=EventNoise(...))`; csrc/event_noise.hip; include/enslam_hip.h states it too).  Opt-in:
+without a noise object everything above is untouched.  New state beside L_ref: t_last float64 [H,W], the time of the pixel's
+last emitted event, -inf after `reset`.  Parameters: refractory rho >= 0 (s), leak_rate lambda >= 0 (Hz), shot_rate r >= 0 (Hz
+per pixel and polarity), seed (uint64); the simulator counts the intervals since `reset` and passes the index along -- no
+generator state is stored.  With delta = (t_b - t_a) / K the host computes g = lambda * delta and q = r * delta (q > 1 is
+refused: raise K).  Per pixel with flat index o, at sub-step s = 1..K, in this order:
+
+    1 leak (v2e's rule), if lambda > 0: L_ref = L_ref - g * C_pos, the product, then the difference; under constant light
+      this yields positive events at lambda Hz
+    2 signal candidates, exactly the time-stamped events above: R = L_ref, the closed form moves L_ref and gives n
+      candidates of one polarity with X_k, f_k limited to [0, 1] and t_k in the operation order above
+    3 shot-noise candidates, if r > 0: one Philox4x32-10 block (w0..w3) with key (seed & 0xffffffff, seed >> 32) and counter
+      (o, interval, s, 0); u(w) = (w + 0.5) * 2^-32 (exact); a negative candidate exists iff u(w0) < q, at f = u(w1), a
+      positive one iff u(w2) < q, at f = u(w3); both at t = t_a + (((s - 1) + f) / K) * (t_b - t_a); they do not move L_ref
+    4 merge: the signal candidates in the order k = 1..n and the noise candidates in ascending t (on equal t the negative
+      one first), two-way: the next noise candidate leaves before the next signal candidate iff its t is smaller
+    5 refractory filter (ESIM's rule) in merged order: a candidate is emitted iff t - t_last >= rho (always for
+      t_last = -inf) and then sets t_last = t; a suppressed signal candidate has still moved L_ref
+
+The event image counts EMITTED events (saturated at 255); the stream holds them pixel-major, in merged order within a pixel.
+With rho = lambda = r = 0 image, L_ref and stream equal the noise-free ones bit for bit.  On the device a sub-step walks at most
+65536 signal candidates of a pixel; an interval beyond that is refused by the stream call (include/enslam_hip.h).  A stream
+binned by frame times (event_stream.accumulate, tools/events_to_frames.py) returns these images, with one exception: a leak
+event of a pixel whose level does not move has f = 0, at the first sub-step it carries the frame time t_a itself, and the
+accumulator's rule gives an event on an edge to the frame before.
+
+Not modelled: bandwidth-limited pixels, intensity-dependent noise rates, a reference level held in reset during
+the refractory period, learned frame interpolation."""
 import numpy as np
 import torch
 
@@ -126,6 +153,107 @@ def _stream_of(parts, W, device='cpu'):
     return EventStream(t[order], (pix % W).astype(np.uint16), (pix // W).astype(np.uint16), p[order]).to(device)
 
 
+class EventNoise:
+    """Refractory period, leak and shot noise of an EventSimulator (the module docstring holds the model).  refractory in
+    seconds, leak_rate in Hz, shot_rate in Hz per pixel and polarity, seed uint64."""
+
+    def __init__(self, refractory=0.0, leak_rate=0.0, shot_rate=0.0, seed=0):
+        self.refractory, self.leak_rate, self.shot_rate, self.seed = float(refractory), float(leak_rate), float(shot_rate), int(seed)
+        for name in ('refractory', 'leak_rate', 'shot_rate'):
+            v = getattr(self, name)
+            if not (v >= 0.0 and v < float('inf')):
+                raise EnslamError(f"EventNoise: {name} must be finite and not negative (got {v})")
+        if not 0 <= self.seed < 2 ** 64:
+            raise EnslamError(f"EventNoise: seed must fit uint64 (got {seed})")
+
+    def params(self, interval):
+        return dict(refractory=self.refractory, leak_rate=self.leak_rate, shot_rate=self.shot_rate, seed=self.seed, interval=interval)
+
+    def __repr__(self):
+        return (f"EventNoise(refractory={self.refractory}, leak_rate={self.leak_rate}, shot_rate={self.shot_rate}, "
+                f"seed={self.seed})")
+
+
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 on arrays: counter = four and key = two uint64 arrays (or ints) of 32-bit values; returns the four words
+    of the block as uint64 arrays holding 32-bit values."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(v, dtype=np.uint64) & m32 for v in counter]
+    k = [np.asarray(v, dtype=np.uint64) & m32 for v in key]
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c[0], np.uint64(_PHILOX_M1) * c[2]     # 32 x 32 bits: exact in uint64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & m32]
+        k = [(k[0] + np.uint64(_PHILOX_W0)) & m32, (k[1] + np.uint64(_PHILOX_W1)) & m32]
+    return c
+
+
+def _uniform(w):
+    return (w.astype(np.float64) + 0.5) * (1.0 / 4294967296.0)
+
+
+def _running_max(t, pix):
+    """per run of equal `pix` (sorted), the running maximum of t: the key that keeps a run in its own order in a merge"""
+    out = t.copy()
+    if out.size < 2:
+        return out
+    same = np.concatenate([[False], pix[1:] == pix[:-1]])
+    while True:
+        before = np.concatenate([out[:1], out[:-1]])
+        bad = same & (before > out)
+        if not bad.any():
+            return out
+        out[bad] = before[bad]
+
+
+def noisy_substep(s, K, t_a, t_b, ref, t_last, neg, pos, c_pos, c_neg, L_prev, L, noise, interval):
+    """Sub-step s (1-based) of K of the noisy sensor, numpy route of the model above, in place on the float64 [H,W] arrays ref,
+    t_last and the emitted counts neg / pos.  Returns (pixel int64 [n], t float64 [n], p uint8 [n]) of the emitted events in
+    pixel order, merged order within a pixel."""
+    H, W = ref.shape
+    delta = (t_b - t_a) / K
+    g, q = noise.leak_rate * delta, noise.shot_rate * delta
+    cp = np.broadcast_to(np.asarray(c_pos, dtype=np.float64), ref.shape)
+    if noise.leak_rate > 0.0:
+        ref[...] = ref - g * cp
+    R, n_pos, n_neg = ref.copy(), np.zeros_like(ref), np.zeros_like(ref)
+    sensor_update(L, ref, n_pos, n_neg, c_pos, c_neg)
+    pix, t, p = stream_substep(s, K, t_a, t_b, R, n_pos, n_neg, c_pos, c_neg, L_prev, L)
+    key, cls = _running_max(t, pix), np.zeros(pix.size, dtype=np.int64)
+    if noise.shot_rate > 0.0:
+        o = np.arange(H * W, dtype=np.uint64)
+        w = philox4x32((o, np.uint64(interval), np.uint64(s), np.uint64(0)), (noise.seed & 0xFFFFFFFF, noise.seed >> 32))
+        for exists, frac, polarity in ((w[0], w[1], 0), (w[2], w[3], 1)):
+            idx = np.nonzero(_uniform(exists) < q)[0]
+            u = ((s - 1) + _uniform(frac[idx])) / K
+            tn = t_a + u * (t_b - t_a)
+            pix, t, key = np.concatenate([pix, idx]), np.concatenate([t, tn]), np.concatenate([key, tn])
+            p = np.concatenate([p, np.full(idx.size, polarity, dtype=np.uint8)])
+            cls = np.concatenate([cls, np.full(idx.size, 1 + polarity, dtype=np.int64)])
+    order = np.lexsort((np.arange(pix.size), cls, key, pix))
+    pix, t, p = pix[order], t[order], p[order]
+    # the refractory filter is sequential within a pixel: rank j of every pixel's run at once
+    count = np.bincount(pix, minlength=H * W)
+    start = np.cumsum(count) - count
+    keep = np.zeros(pix.size, dtype=bool)
+    last, rho = t_last.reshape(-1), noise.refractory
+    live = np.nonzero(count > 0)[0]
+    j = 0
+    while live.size:
+        at = start[live] + j
+        ok = t[at] - last[live] >= rho
+        keep[at[ok]] = True
+        last[live[ok]] = t[at[ok]]
+        j += 1
+        live = live[count[live] > j]
+    pix, t, p = pix[keep], t[keep], p[keep]
+    pos += np.bincount(pix[p == 1], minlength=H * W).reshape(H, W)
+    neg += np.bincount(pix[p == 0], minlength=H * W).reshape(H, W)
+    return pix, t, p
+
+
 def _stamps(stamps):
     try:
         t_a, t_b = (float(v) for v in stamps)
@@ -203,9 +331,11 @@ class EventSimulator:
         events = sim.step_images(prev_image, cur_image)     # uint8 [H,W,2] = (-, +) on `device`
         events = sim.step_scene(room, c2w_prev, c2w_cur, cam)
 
-    device: a HIP device runs csrc/event_sim.hip, 'cpu' the numpy route of the same definition."""
+    device: a HIP device runs csrc/event_sim.hip, 'cpu' the numpy route of the same definition.
+    noise: an EventNoise switches to the noisy sensor (csrc/event_noise.hip): every step then needs `stamps`, and
+    `stream=False` on a step returns the image alone (one launch on the device)."""
 
-    def __init__(self, H, W, c_pos=0.2, c_neg=0.2, sigma_c=0.0, substeps=8, eps=1e-3, seed=0, device='cuda:0'):
+    def __init__(self, H, W, c_pos=0.2, c_neg=0.2, sigma_c=0.0, substeps=8, eps=1e-3, seed=0, device='cuda:0', noise=None):
         self.H, self.W, self.substeps, self.eps = int(H), int(W), int(substeps), float(eps)
         self.c_pos, self.c_neg, self.sigma_c, self.seed = float(c_pos), float(c_neg), float(sigma_c), int(seed)
         self.device = torch.device(device)
@@ -227,12 +357,21 @@ class EventSimulator:
             self.c_pos_map, self.c_neg_map = (torch.from_numpy(m).to(self.device) for m in maps)
         self._lut = torch.from_numpy(grey_table(self.eps)).to(self.device)
         self._ref = None
+        if noise is not None and not isinstance(noise, EventNoise):
+            raise EnslamError(f"EventSimulator: noise must be an EventNoise (got {type(noise).__name__})")
+        self.noise, self._t_last, self._interval = noise, None, 0
 
     # ---- state -------------------------------------------------------------------------------------------------------------
     @property
     def state(self):
         """L_ref, float64 [H,W] on the simulator's device (None before `reset`); the live tensor, updated in place."""
         return self._ref
+
+    @property
+    def last_event_time(self):
+        """t_last, float64 [H,W] on the simulator's device: the time of every pixel's last emitted event, -inf where there was
+        none since `reset` (None without a noise object or before `reset`); the live tensor."""
+        return self._t_last
 
     @property
     def on_device(self):
@@ -277,6 +416,9 @@ class EventSimulator:
         scene = isinstance(first, (tuple, list)) and len(first) == 3 and hasattr(first[0], 'room_lo')
         if scene:
             self._check_cam(first[2])
+        if self.noise is not None:
+            self._t_last = torch.full((self.H, self.W), float('-inf'), dtype=torch.float64, device=self.device)
+            self._interval = 0
         if not self.on_device:
             if scene:
                 room, c2w, cam = first
@@ -297,12 +439,59 @@ class EventSimulator:
         return self
 
     # ---- one interval ------------------------------------------------------------------------------------------------------
-    def step_images(self, prev, cur, host_log=False, stamps=None):
+    def _noisy_stamps(self, stamps, what):
+        if stamps is None:
+            raise EnslamError(f"EventSimulator.{what}: a simulator with noise needs stamps = (t_a, t_b): the refractory period and "
+                              "the rates are in seconds")
+        stamps = _stamps(stamps)
+        q = self.noise.shot_rate * ((stamps[1] - stamps[0]) / self.substeps)
+        if q > 1.0:
+            raise EnslamError(f"EventSimulator.{what}: shot_rate * sub-step length is {q} > 1: raise the number of sub-steps")
+        if self._interval >= 2 ** 32:
+            raise EnslamError("EventSimulator: the interval counter is uint32; reset() the simulator")
+        return stamps
+
+    def _noisy_levels(self, levels, stamps, stream):
+        """the numpy route of the noisy sensor over the K + 1 level images `levels` (the previous frame's first)"""
+        ref, t_last = self._ref.numpy(), self._t_last.numpy()
+        pos, neg = np.zeros_like(ref), np.zeros_like(ref)
+        cp, cn = self._thresholds()
+        parts = []
+        for s in range(1, self.substeps + 1):
+            parts.append(noisy_substep(s, self.substeps, stamps[0], stamps[1], ref, t_last, neg, pos, cp, cn, levels[s - 1],
+                                       levels[s], self.noise, self._interval))
+        self._interval += 1
+        events = torch.from_numpy(saturate(neg, pos))
+        return (events, _stream_of(parts, self.W)) if stream else events
+
+    def _noisy_device(self, out, stream):
+        self._interval += 1
+        return self._with_stream(out) if stream else out
+
+    def step_images(self, prev, cur, host_log=False, stamps=None, stream=True):
         """Events uint8 [H,W,2] = (-, +) between two decoded images (numpy arrays, or tensors on the device).  host_log: on a
         device, take the two level images from the host (numpy's log) instead of the kernel's -- bit-equal to the CPU route
         for RGB images too, at the price of two float64 uploads.  stamps = (t_a, t_b), the times of the two frames: returns
-        (events, EventStream) -- the same image and state, and the time-stamped events in pixel-major order."""
+        (events, EventStream) -- the same image and state, and the time-stamped events in pixel-major order.  With a noise object
+        stamps are required; stream=False then returns the image alone."""
         self._need_state()
+        if self.noise is not None:
+            stamps = self._noisy_stamps(stamps, 'step_images')
+            K = self.substeps
+            if not self.on_device:
+                La, Lb = self._host_level(prev), self._host_level(cur)
+                dL = Lb - La
+                return self._noisy_levels([La] + [La + (s / K) * dL for s in range(1, K + 1)], stamps, stream)
+            kw = dict(substeps=K, stream=stream, **self._kw())
+            if host_log:
+                levels = tuple(torch.from_numpy(self._host_level(im)).to(self.device) for im in (prev, cur))
+                return self._noisy_device(self._EF.event_noisy_images(None, None, self._ref, self._t_last, stamps,
+                                                                      self.noise.params(self._interval), levels=levels, **kw), stream)
+            a, b = self._image(prev), self._image(cur)
+            if a.shape != b.shape:
+                raise EnslamError(f"EventSimulator: the two images differ in shape ({tuple(a.shape)}, {tuple(b.shape)})")
+            return self._noisy_device(self._EF.event_noisy_images(a, b, self._ref, self._t_last, stamps,
+                                                                  self.noise.params(self._interval), lut=self._lut, **kw), stream)
         if stamps is not None:
             stamps = _stamps(stamps)
         if not self.on_device:
@@ -343,7 +532,7 @@ class EventSimulator:
         events, arrays = out
         return events, EventStream(*arrays)
 
-    def step_scene(self, room, c2w_prev, c2w_cur, cam, want_frame=False, stamps=None):
+    def step_scene(self, room, c2w_prev, c2w_cur, cam, want_frame=False, stamps=None, stream=True):
         """Events of the interval between two views of `room`; with want_frame also (color float64 [H,W,3], depth float32
         [H,W]) of c2w_cur, what room.render(c2w_cur, cam) returns.  stamps = (t_a, t_b), the times of the two views: returns
         (events, EventStream) -- the room is then rendered at c2w_prev as well, for the level the first sub-step starts from
@@ -351,6 +540,19 @@ class EventSimulator:
         self._need_state()
         self._check_cam(cam)
         poses = interpolate_poses(_pose64(c2w_prev), _pose64(c2w_cur), self.substeps)
+        if self.noise is not None:
+            if want_frame:
+                raise EnslamError("EventSimulator.step_scene: stamps and want_frame are not combined")
+            stamps = self._noisy_stamps(stamps, 'step_scene')
+            first = np.eye(4, dtype=np.float64)
+            first[:3, :] = _pose64(c2w_prev)[:3, :]
+            with_prev = np.concatenate([first[None], poses], axis=0)
+            if self.on_device:
+                return self._noisy_device(self._EF.event_noisy_boxroom(room, with_prev, cam, self._ref, self._t_last, stamps,
+                                                                       self.noise.params(self._interval), stream=stream,
+                                                                       **self._kw()), stream)
+            return self._noisy_levels([np.log(luminance(render_boxroom(room, P, cam)[0]) + self.eps) for P in with_prev], stamps,
+                                      stream)
         if stamps is not None:
             if want_frame:
                 raise EnslamError("EventSimulator.step_scene: stamps and want_frame are not combined")

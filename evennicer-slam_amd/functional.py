@@ -3123,6 +3123,136 @@ def event_stream_boxroom(room, poses, cam, state, stamps, eps=1e-3, c_pos=0.2, c
         state, H, W, stamps)
 
 
+# ------------------------------------------------------------------------------------------------
+# The noisy event sensor (csrc/event_noise.hip; event_sim.EventSimulator(noise=...) drives it)
+# ------------------------------------------------------------------------------------------------
+def event_noise_params(what, noise, substeps, stamps):
+    """The enslam_event_noise of one interval (host arithmetic only).  noise: dict with refractory (s), leak_rate (Hz),
+    shot_rate (Hz), seed, interval; g = leak_rate * delta and q = shot_rate * delta with delta = (t_b - t_a) / K."""
+    rho, lam, r = (float(noise.get(k, 0.0)) for k in ('refractory', 'leak_rate', 'shot_rate'))
+    for name, v in (('refractory', rho), ('leak_rate', lam), ('shot_rate', r)):
+        if not (v >= 0.0 and v < float('inf')):
+            raise L.EnslamError(f"{what}: {name} must be finite and not negative (got {v})")
+    delta = (stamps[1] - stamps[0]) / substeps
+    q = r * delta
+    if q > 1.0:
+        raise L.EnslamError(f"{what}: shot_rate * sub-step length is {q} > 1: raise the number of sub-steps")
+    seed, interval = int(noise.get('seed', 0)), int(noise.get('interval', 0))
+    if not (0 <= seed < 2 ** 64 and 0 <= interval < 2 ** 32):
+        raise L.EnslamError(f"{what}: seed must fit uint64 and interval uint32 (got {seed}, {interval})")
+    n = L.EventNoiseParams()
+    n.refractory, n.leak, n.shot, n.seed, n.interval, n.reserved = rho, lam * delta, q, seed, interval, 0
+    return n
+
+
+def _event_noisy_run(what, count, emit, state, t_last, H, W, stamps, stream):
+    """stream: count -> prefix sum -> one read-back of the total -> emit, returns (events, (t, x, y, p)); otherwise the one
+    launch of the count-image-only form, returns events"""
+    if H > 65536 or W > 65536:
+        raise L.EnslamError(f"{what}: event coordinates are uint16, the sensor is {H} x {W}")
+    _event_sim_tensor(what, 't_last', t_last, torch.float64, (H, W), state.device)
+    dev = state.device
+    with torch.cuda.device(dev):
+        events = torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
+        if not stream:
+            L.check(emit(events, None, 0, stamps[0], stamps[1], None, None, None, None), what + " (image)")
+            return events
+        counts = torch.empty((H, W), dtype=torch.int64, device=dev)
+        L.check(count(counts, stamps[0], stamps[1]), what + " (count)")
+        ends = torch.cumsum(counts.view(-1), 0)
+        total = int(ends[-1].item())                            # the one read-back of the interval
+        if total > 2 ** 31 - 1:
+            raise L.EnslamError(f"{what}: {total} events in one interval (at most 2^31 - 1)")
+        t = torch.empty(total, dtype=torch.float64, device=dev)
+        x, y = (torch.empty(total, dtype=torch.uint16, device=dev) for _ in range(2))
+        p = torch.empty(total, dtype=torch.uint8, device=dev)
+        L.check(emit(events, ends, total, stamps[0], stamps[1], t, x, y, p), what + " (emit)")
+    return events, (t, x, y, p)
+
+
+def event_noisy_images(prev, cur, state, t_last, stamps, noise, substeps=8, eps=1e-3, c_pos=0.2, c_neg=0.2, lut=None, levels=None,
+                       c_pos_map=None, c_neg_map=None, stream=True):
+    """One interval of the image route through the noisy sensor (enslam_event_noisy_images_*, enslam_hip.h): the arguments of
+    `event_stream_images` plus `t_last` (float64 [H,W], updated in place like `state`) and `noise` (dict: refractory,
+    leak_rate, shot_rate, seed, interval).  stream=True: (events, (t, x, y, p)) of the EMITTED events, two launches;
+    stream=False: events alone, one launch."""
+    what = "event_noisy_images"
+    if not torch.is_tensor(state):
+        raise L.EnslamError(f"{what}: state must be a tensor")
+    H, W = (int(v) for v in state.shape) if state.dim() == 2 else (0, 0)
+    _event_sim_checks(what, H, W, substeps, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, False)
+    stamps = _event_stamps(what, stamps)
+    dev = state.device
+    channels = 1
+    if levels is not None:
+        if len(levels) != 2:
+            raise L.EnslamError(f"{what}: levels must be the pair (L_prev, L_cur)")
+        for name, t in zip(('L_prev', 'L_cur'), levels):
+            _event_sim_tensor(what, name, t, torch.float64, (H, W), dev)
+        prev = cur = None
+    else:
+        if not torch.is_tensor(prev) or not torch.is_tensor(cur):
+            raise L.EnslamError(f"{what}: prev and cur must be tensors (or pass `levels`)")
+        for name, t in (('prev', prev), ('cur', cur)):
+            if t.dim() not in (2, 3) or t.shape != cur.shape:
+                raise L.EnslamError(f"{what}: prev and cur must be uint8 tensors of one shape [H,W] or [H,W,C]")
+            shape = (H, W) if t.dim() == 2 else (H, W, int(t.shape[2]))
+            if t.dim() == 3 and shape[2] not in (1, 3):
+                raise L.EnslamError(f"{what}: images must have 1 or 3 channels (got {shape[2]})")
+            _event_sim_tensor(what, name, t, torch.uint8, shape, dev)
+        channels = 3 if cur.dim() == 3 and cur.shape[2] == 3 else 1
+        if channels == 1:
+            if lut is None:
+                raise L.EnslamError(f"{what}: grey images need the host-computed table `lut` (float64 [256])")
+            _event_sim_tensor(what, 'lut', lut, torch.float64, (256,), dev)
+    plan = event_sim_plan(H, W, substeps, eps, c_pos, c_neg, channels=channels)
+    params = event_noise_params(what, noise, int(substeps), stamps)
+    la, lb = levels if levels is not None else (None, None)
+    src = (ctypes.byref(plan), _ptr(prev), _ptr(cur), _ptr(lut), _ptr(la), _ptr(lb), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state))
+    lib = L.lib()
+    return _event_noisy_run(
+        what, lambda counts, t_a, t_b: lib.enslam_event_noisy_images_count(*src, _ptr(counts), ctypes.byref(params), t_a, t_b,
+                                                                           _ptr(t_last), _stream()),
+        lambda events, ends, total, t_a, t_b, t, x, y, p: lib.enslam_event_noisy_images_emit(
+            *src, _ptr(events), _ptr(ends), total, t_a, t_b, _ptr(t), _ptr(x), _ptr(y), _ptr(p), ctypes.byref(params), _ptr(t_last),
+            _stream()),
+        state, t_last, H, W, stamps, stream)
+
+
+def event_noisy_boxroom(room, poses, cam, state, t_last, stamps, noise, eps=1e-3, c_pos=0.2, c_neg=0.2, c_pos_map=None,
+                        c_neg_map=None, stream=True):
+    """One interval of the analytic route through the noisy sensor (enslam_event_noisy_boxroom_*, enslam_hip.h): the arguments
+    of `event_stream_boxroom` (poses float64 [K+1,3|4,4], the previous frame's first) plus `t_last` and `noise` as in
+    `event_noisy_images`; both passes read all K + 1 poses."""
+    what = "event_noisy_boxroom"
+    if not torch.is_tensor(state):
+        raise L.EnslamError(f"{what}: state must be a tensor")
+    H, W = int(cam['H']), int(cam['W'])
+    dev = state.device
+    p = poses if torch.is_tensor(poses) else torch.as_tensor(poses)
+    if p.dim() != 3 or p.shape[0] < 2 or p.shape[1] not in (3, 4) or p.shape[2] != 4 or p.dtype != torch.float64:
+        raise L.EnslamError(f"{what}: poses must be float64 [K+1,3|4,4], the previous frame's first (got {p.dtype} {tuple(p.shape)})")
+    K = int(p.shape[0]) - 1
+    _event_sim_checks(what, H, W, K, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, False)
+    stamps = _event_stamps(what, stamps)
+    if torch.is_tensor(poses):
+        _require_hip(poses, f"{what}: a pose tensor")
+    if not (float(cam['fx']) != 0 and float(cam['fy']) != 0):
+        raise L.EnslamError(f"{what}: fx and fy must not be zero")
+    p = p[:, :3, :].to(dev).contiguous()
+    plan = event_sim_plan(H, W, K, eps, c_pos, c_neg, cam=cam, room=room)
+    params = event_noise_params(what, noise, K, stamps)
+    src = (ctypes.byref(plan), _ptr(p), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state))
+    lib = L.lib()
+    return _event_noisy_run(
+        what, lambda counts, t_a, t_b: lib.enslam_event_noisy_boxroom_count(*src, _ptr(counts), ctypes.byref(params), t_a, t_b,
+                                                                            _ptr(t_last), _stream()),
+        lambda events, ends, total, t_a, t_b, t, x, y, q: lib.enslam_event_noisy_boxroom_emit(
+            *src, _ptr(events), _ptr(ends), total, t_a, t_b, _ptr(t), _ptr(x), _ptr(y), _ptr(q), ctypes.byref(params), _ptr(t_last),
+            _stream()),
+        state, t_last, H, W, stamps, stream)
+
+
 def event_accumulate(t, x, y, p, edges, H, W, want_unsaturated=False):
     """Bin a stream into count images (enslam_event_accumulate, enslam_hip.h).  t float64 [N], x, y uint16 [N], p uint8 [N] on
     one HIP device, in any order; edges: B + 1 ascending float64 times (a host sequence or array).  Event t goes to bin b

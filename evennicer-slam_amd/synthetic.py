@@ -166,13 +166,15 @@ def demo_config(inp, evf, cam, device='cuda:0', env=None):
     }
 
 
-def write_demo_sequence(root, n, cam, step=0.012, yaw_deg=0.5, events=None, sim=None, stamps=None, streams=None):
+def write_demo_sequence(root, n, cam, step=0.012, yaw_deg=0.5, events=None, sim=None, stamps=None, streams=None, noise=None):
     """n frames of a BoxRoom inside the demo bound along `trajectory`, written in the Replica_event layout.
     events: None writes all-zero event images; 'simulate' fills them from `event_sim.EventSimulator.step_scene` along the
     trajectory with `sim` (default: a simulator with default parameters on the CPU, its numpy route; pass one on a HIP device
     to run the kernel, which then renders the frames as well -- one launch per frame).
     stamps (n frame times) with events = 'simulate': the intervals are simulated with time stamps and the list `streams`
     receives one event_stream.EventStream per interval (pixel-major); the frames then come from BoxRoom.render.
+    noise (an event_sim.EventNoise) with events = 'simulate': the default simulator is built with it (a `sim` passed in
+    carries its own); the noisy sensor needs `stamps`.
     Returns ((input_folder, event_folder), poses)."""
     from . import datasets as D
     from .scene import scene_bound
@@ -183,7 +185,9 @@ def write_demo_sequence(root, n, cam, step=0.012, yaw_deg=0.5, events=None, sim=
     poses = trajectory(room, n, step=step, yaw_deg=yaw_deg)
     if events == 'simulate' and sim is None:
         from .event_sim import EventSimulator
-        sim = EventSimulator(cam['H'], cam['W'], device='cpu')
+        sim = EventSimulator(cam['H'], cam['W'], device='cpu', noise=noise)
+    if events == 'simulate' and sim.noise is not None and stamps is None:
+        raise ValueError("write_demo_sequence: a simulator with noise needs the frame times `stamps`")
     frames, evs = [], []
     for i, c2w in enumerate(poses):
         if events is None:
@@ -195,10 +199,13 @@ def write_demo_sequence(root, n, cam, step=0.012, yaw_deg=0.5, events=None, sim=
             sim.reset((room, c2w.double(), cam))
         elif stamps is not None:
             col, dep = room.render(c2w.double(), cam)
-            ev, stream = sim.step_scene(room, poses[i - 1].double(), c2w.double(), cam, stamps=(stamps[i - 1], stamps[i]))
+            if streams is None and sim.noise is not None:           # the noisy sensor, images only: its one-launch form
+                ev = sim.step_scene(room, poses[i - 1].double(), c2w.double(), cam, stamps=(stamps[i - 1], stamps[i]), stream=False)
+            else:
+                ev, stream = sim.step_scene(room, poses[i - 1].double(), c2w.double(), cam, stamps=(stamps[i - 1], stamps[i]))
+                if streams is not None:
+                    streams.append(stream)
             evs.append(ev.cpu().numpy())
-            if streams is not None:
-                streams.append(stream)
         elif sim.on_device:
             ev, col, dep = sim.step_scene(room, poses[i - 1].double(), c2w.double(), cam, want_frame=True)
             evs.append(ev.cpu().numpy())

@@ -1072,6 +1072,74 @@ int enslam_event_accumulate(const double *t, const uint16_t *x, const uint16_t *
                             const double *edges_host, const double *edges, int32_t B, int32_t H, int32_t W, uint32_t *acc,
                             uint8_t *counts, uint64_t *dropped, void *stream);
 
+/* The noisy event sensor (event_sim.EventNoise, csrc/event_noise.hip): refractory period, leak and shot noise on top of the
+ * sensor and the time stamps above.  All arithmetic is float64, no fused multiply-adds.
+ *
+ * State beside L_ref: t_last float64 [H,W], the time of the pixel's last emitted event; -inf after a reset.
+ * Parameters (struct enslam_event_noise): refractory = rho >= 0 in seconds; leak = g = lambda * delta and shot = q = r * delta,
+ *   the leak rate lambda (Hz) and the shot-noise rate r (Hz per pixel and polarity) times the length of a sub-step
+ *   delta = (t_b - t_a) / K, computed by the host; seed; interval, the index of the interval since the reset, supplied by the
+ *   caller (no generator state is stored).
+ * Per pixel with flat index o = y W + x, at sub-step s = 1..K, in this order:
+ *   1 leak (v2e's rule), if g > 0: L_ref = L_ref - g * C_pos (the product, then the difference).  Under constant light this
+ *     yields positive events at lambda Hz.
+ *   2 signal candidates, exactly the events of the stream model above: R = L_ref, the closed form moves L_ref and gives n
+ *     candidates of one polarity with X_k, f_k limited to [0, 1] and t_k in the operation order stated there.
+ *   3 shot-noise candidates, if q > 0: one Philox4x32-10 block (w0, w1, w2, w3) with key (seed & 0xffffffff, seed >> 32) and
+ *     counter (o, interval, s, 0); multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 / BB67AE85.  With
+ *     u(w) = (w + 0.5) * 2^-32 (exact): a negative candidate exists iff u(w0) < q, at f = u(w1); a positive one iff u(w2) < q,
+ *     at f = u(w3); both at t = t_a + (((s - 1) + f) / K) * (t_b - t_a).  Noise candidates do not move L_ref.
+ *   4 merge: the signal candidates in the order k = 1..n and the noise candidates in ascending t (on equal t the negative
+ *     one first) are merged two-way: the next noise candidate leaves before the next signal candidate iff its t is smaller
+ *     (on equal t signal comes first).  Signal times ascend with k wherever the level moves towards the crossing, so the
+ *     merged order is ascending in t.
+ *   5 refractory filter (ESIM's rule) in merged order: a candidate is emitted iff t - t_last >= rho (always for t_last = -inf)
+ *     and then sets t_last = t.  A suppressed signal candidate has still moved L_ref.
+ * Outputs: the uint8 (-, +) image of EMITTED events saturated at 255, L_ref, t_last, and the stream of emitted events
+ * (pixel-major, merged order within a pixel).  With rho = g = q = 0 and frame times that do not go backwards the image, L_ref
+ * and the stream equal those of enslam_event_stream_* bit for bit.
+ * Limit of the device route: the walk over the candidates is serial, so a sub-step walks at most 65536 signal candidates of a
+ * pixel (256 times what the uint8 image shows; a threshold that tiny against the level change is not a sensor).  A pixel beyond
+ * that reports the count cap 2^33, so the emit entry's total refuses the interval; the count-image-only form has no count pass
+ * and cannot report it: there L_ref stays the closed form's, the image and t_last are those of the candidates walked.
+ * Not modelled: bandwidth-limited pixels, intensity-dependent noise rates, a reference level held in reset during the
+ * refractory period.
+ *
+ * One thread per pixel, no atomics, no LDS (bit-reproducible):
+ *   enslam_event_noisy_*_count: the arguments of enslam_event_stream_*_count, then noise, t_a, t_b and t_last; counts receives
+ *     the emitted events per pixel; L_ref and t_last are only read.  The boxroom entry takes K + 1 poses [K+1,12] as its emit
+ *     entry does: the refractory decision needs the time stamps, those the previous frame's level.
+ *   enslam_event_noisy_*_emit: the arguments of enslam_event_stream_*_emit, then noise and t_last; writes the runs, the image,
+ *     L_ref and t_last.  Count-image-only form: ends, t, x, y, p all NULL and total 0 -- one launch, no prefix sum, writes
+ *     the image and the two states only.
+ *   ENSLAM_EINVAL without a launch: what enslam_event_stream_* refuses, a NULL noise or t_last, refractory, leak or shot
+ *     negative or not finite, shot > 1 (raise K), t_a or t_b not finite or t_b < t_a, only some of ends, t, x, y, p given (t, x,
+ *     y, p may be NULL together beside ends while total = 0).  ENSLAM_EUNSUPPORTED as enslam_event_stream_*. */
+typedef struct enslam_event_noise {
+    double refractory;              /* rho, seconds */
+    double leak;                    /* g = leak rate * sub-step length */
+    double shot;                    /* q = shot rate * sub-step length, at most 1 */
+    uint64_t seed;
+    uint32_t interval, reserved;
+} enslam_event_noise;
+int64_t enslam_event_noise_bytes(void);              /* sizeof(enslam_event_noise): binding self-check */
+int enslam_event_noisy_images_count(const enslam_event_sim_plan *plan, const uint8_t *prev, const uint8_t *cur,
+                                    const double *lut, const double *L_prev, const double *L_cur, const double *c_pos_map,
+                                    const double *c_neg_map, const double *L_ref, int64_t *counts,
+                                    const enslam_event_noise *noise, double t_a, double t_b, const double *t_last, void *stream);
+int enslam_event_noisy_images_emit(const enslam_event_sim_plan *plan, const uint8_t *prev, const uint8_t *cur,
+                                   const double *lut, const double *L_prev, const double *L_cur, const double *c_pos_map,
+                                   const double *c_neg_map, double *L_ref, uint8_t *events, const int64_t *ends, int64_t total,
+                                   double t_a, double t_b, double *t, uint16_t *x, uint16_t *y, uint8_t *p,
+                                   const enslam_event_noise *noise, double *t_last, void *stream);
+int enslam_event_noisy_boxroom_count(const enslam_event_sim_plan *plan, const double *poses, const double *c_pos_map,
+                                     const double *c_neg_map, const double *L_ref, int64_t *counts,
+                                     const enslam_event_noise *noise, double t_a, double t_b, const double *t_last, void *stream);
+int enslam_event_noisy_boxroom_emit(const enslam_event_sim_plan *plan, const double *poses, const double *c_pos_map,
+                                    const double *c_neg_map, double *L_ref, uint8_t *events, const int64_t *ends, int64_t total,
+                                    double t_a, double t_b, double *t, uint16_t *x, uint16_t *y, uint8_t *p,
+                                    const enslam_event_noise *noise, double *t_last, void *stream);
+
 /* Per-iteration frame report (frame_vis.py, csrc/frame_report.hip): the figure of the reference's src/utils/Visualizer.py
  * as one uint8 sheet, the frame's error sums, and the mean SSIM of two images.
  *

@@ -9,7 +9,9 @@ seconds and p in {0, 1}.  STAMPS: a text file whose first field per non-comment 
 images.txt).  Every --gap-th frame is kept and each kept interval is split into --density equal parts
 (event_stream.frame_edges); one png per part is written into --out, numbered from 1 like the sequence writers do:
 event%06d.png with channels (+, -, 0) for `rpg_event` (RPG_event at density 1, RPG_event_dense above), event_frame%06d.png
-with (0, -, +) for `replica_event`.  For n kept frames that is (n - 1) * density files, what the readers assert.
+with (0, -, +) for `replica_event`.  For n kept frames that is (n - 1) * density files, what the readers assert.  An event
+whose time is exactly a frame time belongs to the part that ENDS there; a simulated stream with leak (tools/simulate_events.py
+--leak-rate) holds such events at the start of an interval, which therefore count for the frame before, not for their own.
 
 --poses traj.txt (one row-major 4x4 camera-to-world per line, one line per frame of STAMPS) with --density above 1 also
 writes traj_density{D}.txt next to it, in the format of datasets.write_rpg_event_dense_sequence: the kept frames' poses with

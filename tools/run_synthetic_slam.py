@@ -11,7 +11,9 @@ thresholds EVENT_C, default 0.2) instead of all-zero event images and sets event
 state_dict (tools/train_event_net.py) into a frozen eval-mode UNet_2heads(6, 2, 2) and hands it to the harness, which the
 event term needs; [--net-backend hip|torch] picks event.net_backend for it; [--vis DIR] keeps the tracked run's per-iteration
 figures (frame_vis.Visualizer: DIR/tracking_vis, DIR/mapping_vis; VIS_FREQ and VIS_INSIDE_FREQ, default 5 and 10, set both
-stages' vis_freq / vis_inside_freq)."""
+stages' vis_freq / vis_inside_freq); with --events simulate, [--refractory S] [--leak-rate HZ] [--shot-rate HZ] [--noise-seed N]
+switch the simulator to the noisy sensor (event_sim.EventNoise; the frame times are i / 30 s, those of
+tools/simulate_events.py's default --fps)."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -70,7 +72,8 @@ def mesh_metrics(slam, path, n_gt=200000, tsdf=False):
     return out
 
 
-def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=None, event_net=None, net_backend=None, vis=None):
+def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=None, event_net=None, net_backend=None, vis=None,
+        noise=None):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -78,9 +81,12 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=Non
         if events == 'simulate':
             from evennicer_slam_amd.event_sim import EventSimulator
             c = float(os.environ.get('EVENT_C', 0.2))
-            sim = EventSimulator(cam['H'], cam['W'], c_pos=c, c_neg=c, device=DEV)
+            sim = EventSimulator(cam['H'], cam['W'], c_pos=c, c_neg=c, device=DEV, noise=noise)
+        elif noise is not None:
+            raise SystemExit("the noise options need --events simulate")
         (inp, evf), poses = write_demo_sequence(os.path.join(tmp, 'data'), n, cam, step=float(os.environ.get('STEP', 0.012)), yaw_deg=float(os.environ.get('YAW', 0.5)),
-                                                events=events, sim=sim)
+                                                events=events, sim=sim,
+                                                stamps=None if noise is None else [i / 30.0 for i in range(n)])
         cfg = demo_config(inp, evf, cam, device=DEV, env=os.environ)
         extra = {}
         if events == 'simulate':
@@ -139,4 +145,14 @@ if __name__ == '__main__':
             del args[k:k + 2]
     if opts.get('events') not in (None, 'simulate'):
         raise SystemExit("--events takes 'simulate'")
+    noise = {}
+    for flag, key, kind in (('--refractory', 'refractory', float), ('--leak-rate', 'leak_rate', float), ('--shot-rate', 'shot_rate', float),
+                            ('--noise-seed', 'seed', int)):
+        if flag in args:
+            k = args.index(flag)
+            noise[key] = kind(args[k + 1])
+            del args[k:k + 2]
+    if any(noise.get(k, 0) > 0 for k in ('refractory', 'leak_rate', 'shot_rate')):
+        from evennicer_slam_amd.event_sim import EventNoise
+        opts['noise'] = EventNoise(**noise)
     run(int(args[0]) if args else 30, mesh_dir=mesh_dir, overlap=overlap, tsdf=tsdf, **opts)

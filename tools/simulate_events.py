@@ -5,6 +5,7 @@
     python tools/simulate_events.py --demo N --out DIR
     common: [--device cuda:0|cpu] [--c-pos C] [--c-neg C] [--sigma-c S] [--substeps K] [--eps E] [--seed N]
             [--stream OUT [--stamps FILE | --fps F]]
+            [--refractory S] [--leak-rate HZ] [--shot-rate HZ] [--noise-seed N]
 
 With a reference-format YAML chain (config.load_config; --input_folder overrides data.input_folder) the colour images of
 any sequence the readers support are read RAW -- decoded, nothing else: grey for the rpg* layouts, RGB otherwise -- and the
@@ -20,6 +21,14 @@ under --out; on a HIP device the kernel renders the frames as well.
 sub-step, event_sim.py), sorted by time: OUT ending in .npz as event_stream.EventStream.save writes it, any other name as text,
 one event per line `t x y p`.  The frame times come from --stamps (first field per non-comment line) or are i / --fps (30).
 tools/events_to_frames.py bins such a stream back into event images, at any gap or density.
+
+--refractory S, --leak-rate HZ, --shot-rate HZ (any of them above zero; --noise-seed N seeds the shot noise) switch to the
+noisy sensor (event_sim.EventNoise): refractory period in seconds, leak events at HZ under constant light, shot-noise events at
+HZ per pixel and polarity.  Its rates are in seconds, so the frame times are needed: the ones --stream uses (--stamps, or
+i / --fps), with or without --stream (without it the one-launch image-only form runs).  The event images then count the
+emitted events, and a stream written alongside bins back into exactly them (tools/events_to_frames.py) -- with one exception
+under --leak-rate: a leak event of a pixel that does not change between two frames sits exactly on the start of a sub-step, at
+the first sub-step on the frame time itself, and binning by frame times gives an event on an edge to the frame before.
 
 --device cpu runs the numpy route of the same model.  Prints one JSON line: frames, the share of pixels with an event, the
 mean counts per polarity and pixel, the share of saturated pixels, and seconds per frame (wall time of the whole loop,
@@ -37,10 +46,25 @@ DEMO_CAM = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)       # the came
 BASE_READER = {'replica_event': 'replica', 'rpg_event': 'rpg', 'rpg_event_dense': 'rpg'}
 
 
+def add_noise_options(ap):
+    ap.add_argument('--refractory', type=float, default=0.0)
+    ap.add_argument('--leak-rate', type=float, default=0.0)
+    ap.add_argument('--shot-rate', type=float, default=0.0)
+    ap.add_argument('--noise-seed', type=int, default=0)
+
+
+def noise_of(args):
+    """the EventNoise the options ask for, None when all three effects are off"""
+    if not (args.refractory > 0 or args.leak_rate > 0 or args.shot_rate > 0):
+        return None
+    from evennicer_slam_amd.event_sim import EventNoise
+    return EventNoise(refractory=args.refractory, leak_rate=args.leak_rate, shot_rate=args.shot_rate, seed=args.noise_seed)
+
+
 def simulator(args, H, W):
     from evennicer_slam_amd.event_sim import EventSimulator
     return EventSimulator(H, W, c_pos=args.c_pos, c_neg=args.c_neg, sigma_c=args.sigma_c, substeps=args.substeps, eps=args.eps,
-                          seed=args.seed, device=args.device)
+                          seed=args.seed, device=args.device, noise=noise_of(args))
 
 
 def event_stats(events):
@@ -80,6 +104,7 @@ def main(argv=None):
     ap.add_argument('--stream', default=None)
     ap.add_argument('--stamps', default=None)
     ap.add_argument('--fps', type=float, default=30.0)
+    add_noise_options(ap)
     args = ap.parse_args(argv)
     if (args.demo is None) == (args.config is None):
         ap.error("give either a CONFIG or --demo N")
@@ -91,9 +116,12 @@ def main(argv=None):
     sync = torch.cuda.synchronize if torch.device(args.device).type == 'cuda' else (lambda: None)
     out = dict(out=args.out, device=args.device)
     streams = []
+    noise = noise_of(args)
+    if noise is not None:
+        out.update(noise=dict(refractory=noise.refractory, leak_rate=noise.leak_rate, shot_rate=noise.shot_rate, seed=noise.seed))
 
     def frame_times(n):
-        if args.stream is None:
+        if args.stream is None and noise is None:
             return None
         if args.stamps is not None:
             from evennicer_slam_amd.event_stream import read_stamps
@@ -110,7 +138,7 @@ def main(argv=None):
         sim = simulator(args, DEMO_CAM['H'], DEMO_CAM['W'])
         t0 = time.perf_counter()
         (inp, evf), _ = write_demo_sequence(args.out, args.demo, DEMO_CAM, events='simulate', sim=sim,
-                                            stamps=frame_times(args.demo), streams=streams)
+                                            stamps=frame_times(args.demo), streams=streams if args.stream is not None else None)
         sync()
         seconds = time.perf_counter() - t0
         events = [D._imread_rgb(os.path.join(evf, p))[:, :, 1:] for p in sorted(os.listdir(evf))]
@@ -137,6 +165,8 @@ def main(argv=None):
             cur = raw_color(paths[i], grey)
             if times is None:
                 ev = sim.step_images(prev, cur, host_log=args.host_log).cpu().numpy()
+            elif args.stream is None:                               # the noisy sensor, images only: one launch
+                ev = sim.step_images(prev, cur, host_log=args.host_log, stamps=(times[i - 1], times[i]), stream=False).cpu().numpy()
             else:
                 ev, stream = sim.step_images(prev, cur, host_log=args.host_log, stamps=(times[i - 1], times[i]))
                 ev = ev.cpu().numpy()
