@@ -337,6 +337,14 @@ _SIGS = {
     "enslam_event_noisy_boxroom_emit": (ctypes.c_int, [POINTER(EventSimPlan), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                        c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                                        c_void_p, POINTER(EventNoiseParams), c_void_p, c_void_p]),
+    "enslam_event_pixel_counts": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_event_filter_walk": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_double, c_void_p, c_void_p, c_int64,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_event_filter_support": (ctypes.c_int, [c_int64, c_int32, c_int32, c_int32, c_double, c_void_p, c_int64, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "enslam_event_filter_compact": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "enslam_vis_panels_workspace": (ctypes.c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "enslam_vis_panels": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                          c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),

@@ -106,7 +106,10 @@ class BaseDataset(torch.utils.data.Dataset):
         and `data.frame_stamps` (a text file whose first field per non-comment line is a frame time).  With both set the
         event image of an item is accumulated from the stream (event_stream.accumulate: the HIP kernel on a HIP device,
         numpy on the CPU) instead of read from a png; it is built as the uint8 [H,W,3] array the png would decode to, at the
-        size of the raw colour frame, so everything behind the decode is shared.  Returns False when neither key is set."""
+        size of the raw colour frame, so everything behind the decode is shared.  Returns False when neither key is set.
+        `data.event_filter` (opt-in, honoured only together with these two): a mapping with any of the keys refractory,
+        support_dt (seconds), hot_rate (Hz) and hot_max (events); the time-sorted stream is denoised once
+        (event_filter.filter_from_options) before it is cut into frames, and the counters are kept in `event_filter_stats`."""
         path, stamps = cfg['data'].get('event_stream'), cfg['data'].get('frame_stamps')
         self._stream = None
         if path is None and stamps is None:
@@ -119,6 +122,17 @@ class BaseDataset(torch.utils.data.Dataset):
         self._edges = ES.frame_edges(times[:self.n_img], 1, density)
         dev = self.device if torch.device(self.device).type == 'cuda' else 'cpu'
         self._stream = ES.load_stream(path, device=dev).time_sorted()
+        self.event_filter_stats = None
+        opts = cfg['data'].get('event_filter')
+        if opts is not None:                                        # opt-in: denoise the stream once, before the cuts are taken
+            unknown = set(opts) - {'refractory', 'support_dt', 'hot_rate', 'hot_max'}
+            if unknown:
+                raise ValueError(f"data.event_filter: unknown keys {sorted(unknown)} (refractory, support_dt, hot_rate, hot_max)")
+            from . import event_filter as EFI
+            from PIL import Image
+            with Image.open(self.color_paths[0]) as im:
+                W, H = im.size
+            self._stream, self.event_filter_stats = EFI.filter_from_options(self._stream, H, W, **opts)
         # events of bin b are the slice [cuts[b], cuts[b + 1]) of the sorted stream: edges[b] < t <= edges[b + 1]
         self._cuts = torch.searchsorted(self._stream.t, torch.from_numpy(self._edges).to(dev), right=True).tolist()
         self.event_paths = None

@@ -3308,6 +3308,137 @@ def event_accumulate(t, x, y, p, edges, H, W, want_unsaturated=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# Event-stream denoising (csrc/event_filter.hip; event_filter.EventFilter and event_filter.hot_pixels drive it)
+# ------------------------------------------------------------------------------------------------
+EVENT_CLASSES = ('kept', 'sensor', 'time', 'hot', 'refractory', 'unsupported')      # ENSLAM_EVENT_*: the value is the index
+EVENT_NOT_TIME_ORDERED, EVENT_NOT_PIXEL_MAJOR = 1, 2
+EVENT_FILTER_MAX_PIXELS = 1 << 28
+
+
+def _event_arrays(what, t, x, y, p):
+    for name, a, dtype in (('t', t, torch.float64), ('x', x, torch.uint16), ('y', y, torch.uint16), ('p', p, torch.uint8)):
+        if not torch.is_tensor(a):
+            raise L.EnslamError(f"{what}: {name} must be a tensor (got {type(a).__name__})")
+        _require_hip(a, f"{what}: {name}")
+        if a.dtype != dtype or a.dim() != 1 or a.shape != t.shape or not a.is_contiguous() or a.device != t.device:
+            raise L.EnslamError(f"{what}: {name} must be a contiguous {dtype} tensor [N] on the device of t (got {a.dtype} "
+                                f"{tuple(a.shape)} on {a.device})")
+    if int(t.shape[0]) > 2147483647:
+        raise L.EnslamError(f"{what}: at most 2^31 - 1 events per call (got {int(t.shape[0])})")
+
+
+def _event_sensor(what, H, W):
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or H > 65536 or W > 65536 or H * W > EVENT_FILTER_MAX_PIXELS:
+        raise L.EnslamError(f"{what}: the sensor must have 1..65536 rows and columns and at most 2^28 pixels (got {H} x {W})")
+    return H, W
+
+
+def _event_plane(what, name, a, dtype, H, W, dev):
+    if not torch.is_tensor(a) or a.dtype != dtype or tuple(a.shape) != (H, W) or a.device != dev or not a.is_contiguous():
+        raise L.EnslamError(f"{what}: {name} must be a contiguous {dtype} tensor [{H},{W}] on {dev} (got "
+                            f"{(a.dtype, tuple(a.shape), a.device) if torch.is_tensor(a) else type(a).__name__})")
+
+
+def event_pixel_counts(t, x, y, p, H, W, hot_mask=None):
+    """Stage 0 of the event filter (enslam_event_pixel_counts, enslam_hip.h) on one HIP device: (cls uint8 [N], pix int32 [N],
+    counts int32 [H,W], flags int).  cls holds the classes SENSOR / TIME / HOT or 0, pix the flat pixel index (-1 outside the
+    sensor), counts the events per pixel that are neither SENSOR nor TIME, flags the bits EVENT_NOT_TIME_ORDERED and
+    EVENT_NOT_PIXEL_MAJOR (one read-back).  hot_mask: uint8 [H,W] on the device or None."""
+    what = "event_pixel_counts"
+    _event_arrays(what, t, x, y, p)
+    H, W = _event_sensor(what, H, W)
+    dev, N = t.device, int(t.shape[0])
+    if hot_mask is not None:
+        _event_plane(what, 'hot_mask', hot_mask, torch.uint8, H, W, dev)
+    with torch.cuda.device(dev):
+        cls = torch.empty(N, dtype=torch.uint8, device=dev)
+        pix = torch.empty(N, dtype=torch.int32, device=dev)
+        counts = torch.empty((H, W), dtype=torch.int32, device=dev)
+        flags = torch.empty(1, dtype=torch.int32, device=dev)
+        L.check(L.lib().enslam_event_pixel_counts(_ptr(t), _ptr(x), _ptr(y), N, H, W, _ptr(hot_mask), _ptr(cls), _ptr(pix),
+                                                  _ptr(counts), _ptr(flags), _stream()), "enslam_event_pixel_counts")
+        return cls, pix, counts, int(flags.item())
+
+
+def event_filter_order(t, cls, pix, counts, flags, hot_mask=None):
+    """The ordering plumbing of the event filter, torch only: (order int32 [n_live], starts int64 [H W + 1], path).  order lists
+    the live events (cls == 0) by (pixel, t, stream position); no sort where the stream is pixel-major already
+    (path 'pixel_major'), one stable sort on the pixel where it is time-ordered ('time_ordered'), else a stable sort on t and
+    one on the pixel ('unordered').  starts: the exclusive prefix sum of the live events per pixel."""
+    idx = torch.nonzero(cls == 0).squeeze(1)
+    if not flags & EVENT_NOT_PIXEL_MAJOR:
+        order, path = idx, 'pixel_major'
+    elif not flags & EVENT_NOT_TIME_ORDERED:
+        order, path = idx[torch.sort(pix[idx], stable=True).indices], 'time_ordered'
+    else:
+        by_t = idx[torch.sort(t[idx], stable=True).indices]
+        order, path = by_t[torch.sort(pix[by_t], stable=True).indices], 'unordered'
+    live = counts if hot_mask is None else counts.masked_fill(hot_mask != 0, 0)
+    starts = torch.zeros(live.numel() + 1, dtype=torch.int64, device=counts.device)
+    torch.cumsum(live.reshape(-1), 0, dtype=torch.int64, out=starts[1:])
+    return order.to(torch.int32), starts, path
+
+
+def event_filter_stages(t, x, y, p, H, W, cls, pix, order, starts, t_last, t_seen, refractory=0.0, support_dt=None, mark=None):
+    """Stages 1 and 2 and the compaction (enslam_event_filter_walk / _support / _compact) after event_pixel_counts and
+    event_filter_order.  cls is completed in place (REFRACTORY, UNSUPPORTED), t_last and t_seen (float64 [H,W]) are updated in
+    place.  Returns ((t, x, y, p) of the kept events in stream order, n_out).  mark: called with 'walk', 'support' and
+    'compact' after the calls of each stage were enqueued (tools/bench_event_filter.py records device events there)."""
+    what = "event_filter_stages"
+    _event_arrays(what, t, x, y, p)
+    H, W = _event_sensor(what, H, W)
+    dev, N = t.device, int(t.shape[0])
+    rho, dt = float(refractory), (0.0 if support_dt is None else float(support_dt))
+    if not (0.0 <= rho < float('inf')) or not (0.0 <= dt < float('inf')):
+        raise L.EnslamError(f"{what}: refractory and support_dt must be finite and not negative (got {refractory}, {support_dt})")
+    _event_plane(what, 't_last', t_last, torch.float64, H, W, dev)
+    _event_plane(what, 't_seen', t_seen, torch.float64, H, W, dev)
+    for name, a, dtype, n in (('cls', cls, torch.uint8, N), ('pix', pix, torch.int32, N), ('order', order, torch.int32, None),
+                              ('starts', starts, torch.int64, H * W + 1)):
+        if not torch.is_tensor(a) or a.dtype != dtype or a.dim() != 1 or a.device != dev or not a.is_contiguous() or \
+                (n is not None and int(a.shape[0]) != n):
+            raise L.EnslamError(f"{what}: {name} must be a contiguous {dtype} tensor" + (f" [{n}]" if n is not None else "") + f" on {dev}")
+    n_live = int(order.shape[0])
+    if n_live > N:
+        raise L.EnslamError(f"{what}: order lists {n_live} events of {N}")
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        s_times = torch.empty(n_live, dtype=torch.float64, device=dev)
+        s_event = torch.empty(n_live, dtype=torch.int32, device=dev)
+        s_count = torch.empty(H * W, dtype=torch.int32, device=dev)
+        L.check(lib.enslam_event_filter_walk(_ptr(t), N, H, W, rho, _ptr(pix), _ptr(order), n_live, _ptr(starts), _ptr(cls),
+                                             _ptr(t_last), _ptr(s_times), _ptr(s_event), _ptr(s_count), _stream()),
+                "enslam_event_filter_walk")
+        if mark is not None:
+            mark('walk')
+        L.check(lib.enslam_event_filter_support(N, H, W, 0 if support_dt is None else 1, dt, _ptr(pix), n_live, _ptr(starts),
+                                                _ptr(cls), _ptr(t_last), _ptr(t_seen), _ptr(s_times), _ptr(s_event),
+                                                _ptr(s_count), _stream()), "enslam_event_filter_support")
+        if mark is not None:
+            mark('support')
+        ends = torch.cumsum(cls == 0, 0, dtype=torch.int64)
+        n_out = int(ends[-1].item()) if N else 0
+        out = (torch.empty(n_out, dtype=torch.float64, device=dev), torch.empty(n_out, dtype=torch.uint16, device=dev),
+               torch.empty(n_out, dtype=torch.uint16, device=dev), torch.empty(n_out, dtype=torch.uint8, device=dev))
+        L.check(lib.enslam_event_filter_compact(_ptr(t), _ptr(x), _ptr(y), _ptr(p), N, _ptr(cls), _ptr(ends), n_out,
+                                                *(_ptr(a) for a in out), _stream()), "enslam_event_filter_compact")
+        if mark is not None:
+            mark('compact')
+    return out, n_out
+
+
+def event_class_counters(cls):
+    """The counters of one filter call from its class array (uint8 [N], any device): dict n_in, sensor, time, hot, refractory,
+    unsupported, n_out."""
+    n = torch.bincount(cls.to(torch.int64), minlength=len(EVENT_CLASSES)).tolist() if cls.numel() else [0] * len(EVENT_CLASSES)
+    out = dict(n_in=int(cls.numel()))
+    out.update({name: int(n[k]) for k, name in enumerate(EVENT_CLASSES) if k})
+    out['n_out'] = int(n[0])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # Frame report (csrc/frame_report.hip; frame_vis.Visualizer and frame_vis.render_metrics drive it)
 # ------------------------------------------------------------------------------------------------
 SSIM_TILE = (16, 32)                    # ENSLAM_SSIM_TILE_H, ENSLAM_SSIM_TILE_W: output pixels of one workgroup

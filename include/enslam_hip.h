@@ -1140,6 +1140,95 @@ int enslam_event_noisy_boxroom_emit(const enslam_event_sim_plan *plan, const dou
                                     double t_a, double t_b, double *t, uint16_t *x, uint16_t *y, uint8_t *p,
                                     const enslam_event_noise *noise, double *t_last, void *stream);
 
+/* Event-stream denoising (event_filter.py, csrc/event_filter.hip): hot-pixel mask, refractory filter and background-activity
+ * (neighbour-support) filter between a stream and the accumulator above.  All arithmetic is float64 comparisons and one
+ * float64 subtraction: every result is exact, and the same on every route.
+ *
+ * Stream: the struct-of-arrays above (t float64, x, y uint16, p uint8), N events i = 0..N-1 in stream order.  Sensor H x W,
+ *   flat index o = y W + x.
+ * State, carried between calls, all -inf after a reset:
+ *   t_last float64 [H,W]  the time of the pixel's last event that passed the refractory stage (the simulator's t_last)
+ *   t_seen float64 [H,W]  the largest time of the pixel's events that passed stages 0 and 1
+ * Parameters: rho >= 0, the refractory period in seconds; support on or off with dt >= 0, the support window in seconds
+ *   (dt = 0 is meaningful: only equal-time neighbours support); optionally hot_mask uint8 [H,W].
+ *
+ * One call filters one chunk.  Every event gets exactly one class, the first that applies (ENSLAM_EVENT_* below, 0 = kept):
+ *   Stage 0, classification.  SENSOR: x >= W or y >= H, decided before any address is formed and before the time is looked
+ *     at.  TIME: t is not finite (NaN, +inf, -inf).  HOT: hot_mask[o] != 0.  Otherwise the event is live.
+ *   Stage 1, refractory (ESIM's rule, the noisy sensor's expression).  The live events of a pixel are taken in the order of
+ *     (t, i): time first, stream position on equal times.  An event passes iff t - t_last[o] >= rho (with t_last = -inf the
+ *     difference is +inf: it passes) and then sets t_last[o] = t; otherwise its class is REFRACTORY.  Polarity plays no part.
+ *     With rho = 0 the stage removes nothing and still maintains t_last.  The events that passed are called S.
+ *   Stage 2, support (non-recursive background-activity filter), only when support is on.  An S-event at (x, y, t) is kept iff
+ *     a supporting time t' exists for one of the up to eight pixels (x + dx, y + dy), (dx, dy) != (0, 0), that lie inside the
+ *     sensor: t' <= t and t - t' <= dt, evaluated exactly so, where t' is the time of an S-event of that neighbour in this
+ *     chunk or the carried t_seen of that neighbour (the value before this call).  Without such a t' the class is UNSUPPORTED.
+ *     Equal-time neighbours support each other.  HOT, REFRACTORY, SENSOR and TIME events support nobody.  An S-event that
+ *     ends up UNSUPPORTED still supports others (the classical filter writes every event's time stamp; it also keeps the
+ *     stage parallel).  A pixel never supports itself.  Neighbours are spatial: (W-1, y) and (0, y+1) are adjacent in memory
+ *     and are NOT neighbours.  t - t' is monotone in t', so only the largest t' <= t of each neighbour needs the test: one
+ *     binary search per neighbour.
+ *   Afterwards t_seen[o] = max(t_seen[o], the largest S time at o).
+ * Output: the events of class 0 in stream order (the input arrays are untouched), the class array uint8 [N], and the counters
+ *   n_in, sensor, time, hot, refractory, unsupported, n_out.
+ * Chunks.  PRECONDITION: successive calls ascend in time -- the smallest live time of a chunk is >= the largest live time of
+ *   all chunks since the reset (event_filter.EventFilter checks it and refuses).  The support kernel still tests
+ *   t_seen <= t, so a violation has a defined, memory-safe result.  A stream filtered in several chunks gives exactly the
+ *   one-call result whenever no time value is shared across a chunk boundary.  The one exception: an event at exactly the
+ *   boundary time in the earlier chunk whose only support would be an equal-time event of the later chunk is UNSUPPORTED
+ *   (the later one is supported by it, through t_seen).
+ * Hot pixels are learned separately: counts[o] is the number of events of the pixel that are neither SENSOR nor TIME
+ *   (integer atomics: independent of the order), and a pixel is hot iff counts[o] > max_events.
+ *
+ * Ordering is the caller's (torch.sort(stable=True) and torch.cumsum in functional.event_filter): `order` (device int32
+ *   [n_live]) lists the live events by (o, t, i) and `starts` (device int64 [H W + 1]) is the exclusive prefix sum of the live
+ *   events per pixel, so pixel o owns order[starts[o] .. starts[o+1]).  The entries are memory-safe whatever the two hold: an
+ *   index outside [0, N), or of an event that is not live or not of that pixel, is skipped; run bounds are clamped to
+ *   [0, n_live]; no load or store leaves an array.
+ *
+ * enslam_event_pixel_counts: stage 0.  One thread per event.  cls (device uint8 [N]) receives the class, pix (device int32 [N])
+ *   the flat index o (-1 for SENSOR), counts (device int32 [H,W], zeroed here) the counts above, flags (device uint32 [1],
+ *   zeroed here) the bits ENSLAM_EVENT_NOT_TIME_ORDERED -- some live t is smaller than the previous live event's -- and
+ *   ENSLAM_EVENT_NOT_PIXEL_MAJOR -- some live (o, t) is lexicographically smaller than the previous live event's; the
+ *   simulator emits pixel-major streams.  A live event separated from the previous live one by more than 32 events that are
+ *   not live sets both bits (a clear bit always guarantees the order; a set bit only costs a sort).  hot_mask may be NULL: the
+ *   same entry serves hot-pixel learning.  Two memsets, and one launch when N > 0.
+ * enslam_event_filter_walk: stage 1.  One thread per pixel over its run, linear in the run.  Writes REFRACTORY into cls,
+ *   t_last, and the workspace of stage 2: s_times (device float64 [n_live]) and s_event (device int32 [n_live]) hold the times
+ *   and stream positions of the pixel's S-events compactly at the front of its run (unused slots of s_event are -1), s_count
+ *   (device int32 [H,W]) their number.  One memset and one launch.
+ * enslam_event_filter_support: stage 2 when `support` != 0 -- one thread per S-event, up to eight binary searches in the
+ *   neighbours' compact runs, then the neighbours' t_seen; writes UNSUPPORTED into cls -- and then, in a launch of its own so
+ *   that stage 2 reads the old values, the update of t_seen.  Call it with support = 0 as well: the state needs it.
+ * enslam_event_filter_compact: `ends` (device int64 [N]) is the INCLUSIVE prefix sum of (cls == 0) in stream order and n_out
+ *   its last element, the capacity of the outputs (which may be NULL when n_out = 0).  One thread per event; a kept event
+ *   goes to slot ends[i] - 1, a slot outside [0, n_out) is skipped.  No launch when N = 0 or n_out = 0.
+ * No float atomics anywhere: two runs give the same bits.
+ * ENSLAM_EINVAL without a launch: a NULL counts, flags, starts, t_last, t_seen or s_count; N < 0; a NULL stream array, cls,
+ *   pix or ends with N > 0; a NULL order, s_times or s_event with n_live > 0; a NULL output with n_out > 0; n_live or n_out
+ *   outside [0, N]; H or W <= 0; rho or dt negative or not finite; an array not aligned to its element size.
+ *   ENSLAM_EUNSUPPORTED: N above 2^31 - 1, H or W above 65536, more than 2^28 pixels. */
+#define ENSLAM_EVENT_KEPT 0
+#define ENSLAM_EVENT_SENSOR 1
+#define ENSLAM_EVENT_TIME 2
+#define ENSLAM_EVENT_HOT 3
+#define ENSLAM_EVENT_REFRACTORY 4
+#define ENSLAM_EVENT_UNSUPPORTED 5
+#define ENSLAM_EVENT_NOT_TIME_ORDERED 1u
+#define ENSLAM_EVENT_NOT_PIXEL_MAJOR 2u
+int enslam_event_pixel_counts(const double *t, const uint16_t *x, const uint16_t *y, int64_t N, int32_t H, int32_t W,
+                              const uint8_t *hot_mask, uint8_t *cls, int32_t *pix, int32_t *counts, uint32_t *flags,
+                              void *stream);
+int enslam_event_filter_walk(const double *t, int64_t N, int32_t H, int32_t W, double rho, const int32_t *pix,
+                             const int32_t *order, int64_t n_live, const int64_t *starts, uint8_t *cls, double *t_last,
+                             double *s_times, int32_t *s_event, int32_t *s_count, void *stream);
+int enslam_event_filter_support(int64_t N, int32_t H, int32_t W, int32_t support, double dt, const int32_t *pix,
+                                int64_t n_live, const int64_t *starts, uint8_t *cls, const double *t_last, double *t_seen,
+                                const double *s_times, const int32_t *s_event, const int32_t *s_count, void *stream);
+int enslam_event_filter_compact(const double *t, const uint16_t *x, const uint16_t *y, const uint8_t *p, int64_t N,
+                                const uint8_t *cls, const int64_t *ends, int64_t n_out, double *t_out, uint16_t *x_out,
+                                uint16_t *y_out, uint8_t *p_out, void *stream);
+
 /* Per-iteration frame report (frame_vis.py, csrc/frame_report.hip): the figure of the reference's src/utils/Visualizer.py
  * as one uint8 sheet, the frame's error sums, and the mean SSIM of two images.
  *

@@ -3,6 +3,7 @@
     python tools/events_to_frames.py EVENTS STAMPS --out DIR --height H --width W
                                      [--gap G] [--density D] [--layout rpg_event|replica_event]
                                      [--poses traj.txt] [--device cuda:0|cpu]
+                                     [--refractory S] [--support-dt S] [--hot-rate HZ | --hot-max N]
 
 EVENTS: a stream, `.npz` (event_stream.EventStream.save) or the RPG / DAVIS text layout, one event per line `t x y p` with t in
 seconds and p in {0, 1}.  STAMPS: a text file whose first field per non-comment line is a frame time (the recordings'
@@ -17,7 +18,12 @@ whose time is exactly a frame time belongs to the part that ENDS there; a simula
 writes traj_density{D}.txt next to it, in the format of datasets.write_rpg_event_dense_sequence: the kept frames' poses with
 density - 1 poses interpolated in between (event_sim.interpolate_poses), (n - 1) * density + 1 lines.
 
---device cpu bins with numpy under the same rule.  Prints one JSON line: events read, binned, dropped by time, dropped by
+--refractory S, --support-dt S, --hot-rate HZ / --hot-max N (all opt-in) denoise the stream before it is binned
+(event_filter.py: refractory filter, neighbour-support filter, hot-pixel mask).  With a hot flag the mask is learned from the
+whole stream first (a pixel is hot above N events, or above HZ times the stream's duration); then the stream is filtered in
+one call, and the counters join the JSON line as `filter`; `events_read` and the drop counts then refer to the filtered stream.
+
+--device cpu bins (and filters) with numpy under the same rules.  Prints one JSON line: events read, binned, dropped by time, dropped by
 sensor, saturated pixels (pixel-polarity counts above 255), files written."""
 import argparse
 import json
@@ -51,6 +57,11 @@ def main(argv=None):
     ap.add_argument('--layout', choices=('rpg_event', 'replica_event'), default='rpg_event')
     ap.add_argument('--poses', default=None)
     ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--refractory', type=float, default=None, metavar='S')
+    ap.add_argument('--support-dt', type=float, default=None, metavar='S')
+    hot = ap.add_mutually_exclusive_group()
+    hot.add_argument('--hot-rate', type=float, default=None, metavar='HZ')
+    hot.add_argument('--hot-max', type=int, default=None, metavar='N')
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -61,6 +72,10 @@ def main(argv=None):
     stamps = ES.read_stamps(args.stamps)
     edges = ES.frame_edges(stamps, args.gap, args.density)
     stream = ES.load_stream(args.events, device=args.device)
+    filter_stats = None
+    if any(v is not None for v in (args.refractory, args.support_dt, args.hot_rate, args.hot_max)):
+        from evennicer_slam_amd import event_filter as EFI
+        stream, filter_stats = EFI.filter_from_options(stream, H, W, args.refractory, args.support_dt, args.hot_rate, args.hot_max)
     os.makedirs(args.out, exist_ok=True)
     B = len(edges) - 1
     binned = saturated = 0
@@ -81,6 +96,8 @@ def main(argv=None):
     out = dict(out=args.out, layout=args.layout, gap=args.gap, density=args.density, frames_kept=(B // args.density) + 1,
                events_read=len(stream), events_binned=binned, dropped_by_time=len(stream) - (sensor or 0) - binned,
                dropped_by_sensor=sensor or 0, saturated_pixels=saturated, files_written=B, device=args.device)
+    if filter_stats is not None:
+        out['filter'] = filter_stats
     assert calls == 0 or missed - (calls - 1) * (len(stream) - (sensor or 0)) == out['dropped_by_time']
     if args.poses is not None and args.density > 1:
         with open(args.poses, 'r') as f:
