@@ -1,20 +1,20 @@
 // The noisy event sensor (enslam_event_noisy_*; enslam_hip.h holds the model): refractory period (ESIM's rule), leak (v2e's
 // rule) and shot noise on top of the sensor of event_sim.hip and the time stamps of event_stream.hip.
 //
-// One thread per pixel on the 64 x 4 tile of event_sim.hip.  A pixel walks its sub-steps; at each it leaks, runs the closed
-// form es_update (the one event_sim.hip calls), draws its at most two shot-noise candidates from one Philox4x32-10 block
-// keyed by (seed) and counted by (pixel, interval, sub-step, 0), and then walks the signal candidates k = 1..n in order with
-// the noise candidates held in registers and interleaved where their times fall; every candidate passes the refractory
-// filter t - t_last >= rho.  The fraction and the time of a candidate are es_cross_fraction / es_stamp of
-// event_sim_core.hpp, the ones event_stream.hip calls.  en_substep is one function templated on "count only" or "emit", so
-// both passes decide alike (a sub-step walks at most EN_WALK_CAP candidates; a pixel beyond reports the count cap, which the
-// emit entry's total refuses); three kernels per route instantiate it:
+// One more pass of the kernel of event_sim_core.hpp (one thread per pixel on its 64 x 4 tile, either source).  A pixel walks
+// its sub-steps; at each it leaks, runs the closed form es_update (the one event_sim.hip calls), draws its at most two
+// shot-noise candidates from one Philox4x32-10 block keyed by (seed) and counted by (pixel, interval, sub-step, 0), and then
+// walks the signal candidates k = 1..n in order with the noise candidates held in registers and interleaved where their times
+// fall; every candidate passes the refractory filter t - t_last >= rho.  The fraction and the time of a candidate are
+// es_cross_fraction / es_stamp of event_sim_core.hpp, the ones event_stream.hip calls.  en_substep is one function templated
+// on "count only" or "emit", so both passes decide alike (a sub-step walks at most EN_WALK_CAP candidates; a pixel beyond
+// reports the count cap, which the emit entry's total refuses); EnPass<MODE> wraps it, three instances per source:
 //   count  reads both states, writes the emitted total per pixel (int64)
 //   image  one launch: writes the uint8 image of emitted events and both states, no stream
 //   emit   as image, and the pixel's run at its offset; every store is guarded by the end of the run and by the capacity
-// No LDS (group segment 0 in all six kernels), no atomics, no cross-lane traffic: two runs are bit-identical.  Philox is
-// 32-bit integer arithmetic (__umulhi and the low product); with q = 0 the block is skipped by a branch on a kernel argument, uniform across the launch.  No local array
-// is indexed dynamically, so nothing goes to scratch.
+// No LDS (group segment 0 in all six instances), no atomics, no cross-lane traffic: two runs are bit-identical.  Philox is
+// 32-bit integer arithmetic (__umulhi and the low product); with q = 0 the block is skipped by a branch on a kernel argument,
+// uniform across the launch.  No local array is indexed dynamically, so nothing goes to scratch.
 #include "../../include/enslam_hip.h"
 #include "common.hpp"
 
@@ -131,70 +131,30 @@ ES_HD void en_substep(const EnArgs& N, const EsStreamOut& O, EnPixel& P, int64_t
 enum { EN_COUNT = 0, EN_IMAGE = 1, EN_EMIT = 2 };
 
 template <int MODE>
-ES_HD void en_begin(const EsCommon& C, const EnArgs& N, const EsStreamOut& O, int64_t o, EnPixel& P, double& cp, double& cn) {
-    es_load(C, o, P.S, cp, cn);
-    P.t_last = N.t_last_in[o];
-    P.at = 0; P.end = 0; P.over = false;
-    if (MODE == EN_EMIT) es_run(O, o, P.at, P.end);
-}
-
-template <int MODE>
-ES_HD void en_end(const EsCommon& C, const EnArgs& N, int64_t* counts, int64_t o, const EnPixel& P, double L_last) {
-    if (MODE == EN_COUNT) {
-        counts[o] = P.over ? ES_COUNT_CAP : es_total(P.S);
-    } else {
-        es_store(C, o, P.S, L_last);
-        N.t_last_out[o] = P.t_last;
+struct EnPass {
+    static constexpr bool STAMPS = true, FRAME = false;
+    using State = EnPixel;
+    EnArgs N;
+    EsStreamOut O;
+    int64_t* counts;                // [H,W] (count) or NULL
+    ES_HD void begin(const EsCommon& C, int64_t o, State& P, double& cp, double& cn) const {
+        es_load(C, o, P.S, cp, cn);
+        P.t_last = N.t_last_in[o];
+        P.at = 0; P.end = 0; P.over = false;
+        if (MODE == EN_EMIT) es_run(O, o, P.at, P.end);
     }
-}
-
-template <int MODE>
-ES_HD void en_image_pixel(const EsImageArgs& A, const EnArgs& N, const EsStreamOut& O, int64_t* counts, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    const double La = A.L_prev ? A.L_prev[o] : es_image_level(A, A.prev, o);
-    const double Lb = A.L_cur ? A.L_cur[o] : es_image_level(A, A.cur, o);
-    EnPixel P;
-    double cp, cn, L = Lb, L_before = La;
-    en_begin<MODE>(A.c, N, O, o, P, cp, cn);
-    const double dL = Lb - La;
-    for (int s = 1; s <= A.c.K; ++s) {
-        L = La + ((double)s / (double)A.c.K) * dL;
-        en_substep<MODE == EN_EMIT>(N, O, P, o, y, x, s, A.c.K, cp, cn, L_before, L);
-        L_before = L;
+    ES_HD void substep(const EsCommon& C, State& P, int64_t o, int y, int x, int s, double cp, double cn, double L_prev, double L) const {
+        en_substep<MODE == EN_EMIT>(N, O, P, o, y, x, s, C.K, cp, cn, L_prev, L);
     }
-    en_end<MODE>(A.c, N, counts, o, P, L);
-}
-
-// poses: [K+1,12], row 0 the previous frame's (rendered for L_prev only), rows 1..K the sub-steps
-template <int MODE>
-ES_HD void en_room_pixel(const EsRoomArgs& A, const EnArgs& N, const EsStreamOut& O, int64_t* counts, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    EnPixel P;
-    double cp, cn;
-    en_begin<MODE>(A.c, N, O, o, P, cp, cn);
-    double L_before = es_room_level(A, A.poses, y, x), L = L_before;
-#pragma clang loop unroll(disable)
-    for (int s = 1; s <= A.c.K; ++s) {
-        L = es_room_level(A, A.poses + 12 * s, y, x);
-        en_substep<MODE == EN_EMIT>(N, O, P, o, y, x, s, A.c.K, cp, cn, L_before, L);
-        L_before = L;
+    ES_HD void end(const EsCommon& C, int64_t o, const State& P, double L_last) const {
+        if (MODE == EN_COUNT) {
+            counts[o] = P.over ? ES_COUNT_CAP : es_total(P.S);
+        } else {
+            es_store(C, o, P.S, L_last);
+            N.t_last_out[o] = P.t_last;
+        }
     }
-    en_end<MODE>(A.c, N, counts, o, P, L);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(ES_BLOCK) void event_noisy_images_kernel(EsImageArgs A, EnArgs N, EsStreamOut O, int64_t* counts) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= A.c.W || y >= A.c.H) return;
-    en_image_pixel<MODE>(A, N, O, counts, y, x);
-}
-
-template <int MODE>
-__global__ __launch_bounds__(ES_BLOCK) void event_noisy_boxroom_kernel(EsRoomArgs A, EnArgs N, EsStreamOut O, int64_t* counts) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= A.c.W || y >= A.c.H) return;
-    en_room_pixel<MODE>(A, N, O, counts, y, x);
-}
+};
 
 inline bool en_rate(double v) { return v >= 0.0 && v - v == 0.0; }      // not negative, finite
 
@@ -229,6 +189,28 @@ int en_emit_out(const int64_t* ends, int64_t total, double t_a, double t_b, doub
     return es_stream_out(ends, total, t_a, t_b, t, x, y, p, O);
 }
 
+// what the two count entries check behind their source, in this order; fills the pass
+int en_count_pass(const enslam_event_noise* noise, const double* t_last, double t_a, double t_b, int64_t* counts, EnPass<EN_COUNT>& E) {
+    const int rc = en_args(noise, t_last, nullptr, E.N);
+    if (rc != ENSLAM_OK) return rc;
+    E.counts = counts;
+    return en_count_out(t_a, t_b, E.O);
+}
+
+// what the two emit entries check behind their source, in this order, and the launch of the form the pointers ask for
+template <class Src>
+int en_launch_emit(const Src& A, const enslam_event_noise* noise, double* t_last, const int64_t* ends, int64_t total, double t_a,
+                   double t_b, double* t, uint16_t* x, uint16_t* y, uint8_t* p, void* stream) {
+    EnPass<EN_EMIT> E;
+    bool image = false;
+    int rc = en_args(noise, t_last, t_last, E.N);
+    if (rc != ENSLAM_OK) return rc;
+    rc = en_emit_out(ends, total, t_a, t_b, t, x, y, p, E.O, image);
+    if (rc != ENSLAM_OK) return rc;
+    E.counts = nullptr;
+    return image ? es_launch(A, EnPass<EN_IMAGE>{E.N, E.O, nullptr}, stream) : es_launch(A, E, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -239,22 +221,12 @@ int enslam_event_noisy_images_count(const enslam_event_sim_plan* plan, const uin
                                     const double* lut, const double* L_prev, const double* L_cur, const double* c_pos_map,
                                     const double* c_neg_map, const double* L_ref, int64_t* counts,
                                     const enslam_event_noise* noise, double t_a, double t_b, const double* t_last, void* stream) {
-    int rc = es_stream_plan(plan);
+    EsImageSrc A;
+    EnPass<EN_COUNT> E;
+    int rc = es_image_count_args(plan, prev, cur, lut, L_prev, L_cur, c_pos_map, c_neg_map, L_ref, counts, A);
     if (rc != ENSLAM_OK) return rc;
-    if (!counts) return ENSLAM_EINVAL;
-    EsImageArgs A;                  // the count kernel only reads the states and has no event image: es_store is never called
-    EnArgs N;
-    EsStreamOut O;
-    rc = es_image_args(plan, prev, cur, lut, L_prev, L_cur, c_pos_map, c_neg_map, const_cast<double*>(L_ref),
-                       reinterpret_cast<uint8_t*>(counts), A);
-    if (rc != ENSLAM_OK) return rc;
-    A.c.events = nullptr;
-    rc = en_args(noise, t_last, nullptr, N);
-    if (rc != ENSLAM_OK) return rc;
-    rc = en_count_out(t_a, t_b, O);
-    if (rc != ENSLAM_OK) return rc;
-    event_noisy_images_kernel<EN_COUNT><<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, N, O, counts);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    rc = en_count_pass(noise, t_last, t_a, t_b, counts, E);
+    return rc != ENSLAM_OK ? rc : es_launch(A, E, stream);
 }
 
 int enslam_event_noisy_images_emit(const enslam_event_sim_plan* plan, const uint8_t* prev, const uint8_t* cur,
@@ -264,42 +236,21 @@ int enslam_event_noisy_images_emit(const enslam_event_sim_plan* plan, const uint
                                    const enslam_event_noise* noise, double* t_last, void* stream) {
     int rc = es_stream_plan(plan);
     if (rc != ENSLAM_OK) return rc;
-    EsImageArgs A;
-    EnArgs N;
-    EsStreamOut O;
-    bool image = false;
+    EsImageSrc A;
     rc = es_image_args(plan, prev, cur, lut, L_prev, L_cur, c_pos_map, c_neg_map, L_ref, events, A);
-    if (rc != ENSLAM_OK) return rc;
-    rc = en_args(noise, t_last, t_last, N);
-    if (rc != ENSLAM_OK) return rc;
-    rc = en_emit_out(ends, total, t_a, t_b, t, x, y, p, O, image);
-    if (rc != ENSLAM_OK) return rc;
-    if (image)
-        event_noisy_images_kernel<EN_IMAGE><<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, N, O, nullptr);
-    else
-        event_noisy_images_kernel<EN_EMIT><<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, N, O, nullptr);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    return rc != ENSLAM_OK ? rc : en_launch_emit(A, noise, t_last, ends, total, t_a, t_b, t, x, y, p, stream);
 }
 
+// poses: [K+1,12], row 0 the previous frame's (rendered for L_prev only), rows 1..K the sub-steps -- in both entries
 int enslam_event_noisy_boxroom_count(const enslam_event_sim_plan* plan, const double* poses, const double* c_pos_map,
                                      const double* c_neg_map, const double* L_ref, int64_t* counts,
                                      const enslam_event_noise* noise, double t_a, double t_b, const double* t_last, void* stream) {
-    int rc = es_stream_plan(plan);
+    EsRoomSrc A;
+    EnPass<EN_COUNT> E;
+    int rc = es_room_count_args(plan, poses, true, c_pos_map, c_neg_map, L_ref, counts, A);
     if (rc != ENSLAM_OK) return rc;
-    if (!counts) return ENSLAM_EINVAL;
-    EsRoomArgs A;
-    EnArgs N;
-    EsStreamOut O;
-    rc = es_room_args(plan, poses, c_pos_map, c_neg_map, const_cast<double*>(L_ref), reinterpret_cast<uint8_t*>(counts), nullptr,
-                      nullptr, A);
-    if (rc != ENSLAM_OK) return rc;
-    A.c.events = nullptr;
-    rc = en_args(noise, t_last, nullptr, N);
-    if (rc != ENSLAM_OK) return rc;
-    rc = en_count_out(t_a, t_b, O);
-    if (rc != ENSLAM_OK) return rc;
-    event_noisy_boxroom_kernel<EN_COUNT><<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, N, O, counts);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    rc = en_count_pass(noise, t_last, t_a, t_b, counts, E);
+    return rc != ENSLAM_OK ? rc : es_launch(A, E, stream);
 }
 
 int enslam_event_noisy_boxroom_emit(const enslam_event_sim_plan* plan, const double* poses, const double* c_pos_map,
@@ -308,21 +259,9 @@ int enslam_event_noisy_boxroom_emit(const enslam_event_sim_plan* plan, const dou
                                     const enslam_event_noise* noise, double* t_last, void* stream) {
     int rc = es_stream_plan(plan);
     if (rc != ENSLAM_OK) return rc;
-    EsRoomArgs A;
-    EnArgs N;
-    EsStreamOut O;
-    bool image = false;
-    rc = es_room_args(plan, poses, c_pos_map, c_neg_map, L_ref, events, nullptr, nullptr, A);
-    if (rc != ENSLAM_OK) return rc;
-    rc = en_args(noise, t_last, t_last, N);
-    if (rc != ENSLAM_OK) return rc;
-    rc = en_emit_out(ends, total, t_a, t_b, t, x, y, p, O, image);
-    if (rc != ENSLAM_OK) return rc;
-    if (image)
-        event_noisy_boxroom_kernel<EN_IMAGE><<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, N, O, nullptr);
-    else
-        event_noisy_boxroom_kernel<EN_EMIT><<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, N, O, nullptr);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    EsRoomSrc A;
+    rc = es_room_args(plan, poses, true, c_pos_map, c_neg_map, L_ref, events, nullptr, nullptr, A);
+    return rc != ENSLAM_OK ? rc : en_launch_emit(A, noise, t_last, ends, total, t_a, t_b, t, x, y, p, stream);
 }
 
 }  // extern "C"

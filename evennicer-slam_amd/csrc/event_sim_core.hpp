@@ -1,7 +1,12 @@
-// The per-pixel arithmetic of the event-camera simulator, shared by event_sim.hip (count images), event_stream.hip
-// (time-stamped events) and event_noise.hip (the noisy sensor): the sensor update, the level of an image pixel, the analytic
-// room, and the fraction and time of a crossing, each written once so that all files round alike.  enslam_hip.h holds the model.  The helpers are host-callable too, so that a CPU build can step
-// through one pixel.
+// The event-camera simulator's kernel, written once (enslam_hip.h holds the model).  A launch is a level SOURCE times a PASS:
+//   sources  where a pixel's level at sub-step s = 1..K comes from: EsImageSrc (two decoded images or two host level images)
+//            and EsRoomSrc (the analytic room rendered at K poses), both in this file
+//   passes   what is done with the levels, each beside the entries that launch it: EsFramePass (event_sim.hip), EsCountPass
+//            and EsEmitPass (event_stream.hip), EnPass<MODE> (event_noise.hip)
+// es_pixel holds the only sub-step loop, event_pixels_kernel the only tile arithmetic, es_launch the only launch.  The
+// arithmetic the passes share is here as well, each piece written once so that all files round alike: the sensor update, the
+// level of an image pixel, the analytic room, and the fraction and time of a crossing.  Everything per pixel is host-callable
+// too, so that a CPU build can step through one pixel.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -47,34 +52,7 @@ struct EsCommon {
     uint8_t* events;
 };
 
-struct EsImageArgs {
-    EsCommon c;
-    int32_t channels;
-    const uint8_t* prev;
-    const uint8_t* cur;
-    const double* lut;
-    const double* L_prev;
-    const double* L_cur;
-};
-
-struct EsRoomArgs {
-    EsCommon c;
-    double fx, fy, cx, cy;
-    double room_lo[3], room_hi[3], box_lo[3], box_hi[3];
-    double freq[9], phase[3];
-    int32_t has_box;
-    const double* poses;            // [K,12]
-    double* color_out;              // [H,W,3] or NULL
-    float* depth_out;               // [H,W] or NULL
-};
-
-ES_HD double es_image_level(const EsImageArgs& A, const uint8_t* img, int64_t o) {
-    if (A.channels == 1) return A.lut[img[o]];
-    const uint8_t* s = img + 3 * o;
-    return log(es_luminance((double)s[0] / 255.0, (double)s[1] / 255.0, (double)s[2] / 255.0) + A.c.eps);
-}
-
-// sensor state in, sensor state and counts out: shared tail of both kernels
+// sensor state in, sensor state and counts out: the head of every pass, the tail of those that write the count image
 ES_HD void es_load(const EsCommon& C, int64_t o, EsSensor& S, double& cp, double& cn) {
     S.ref = C.init ? 0.0 : C.L_ref[o];
     S.pos = 0.0;
@@ -91,23 +69,72 @@ ES_HD void es_store(const EsCommon& C, int64_t o, const EsSensor& S, double L_la
     }
 }
 
-ES_HD void es_image_pixel(const EsImageArgs& A, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    const double La = A.L_prev ? A.L_prev[o] : es_image_level(A, A.prev, o);
-    const double Lb = A.L_cur ? A.L_cur[o] : es_image_level(A, A.cur, o);
-    EsSensor S;
-    double cp, cn, L = Lb;
-    es_load(A.c, o, S, cp, cn);
-    const double dL = Lb - La;
-    for (int s = 1; s <= A.c.K; ++s) {
-        L = La + ((double)s / (double)A.c.K) * dL;
-        if (!A.c.init) es_update(S, L, cp, cn);
-    }
-    es_store(A.c, o, S, L);
+// ---- the two level sources ----------------------------------------------------------------------------------------------------
+// A source has a per-pixel record Pixel, begin (fills it), start (the level the first sub-step starts from; evaluated only by
+// the passes that stamp events), level (of sub-step s = 1..K) and frame (what the source writes itself behind a pass that
+// asks for it, from the last sub-step).
+
+// images: L_a and L_b of the two frames, sub-step s at L_a + (s / K) * (L_b - L_a)
+struct EsImageSrc {
+    EsCommon c;
+    int32_t channels;
+    const uint8_t* prev;
+    const uint8_t* cur;
+    const double* lut;
+    const double* L_prev;
+    const double* L_cur;
+
+    struct Pixel {
+        double La, dL;
+    };
+    ES_HD void begin(Pixel& p, int64_t o) const;
+    ES_HD double start(const Pixel& p, int, int) const { return p.La; }
+    ES_HD double level(const Pixel& p, int s, int, int) const { return p.La + ((double)s / (double)c.K) * p.dL; }
+    ES_HD void frame(const Pixel&, int64_t) const {}
+};
+
+ES_HD double es_image_level(const EsImageSrc& A, const uint8_t* img, int64_t o) {
+    if (A.channels == 1) return A.lut[img[o]];
+    const uint8_t* s = img + 3 * o;
+    return log(es_luminance((double)s[0] / 255.0, (double)s[1] / 255.0, (double)s[2] / 255.0) + A.c.eps);
 }
 
+ES_HD void EsImageSrc::begin(Pixel& p, int64_t o) const {
+    p.La = L_prev ? L_prev[o] : es_image_level(*this, prev, o);
+    const double Lb = L_cur ? L_cur[o] : es_image_level(*this, cur, o);
+    p.dL = Lb - p.La;
+}
+
+// boxroom: synthetic.BoxRoom rendered in the kernel at the pose of every sub-step.  The poses are read at a wave-uniform
+// address from a kernel-argument pointer: scalar loads, one copy per wave.
+struct EsRoomSrc {
+    EsCommon c;
+    double fx, fy, cx, cy;
+    double room_lo[3], room_hi[3], box_lo[3], box_hi[3];
+    double freq[9], phase[3];
+    int32_t has_box;
+    const double* pose_prev;        // [12], the previous frame's pose; NULL where no pass asks for `start`
+    const double* poses;            // [K,12], the sub-steps
+    double* color_out;              // [H,W,3] or NULL
+    float* depth_out;               // [H,W] or NULL
+
+    struct Pixel {                  // colour and ray parameter under the last pose rendered
+        double col[3], t;
+    };
+    ES_HD void begin(Pixel& p, int64_t) const { p.col[0] = p.col[1] = p.col[2] = p.t = 0.0; }
+    ES_HD double start(Pixel& p, int y, int x) const;
+    ES_HD double level(Pixel& p, int s, int y, int x) const;
+    ES_HD void frame(const Pixel& p, int64_t o) const {
+        if (color_out) {
+            double* co = color_out + 3 * o;
+            co[0] = p.col[0]; co[1] = p.col[1]; co[2] = p.col[2];
+            depth_out[o] = (float)p.t;
+        }
+    }
+};
+
 // BoxRoom.render of one pixel under the pose P (the 12 values of c2w[:3,:4], row-major): colour and the ray parameter
-ES_HD void es_room_pixel(const EsRoomArgs& A, const double* __restrict__ P, int y, int x, double (&col)[3], double& t) {
+ES_HD void es_room_pixel(const EsRoomSrc& A, const double* __restrict__ P, int y, int x, double (&col)[3], double& t) {
     const double dir[3] = {((double)x - A.cx) / A.fx, -((double)y - A.cy) / A.fy, -1.0};
     double o[3], d[3], dc[3];
 #pragma unroll
@@ -144,29 +171,61 @@ ES_HD void es_room_pixel(const EsRoomArgs& A, const double* __restrict__ P, int 
     }
 }
 
-ES_HD void es_room_pixel_interval(const EsRoomArgs& A, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    EsSensor S;
-    double cp, cn, L = 0.0, col[3] = {0.0, 0.0, 0.0}, t = 0.0;
-    es_load(A.c, o, S, cp, cn);
-#pragma clang loop unroll(disable)
-    for (int s = 0; s < A.c.K; ++s) {
-        es_room_pixel(A, A.poses + 12 * s, y, x, col, t);
-        L = log(es_luminance(col[0], col[1], col[2]) + A.c.eps);
-        if (!A.c.init) es_update(S, L, cp, cn);
-    }
-    es_store(A.c, o, S, L);
-    if (A.color_out) {
-        double* co = A.color_out + 3 * o;
-        co[0] = col[0]; co[1] = col[1]; co[2] = col[2];
-        A.depth_out[o] = (float)t;
-    }
+ES_HD double es_room_level(const EsRoomSrc& A, EsRoomSrc::Pixel& p, const double* __restrict__ P, int y, int x) {
+    es_room_pixel(A, P, y, x, p.col, p.t);
+    return log(es_luminance(p.col[0], p.col[1], p.col[2]) + A.c.eps);
 }
 
+ES_HD double EsRoomSrc::start(Pixel& p, int y, int x) const { return es_room_level(*this, p, pose_prev, y, x); }
+ES_HD double EsRoomSrc::level(Pixel& p, int s, int y, int x) const { return es_room_level(*this, p, poses + 12 * (s - 1), y, x); }
+
+// ---- one pixel, one kernel, one launch ----------------------------------------------------------------------------------------
+// A pass has a per-pixel State, begin (loads it and the pixel's thresholds), substep (s of K at the level L, the level before
+// being L_prev) and end (stores; L_last is the level of sub-step K).  STAMPS says whether it reads L_prev, FRAME whether the
+// source's frame is written behind it.
+//
+// The loop is not unrolled: its trip count is a kernel argument, and copies of the room's render only cost registers
+// (DESIGN.md 4.S has the resource table).
+template <class Src, class Pass>
+ES_HD void es_pixel(const Src& src, const Pass& pass, int y, int x) {
+    const EsCommon& C = src.c;
+    const int64_t o = (int64_t)y * C.W + x;
+    typename Src::Pixel px;
+    typename Pass::State st;
+    double cp, cn;
+    src.begin(px, o);
+    pass.begin(C, o, st, cp, cn);
+    double L_prev = Pass::STAMPS ? src.start(px, y, x) : 0.0, L = L_prev;
+#pragma clang loop unroll(disable)
+    for (int s = 1; s <= C.K; ++s) {
+        L = src.level(px, s, y, x);
+        pass.substep(C, st, o, y, x, s, cp, cn, L_prev, L);
+        L_prev = L;
+    }
+    pass.end(C, o, st, L);
+    if (Pass::FRAME) src.frame(px, o);
+}
+
+// 64 x 4 pixel tiles, a wave = 64 consecutive pixels of one row
+template <class Src, class Pass>
+__global__ __launch_bounds__(ES_BLOCK) void event_pixels_kernel(Src src, Pass pass) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= src.c.W || y >= src.c.H) return;
+    es_pixel(src, pass, y, x);
+}
+
+template <class Src, class Pass>
+inline int es_launch(const Src& src, const Pass& pass, void* stream) {
+    const dim3 grid((unsigned)((src.c.W + 63) / 64), (unsigned)((src.c.H + 3) / 4));
+    event_pixels_kernel<<<grid, ES_BLOCK, 0, (hipStream_t)stream>>>(src, pass);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+// ---- what the entries check before they launch (no device work) ---------------------------------------------------------------
 inline bool es_pos_finite(double x) { return x > 0.0 && x - x == 0.0; }
 inline bool es_finite(double x) { return x == x && x - x == 0.0; }
 
-// Checks what both routes share and fills C.  No device work.
+// Checks what both routes share and fills C.
 inline int es_common(const enslam_event_sim_plan* plan, const double* c_pos_map, const double* c_neg_map, double* L_ref,
               uint8_t* events, EsCommon& C) {
     if (!plan || !L_ref) return ENSLAM_EINVAL;
@@ -184,12 +243,10 @@ inline int es_common(const enslam_event_sim_plan* plan, const double* c_pos_map,
     return ENSLAM_OK;
 }
 
-inline dim3 es_grid(const EsCommon& C) { return dim3((unsigned)((C.W + 63) / 64), (unsigned)((C.H + 3) / 4)); }
-
-// The images route's checks on top of es_common; fills A.  No device work.
+// The images route's checks on top of es_common; fills A.
 inline int es_image_args(const enslam_event_sim_plan* plan, const uint8_t* prev, const uint8_t* cur, const double* lut,
                          const double* L_prev, const double* L_cur, const double* c_pos_map, const double* c_neg_map,
-                         double* L_ref, uint8_t* events, EsImageArgs& A) {
+                         double* L_ref, uint8_t* events, EsImageSrc& A) {
     const int rc = es_common(plan, c_pos_map, c_neg_map, L_ref, events, A.c);
     if (rc != ENSLAM_OK) return rc;
     if ((L_prev == nullptr) != (L_cur == nullptr)) return ENSLAM_EINVAL;
@@ -203,9 +260,11 @@ inline int es_image_args(const enslam_event_sim_plan* plan, const uint8_t* prev,
     return ENSLAM_OK;
 }
 
-// The analytic route's checks on top of es_common; fills A.  No device work.
-inline int es_room_args(const enslam_event_sim_plan* plan, const double* poses, const double* c_pos_map, const double* c_neg_map,
-                        double* L_ref, uint8_t* events, double* color_out, float* depth_out, EsRoomArgs& A) {
+// The analytic route's checks on top of es_common; fills A.  poses: [K,12] the sub-steps, or (with_prev) [K+1,12] with the
+// previous frame's pose as row 0.
+inline int es_room_args(const enslam_event_sim_plan* plan, const double* poses, bool with_prev, const double* c_pos_map,
+                        const double* c_neg_map, double* L_ref, uint8_t* events, double* color_out, float* depth_out,
+                        EsRoomSrc& A) {
     const int rc = es_common(plan, c_pos_map, c_neg_map, L_ref, events, A.c);
     if (rc != ENSLAM_OK) return rc;
     if (!poses || (color_out == nullptr) != (depth_out == nullptr)) return ENSLAM_EINVAL;
@@ -219,7 +278,9 @@ inline int es_room_args(const enslam_event_sim_plan* plan, const double* poses, 
     }
     for (int k = 0; k < 9; ++k) A.freq[k] = P.freq[k];
     A.has_box = P.has_box != 0;
-    A.poses = poses; A.color_out = color_out; A.depth_out = depth_out;
+    A.pose_prev = with_prev ? poses : nullptr;
+    A.poses = with_prev ? poses + 12 : poses;
+    A.color_out = color_out; A.depth_out = depth_out;
     return ENSLAM_OK;
 }
 
@@ -276,18 +337,37 @@ ES_HD void es_put(const EsStreamOut& O, int64_t at, double t, int y, int x, bool
     O.p[at] = up ? (uint8_t)1 : (uint8_t)0;
 }
 
-ES_HD double es_room_level(const EsRoomArgs& A, const double* __restrict__ P, int y, int x) {
-    double col[3] = {0.0, 0.0, 0.0}, t = 0.0;
-    es_room_pixel(A, P, y, x, col, t);
-    return log(es_luminance(col[0], col[1], col[2]) + A.c.eps);
-}
-
 // what the stream entries add to the plan's checks: no first-frame mode, coordinates that fit uint16
 inline int es_stream_plan(const enslam_event_sim_plan* plan) {
     if (!plan) return ENSLAM_EINVAL;
     if (plan->init) return ENSLAM_EINVAL;
     if (plan->H > 65536 || plan->W > 65536) return ENSLAM_EUNSUPPORTED;
     return ENSLAM_OK;
+}
+
+// The head of the four count entries: es_stream_plan, the counts, then the route's own checks.  A count pass only reads
+// L_ref and has no event image (es_store is never called): `counts` stands in for it in the checks alone.
+inline int es_image_count_args(const enslam_event_sim_plan* plan, const uint8_t* prev, const uint8_t* cur, const double* lut,
+                               const double* L_prev, const double* L_cur, const double* c_pos_map, const double* c_neg_map,
+                               const double* L_ref, int64_t* counts, EsImageSrc& A) {
+    int rc = es_stream_plan(plan);
+    if (rc != ENSLAM_OK) return rc;
+    if (!counts) return ENSLAM_EINVAL;
+    rc = es_image_args(plan, prev, cur, lut, L_prev, L_cur, c_pos_map, c_neg_map, const_cast<double*>(L_ref),
+                       reinterpret_cast<uint8_t*>(counts), A);
+    A.c.events = nullptr;
+    return rc;
+}
+
+inline int es_room_count_args(const enslam_event_sim_plan* plan, const double* poses, bool with_prev, const double* c_pos_map,
+                              const double* c_neg_map, const double* L_ref, int64_t* counts, EsRoomSrc& A) {
+    int rc = es_stream_plan(plan);
+    if (rc != ENSLAM_OK) return rc;
+    if (!counts) return ENSLAM_EINVAL;
+    rc = es_room_args(plan, poses, with_prev, c_pos_map, c_neg_map, const_cast<double*>(L_ref), reinterpret_cast<uint8_t*>(counts),
+                      nullptr, nullptr, A);
+    A.c.events = nullptr;
+    return rc;
 }
 
 inline int es_stream_out(const int64_t* ends, int64_t total, double t_a, double t_b, double* t, uint16_t* x, uint16_t* y,

@@ -2,8 +2,8 @@
 //
 // Simulator side: the sensor of event_sim.hip, but every event leaves with a time stamp from linear level-crossing
 // interpolation inside its sub-step (as ESIM does).  A stream is struct-of-arrays (t float64, x / y uint16, p uint8) in
-// pixel-major order: row-major pixels, time-ordered within a pixel.  Two launches per interval, one thread per pixel on the
-// 64 x 4 tile of event_sim.hip:
+// pixel-major order: row-major pixels, time-ordered within a pixel.  Two launches per interval, two passes of the one kernel
+// of event_sim_core.hpp (one thread per pixel on its 64 x 4 tile, either source):
 //   count  walks the sub-steps exactly as event_sim.hip does and writes the unsaturated per-pixel total (int64); L_ref is
 //          only read
 //   emit   walks them again and writes the pixel's run at its offset (the caller's inclusive prefix sum of the counts), the
@@ -43,95 +43,37 @@ ES_HD void es_emit_substep(const EsStreamOut& O, int64_t& at, int64_t end, int y
     }
 }
 
-ES_HD int64_t es_image_pixel_count(const EsImageArgs& A, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    const double La = A.L_prev ? A.L_prev[o] : es_image_level(A, A.prev, o);
-    const double Lb = A.L_cur ? A.L_cur[o] : es_image_level(A, A.cur, o);
-    EsSensor S;
-    double cp, cn;
-    es_load(A.c, o, S, cp, cn);
-    const double dL = Lb - La;
-    for (int s = 1; s <= A.c.K; ++s) {
-        const double L = La + ((double)s / (double)A.c.K) * dL;
+// count: the unsaturated per-pixel total; L_ref is only read.  O(1) per sub-step, no walk.
+struct EsCountPass {
+    static constexpr bool STAMPS = false, FRAME = false;
+    using State = EsSensor;
+    int64_t* counts;
+    ES_HD void begin(const EsCommon& C, int64_t o, State& S, double& cp, double& cn) const { es_load(C, o, S, cp, cn); }
+    ES_HD void substep(const EsCommon&, State& S, int64_t, int, int, int, double cp, double cn, double, double L) const {
         es_update(S, L, cp, cn);
     }
-    return es_total(S);
-}
+    ES_HD void end(const EsCommon&, int64_t o, const State& S, double) const { counts[o] = es_total(S); }
+};
 
-ES_HD void es_image_pixel_emit(const EsImageArgs& A, const EsStreamOut& O, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    const double La = A.L_prev ? A.L_prev[o] : es_image_level(A, A.prev, o);
-    const double Lb = A.L_cur ? A.L_cur[o] : es_image_level(A, A.cur, o);
-    EsSensor S;
-    double cp, cn, L = Lb, L_before = La;
-    int64_t at, end;
-    es_load(A.c, o, S, cp, cn);
-    es_run(O, o, at, end);
-    const double dL = Lb - La;
-    for (int s = 1; s <= A.c.K; ++s) {
-        L = La + ((double)s / (double)A.c.K) * dL;
-        const double R = S.ref, pos0 = S.pos, neg0 = S.neg;
-        es_update(S, L, cp, cn);
-        es_emit_substep(O, at, end, y, x, s, A.c.K, R, S, pos0, neg0, cp, cn, L_before, L);
-        L_before = L;
+// emit: the pixel's run at its offset, the saturated count image and the new L_ref
+struct EsEmitPass {
+    static constexpr bool STAMPS = true, FRAME = false;
+    struct State {
+        EsSensor S;
+        int64_t at, end;
+    };
+    EsStreamOut O;
+    ES_HD void begin(const EsCommon& C, int64_t o, State& P, double& cp, double& cn) const {
+        es_load(C, o, P.S, cp, cn);
+        es_run(O, o, P.at, P.end);
     }
-    es_store(A.c, o, S, L);
-}
-
-// poses: [K,12], the sub-steps
-ES_HD int64_t es_room_pixel_count(const EsRoomArgs& A, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    EsSensor S;
-    double cp, cn;
-    es_load(A.c, o, S, cp, cn);
-#pragma clang loop unroll(disable)
-    for (int s = 0; s < A.c.K; ++s) es_update(S, es_room_level(A, A.poses + 12 * s, y, x), cp, cn);
-    return es_total(S);
-}
-
-// poses: [K+1,12], row 0 the previous frame's (rendered for L_prev only), rows 1..K the sub-steps
-ES_HD void es_room_pixel_emit(const EsRoomArgs& A, const EsStreamOut& O, int y, int x) {
-    const int64_t o = (int64_t)y * A.c.W + x;
-    EsSensor S;
-    double cp, cn;
-    int64_t at, end;
-    es_load(A.c, o, S, cp, cn);
-    es_run(O, o, at, end);
-    double L_before = es_room_level(A, A.poses, y, x), L = L_before;
-#pragma clang loop unroll(disable)
-    for (int s = 1; s <= A.c.K; ++s) {
-        L = es_room_level(A, A.poses + 12 * s, y, x);
-        const double R = S.ref, pos0 = S.pos, neg0 = S.neg;
-        es_update(S, L, cp, cn);
-        es_emit_substep(O, at, end, y, x, s, A.c.K, R, S, pos0, neg0, cp, cn, L_before, L);
-        L_before = L;
+    ES_HD void substep(const EsCommon& C, State& P, int64_t, int y, int x, int s, double cp, double cn, double L_prev, double L) const {
+        const double R = P.S.ref, pos0 = P.S.pos, neg0 = P.S.neg;
+        es_update(P.S, L, cp, cn);
+        es_emit_substep(O, P.at, P.end, y, x, s, C.K, R, P.S, pos0, neg0, cp, cn, L_prev, L);
     }
-    es_store(A.c, o, S, L);
-}
-
-__global__ __launch_bounds__(ES_BLOCK) void event_stream_images_count_kernel(EsImageArgs A, int64_t* counts) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= A.c.W || y >= A.c.H) return;
-    counts[(int64_t)y * A.c.W + x] = es_image_pixel_count(A, y, x);
-}
-
-__global__ __launch_bounds__(ES_BLOCK) void event_stream_images_emit_kernel(EsImageArgs A, EsStreamOut O) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= A.c.W || y >= A.c.H) return;
-    es_image_pixel_emit(A, O, y, x);
-}
-
-__global__ __launch_bounds__(ES_BLOCK) void event_stream_boxroom_count_kernel(EsRoomArgs A, int64_t* counts) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= A.c.W || y >= A.c.H) return;
-    counts[(int64_t)y * A.c.W + x] = es_room_pixel_count(A, y, x);
-}
-
-__global__ __launch_bounds__(ES_BLOCK) void event_stream_boxroom_emit_kernel(EsRoomArgs A, EsStreamOut O) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= A.c.W || y >= A.c.H) return;
-    es_room_pixel_emit(A, O, y, x);
-}
+    ES_HD void end(const EsCommon& C, int64_t o, const State& P, double L_last) const { es_store(C, o, P.S, L_last); }
+};
 
 struct EaArgs {
     const double* t;
@@ -194,16 +136,9 @@ extern "C" {
 int enslam_event_stream_images_count(const enslam_event_sim_plan* plan, const uint8_t* prev, const uint8_t* cur,
                                      const double* lut, const double* L_prev, const double* L_cur, const double* c_pos_map,
                                      const double* c_neg_map, const double* L_ref, int64_t* counts, void* stream) {
-    int rc = es_stream_plan(plan);
-    if (rc != ENSLAM_OK) return rc;
-    if (!counts) return ENSLAM_EINVAL;
-    EsImageArgs A;                  // the count kernel only reads L_ref and has no event image: es_store is never called
-    rc = es_image_args(plan, prev, cur, lut, L_prev, L_cur, c_pos_map, c_neg_map, const_cast<double*>(L_ref),
-                       reinterpret_cast<uint8_t*>(counts), A);
-    if (rc != ENSLAM_OK) return rc;
-    A.c.events = nullptr;
-    event_stream_images_count_kernel<<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, counts);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    EsImageSrc A;
+    const int rc = es_image_count_args(plan, prev, cur, lut, L_prev, L_cur, c_pos_map, c_neg_map, L_ref, counts, A);
+    return rc != ENSLAM_OK ? rc : es_launch(A, EsCountPass{counts}, stream);
 }
 
 int enslam_event_stream_images_emit(const enslam_event_sim_plan* plan, const uint8_t* prev, const uint8_t* cur,
@@ -212,43 +147,34 @@ int enslam_event_stream_images_emit(const enslam_event_sim_plan* plan, const uin
                                     double t_a, double t_b, double* t, uint16_t* x, uint16_t* y, uint8_t* p, void* stream) {
     int rc = es_stream_plan(plan);
     if (rc != ENSLAM_OK) return rc;
-    EsImageArgs A;
-    EsStreamOut O;
+    EsImageSrc A;
+    EsEmitPass E;
     rc = es_image_args(plan, prev, cur, lut, L_prev, L_cur, c_pos_map, c_neg_map, L_ref, events, A);
     if (rc != ENSLAM_OK) return rc;
-    rc = es_stream_out(ends, total, t_a, t_b, t, x, y, p, O);
-    if (rc != ENSLAM_OK) return rc;
-    event_stream_images_emit_kernel<<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, O);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    rc = es_stream_out(ends, total, t_a, t_b, t, x, y, p, E.O);
+    return rc != ENSLAM_OK ? rc : es_launch(A, E, stream);
 }
 
+// poses: [K,12], the sub-steps
 int enslam_event_stream_boxroom_count(const enslam_event_sim_plan* plan, const double* poses, const double* c_pos_map,
                                       const double* c_neg_map, const double* L_ref, int64_t* counts, void* stream) {
-    int rc = es_stream_plan(plan);
-    if (rc != ENSLAM_OK) return rc;
-    if (!counts) return ENSLAM_EINVAL;
-    EsRoomArgs A;
-    rc = es_room_args(plan, poses, c_pos_map, c_neg_map, const_cast<double*>(L_ref), reinterpret_cast<uint8_t*>(counts), nullptr,
-                      nullptr, A);
-    if (rc != ENSLAM_OK) return rc;
-    A.c.events = nullptr;
-    event_stream_boxroom_count_kernel<<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, counts);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    EsRoomSrc A;
+    const int rc = es_room_count_args(plan, poses, false, c_pos_map, c_neg_map, L_ref, counts, A);
+    return rc != ENSLAM_OK ? rc : es_launch(A, EsCountPass{counts}, stream);
 }
 
+// poses: [K+1,12], row 0 the previous frame's (rendered for L_prev only), rows 1..K the sub-steps
 int enslam_event_stream_boxroom_emit(const enslam_event_sim_plan* plan, const double* poses, const double* c_pos_map,
                                      const double* c_neg_map, double* L_ref, uint8_t* events, const int64_t* ends, int64_t total,
                                      double t_a, double t_b, double* t, uint16_t* x, uint16_t* y, uint8_t* p, void* stream) {
     int rc = es_stream_plan(plan);
     if (rc != ENSLAM_OK) return rc;
-    EsRoomArgs A;
-    EsStreamOut O;
-    rc = es_room_args(plan, poses, c_pos_map, c_neg_map, L_ref, events, nullptr, nullptr, A);
+    EsRoomSrc A;
+    EsEmitPass E;
+    rc = es_room_args(plan, poses, true, c_pos_map, c_neg_map, L_ref, events, nullptr, nullptr, A);
     if (rc != ENSLAM_OK) return rc;
-    rc = es_stream_out(ends, total, t_a, t_b, t, x, y, p, O);
-    if (rc != ENSLAM_OK) return rc;
-    event_stream_boxroom_emit_kernel<<<es_grid(A.c), ES_BLOCK, 0, (hipStream_t)stream>>>(A, O);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    rc = es_stream_out(ends, total, t_a, t_b, t, x, y, p, E.O);
+    return rc != ENSLAM_OK ? rc : es_launch(A, E, stream);
 }
 
 int enslam_event_accumulate(const double* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t N,

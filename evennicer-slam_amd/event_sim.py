@@ -439,7 +439,12 @@ class EventSimulator:
         return self
 
     # ---- one interval ------------------------------------------------------------------------------------------------------
-    def _noisy_stamps(self, stamps, what):
+    def _interval_stamps(self, stamps, what, want_frame=False):
+        """the interval's stamps, checked: None without noise means the count image alone"""
+        if want_frame and (self.noise is not None or stamps is not None):
+            raise EnslamError("EventSimulator.step_scene: stamps and want_frame are not combined")
+        if self.noise is None:
+            return None if stamps is None else _stamps(stamps)
         if stamps is None:
             raise EnslamError(f"EventSimulator.{what}: a simulator with noise needs stamps = (t_a, t_b): the refractory period and "
                               "the rates are in seconds")
@@ -451,22 +456,47 @@ class EventSimulator:
             raise EnslamError("EventSimulator: the interval counter is uint32; reset() the simulator")
         return stamps
 
-    def _noisy_levels(self, levels, stamps, stream):
-        """the numpy route of the noisy sensor over the K + 1 level images `levels` (the previous frame's first)"""
-        ref, t_last = self._ref.numpy(), self._t_last.numpy()
+    def _step(self, source, stamps, stream):
+        """One interval from its level source -- on the device (route, the leading arguments of functional.event_*_<route>,
+        keywords), on the CPU ('numpy', then the arguments of `_walk`) -- through the frame, the stream or the noisy pass."""
+        route, head, kw = source[0], source[1], source[2]
+        if route == 'numpy':
+            return self._walk(*source[1:], stamps, stream)
+        if self.noise is not None:
+            out = getattr(self._EF, 'event_noisy_' + route)(*head, self._ref, self._t_last, stamps, self.noise.params(self._interval),
+                                                            stream=stream, **kw, **self._kw())
+            self._interval += 1
+            return self._with_stream(out) if stream else out
+        if stamps is not None:
+            return self._with_stream(getattr(self._EF, 'event_stream_' + route)(*head, self._ref, stamps, **kw, **self._kw()))
+        return getattr(self._EF, 'event_sim_' + route)(*head, self._ref, **kw, **self._kw())
+
+    def _walk(self, levels, first, frame, stamps, stream):
+        """The numpy route of all three passes: one walk over the sub-steps' level images.  first: the level before the first
+        (stamps only); frame: None, or where [colour, ray parameter] of the last sub-step are once `levels` is used up."""
+        ref = self._ref.numpy()
         pos, neg = np.zeros_like(ref), np.zeros_like(ref)
         cp, cn = self._thresholds()
-        parts = []
-        for s in range(1, self.substeps + 1):
-            parts.append(noisy_substep(s, self.substeps, stamps[0], stamps[1], ref, t_last, neg, pos, cp, cn, levels[s - 1],
-                                       levels[s], self.noise, self._interval))
-        self._interval += 1
+        K, parts, L_before = self.substeps, [], first
+        for s, L in enumerate(levels, start=1):
+            if self.noise is not None:
+                parts.append(noisy_substep(s, K, stamps[0], stamps[1], ref, self._t_last.numpy(), neg, pos, cp, cn, L_before, L,
+                                           self.noise, self._interval))
+            elif stamps is None:
+                sensor_update(L, ref, pos, neg, cp, cn)
+            else:
+                R, pos0, neg0 = ref.copy(), pos.copy(), neg.copy()
+                sensor_update(L, ref, pos, neg, cp, cn)
+                parts.append(stream_substep(s, K, stamps[0], stamps[1], R, pos - pos0, neg - neg0, cp, cn, L_before, L))
+            L_before = L
+        if self.noise is not None:
+            self._interval += 1
         events = torch.from_numpy(saturate(neg, pos))
-        return (events, _stream_of(parts, self.W)) if stream else events
-
-    def _noisy_device(self, out, stream):
-        self._interval += 1
-        return self._with_stream(out) if stream else out
+        if frame is not None:
+            return events, torch.from_numpy(frame[0]), torch.from_numpy(frame[1].astype(np.float32))
+        if stamps is None or (self.noise is not None and not stream):
+            return events
+        return events, _stream_of(parts, self.W)
 
     def step_images(self, prev, cur, host_log=False, stamps=None, stream=True):
         """Events uint8 [H,W,2] = (-, +) between two decoded images (numpy arrays, or tensors on the device).  host_log: on a
@@ -475,56 +505,21 @@ class EventSimulator:
         (events, EventStream) -- the same image and state, and the time-stamped events in pixel-major order.  With a noise object
         stamps are required; stream=False then returns the image alone."""
         self._need_state()
-        if self.noise is not None:
-            stamps = self._noisy_stamps(stamps, 'step_images')
-            K = self.substeps
-            if not self.on_device:
-                La, Lb = self._host_level(prev), self._host_level(cur)
-                dL = Lb - La
-                return self._noisy_levels([La] + [La + (s / K) * dL for s in range(1, K + 1)], stamps, stream)
-            kw = dict(substeps=K, stream=stream, **self._kw())
-            if host_log:
-                levels = tuple(torch.from_numpy(self._host_level(im)).to(self.device) for im in (prev, cur))
-                return self._noisy_device(self._EF.event_noisy_images(None, None, self._ref, self._t_last, stamps,
-                                                                      self.noise.params(self._interval), levels=levels, **kw), stream)
+        stamps = self._interval_stamps(stamps, 'step_images')
+        K = self.substeps
+        if not self.on_device:
+            La, Lb = self._host_level(prev), self._host_level(cur)
+            dL = Lb - La
+            source = ('numpy', (La + (s / K) * dL for s in range(1, K + 1)), La, None)
+        elif host_log:
+            levels = tuple(torch.from_numpy(self._host_level(im)).to(self.device) for im in (prev, cur))
+            source = ('images', (None, None), dict(substeps=K, levels=levels))
+        else:
             a, b = self._image(prev), self._image(cur)
             if a.shape != b.shape:
                 raise EnslamError(f"EventSimulator: the two images differ in shape ({tuple(a.shape)}, {tuple(b.shape)})")
-            return self._noisy_device(self._EF.event_noisy_images(a, b, self._ref, self._t_last, stamps,
-                                                                  self.noise.params(self._interval), lut=self._lut, **kw), stream)
-        if stamps is not None:
-            stamps = _stamps(stamps)
-        if not self.on_device:
-            La, Lb = self._host_level(prev), self._host_level(cur)
-            ref = self._ref.numpy()
-            pos, neg = np.zeros_like(ref), np.zeros_like(ref)
-            cp, cn = self._thresholds()
-            dL = Lb - La
-            parts, L_before = [], La
-            for s in range(1, self.substeps + 1):
-                L = La + (s / self.substeps) * dL
-                if stamps is None:
-                    sensor_update(L, ref, pos, neg, cp, cn)
-                    continue
-                R, pos0, neg0 = ref.copy(), pos.copy(), neg.copy()
-                sensor_update(L, ref, pos, neg, cp, cn)
-                parts.append(stream_substep(s, self.substeps, stamps[0], stamps[1], R, pos - pos0, neg - neg0, cp, cn, L_before, L))
-                L_before = L
-            events = torch.from_numpy(saturate(neg, pos))
-            return events if stamps is None else (events, _stream_of(parts, self.W))
-        if host_log:
-            levels = tuple(torch.from_numpy(self._host_level(im)).to(self.device) for im in (prev, cur))
-            if stamps is not None:
-                return self._with_stream(self._EF.event_stream_images(None, None, self._ref, stamps, substeps=self.substeps,
-                                                                      levels=levels, **self._kw()))
-            return self._EF.event_sim_images(None, None, self._ref, substeps=self.substeps, levels=levels, **self._kw())
-        a, b = self._image(prev), self._image(cur)
-        if a.shape != b.shape:
-            raise EnslamError(f"EventSimulator: the two images differ in shape ({tuple(a.shape)}, {tuple(b.shape)})")
-        if stamps is not None:
-            return self._with_stream(self._EF.event_stream_images(a, b, self._ref, stamps, substeps=self.substeps, lut=self._lut,
-                                                                  **self._kw()))
-        return self._EF.event_sim_images(a, b, self._ref, substeps=self.substeps, lut=self._lut, **self._kw())
+            source = ('images', (a, b), dict(substeps=K, lut=self._lut))
+        return self._step(source, stamps, stream)
 
     @staticmethod
     def _with_stream(out):
@@ -540,52 +535,22 @@ class EventSimulator:
         self._need_state()
         self._check_cam(cam)
         poses = interpolate_poses(_pose64(c2w_prev), _pose64(c2w_cur), self.substeps)
-        if self.noise is not None:
-            if want_frame:
-                raise EnslamError("EventSimulator.step_scene: stamps and want_frame are not combined")
-            stamps = self._noisy_stamps(stamps, 'step_scene')
+        stamps = self._interval_stamps(stamps, 'step_scene', want_frame)
+        first = None
+        if stamps is not None:                                      # the previous frame's pose, for the level before sub-step 1
             first = np.eye(4, dtype=np.float64)
             first[:3, :] = _pose64(c2w_prev)[:3, :]
-            with_prev = np.concatenate([first[None], poses], axis=0)
-            if self.on_device:
-                return self._noisy_device(self._EF.event_noisy_boxroom(room, with_prev, cam, self._ref, self._t_last, stamps,
-                                                                       self.noise.params(self._interval), stream=stream,
-                                                                       **self._kw()), stream)
-            return self._noisy_levels([np.log(luminance(render_boxroom(room, P, cam)[0]) + self.eps) for P in with_prev], stamps,
-                                      stream)
-        if stamps is not None:
-            if want_frame:
-                raise EnslamError("EventSimulator.step_scene: stamps and want_frame are not combined")
-            stamps = _stamps(stamps)
-            first = np.eye(4, dtype=np.float64)
-            first[:3, :] = _pose64(c2w_prev)[:3, :]
-            with_prev = np.concatenate([first[None], poses], axis=0)
-            if self.on_device:
-                return self._with_stream(self._EF.event_stream_boxroom(room, with_prev, cam, self._ref, stamps, **self._kw()))
-            ref = self._ref.numpy()
-            pos, neg = np.zeros_like(ref), np.zeros_like(ref)
-            cp, cn = self._thresholds()
-            parts = []
-            L_before = np.log(luminance(render_boxroom(room, with_prev[0], cam)[0]) + self.eps)
-            for s, P in enumerate(poses, start=1):
-                L = np.log(luminance(render_boxroom(room, P, cam)[0]) + self.eps)
-                R, pos0, neg0 = ref.copy(), pos.copy(), neg.copy()
-                sensor_update(L, ref, pos, neg, cp, cn)
-                parts.append(stream_substep(s, self.substeps, stamps[0], stamps[1], R, pos - pos0, neg - neg0, cp, cn, L_before, L))
-                L_before = L
-            return torch.from_numpy(saturate(neg, pos)), _stream_of(parts, self.W)
         if self.on_device:
-            return self._EF.event_sim_boxroom(room, poses, cam, self._ref, want_frame=want_frame, **self._kw())
-        ref = self._ref.numpy()
-        pos, neg = np.zeros_like(ref), np.zeros_like(ref)
-        cp, cn = self._thresholds()
-        for P in poses:
-            col, t = render_boxroom(room, P, cam)
-            sensor_update(np.log(luminance(col) + self.eps), ref, pos, neg, cp, cn)
-        events = torch.from_numpy(saturate(neg, pos))
-        if want_frame:
-            return events, torch.from_numpy(col), torch.from_numpy(t.astype(np.float32))
-        return events
+            source = ('boxroom', (room, poses if first is None else np.concatenate([first[None], poses], axis=0), cam),
+                      dict(want_frame=want_frame) if stamps is None else {})
+        else:
+            frame = [None, None]
+
+            def level(P):
+                frame[:] = render_boxroom(room, P, cam)
+                return np.log(luminance(frame[0]) + self.eps)
+            source = ('numpy', (level(P) for P in poses), None if first is None else level(first), frame if want_frame else None)
+        return self._step(source, stamps, stream)
 
 
 def _pose64(c2w):

@@ -2928,134 +2928,15 @@ def _event_sim_tensor(what, name, t, dtype, shape, device):
                             f"contiguous: {t.is_contiguous()})")
 
 
-def event_sim_images(prev, cur, state, substeps=8, eps=1e-3, c_pos=0.2, c_neg=0.2, lut=None, levels=None, c_pos_map=None,
-                     c_neg_map=None, init=False):
-    """One interval of the image route (enslam_event_sim_images, enslam_hip.h): events uint8 [H,W,2] = (-, +) between two
-    decoded images, `state` (L_ref, float64 [H,W] on a HIP device) updated in place.
-
-      prev, cur  uint8 [H,W] / [H,W,1] (grey) or [H,W,3] (RGB) on the state's device
-      lut        float64 [256]: log(v / 255 + eps) of the grey values, computed by the host (required for grey images)
-      levels     (L_prev, L_cur) float64 [H,W]: host-computed log intensities used INSTEAD of the images (prev and cur may
-                 then be None), so that no device log decides a count
-      c_pos_map, c_neg_map  float64 [H,W] per-pixel thresholds replacing the scalars
-      init       the first frame: no events (None is returned), state := L of `cur`"""
-    what = "event_sim_images"
+def _event_image_source(what, prev, cur, state, stamps, substeps, eps, c_pos, c_neg, c_pos_map, c_neg_map, lut, levels, init):
+    """Validates the images source of one interval (stamps None: the frame entry, which has none) and returns (H, W, stamps,
+    src): src the arguments the three *_images entries share, from the plan to L_ref."""
     if not torch.is_tensor(state):
         raise L.EnslamError(f"{what}: state must be a tensor")
     H, W = (int(v) for v in state.shape) if state.dim() == 2 else (0, 0)
     _event_sim_checks(what, H, W, substeps, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, init)
-    dev = state.device
-    channels = 1
-    if levels is not None:
-        if len(levels) != 2:
-            raise L.EnslamError(f"{what}: levels must be the pair (L_prev, L_cur)")
-        for name, t in zip(('L_prev', 'L_cur'), levels):
-            _event_sim_tensor(what, name, t, torch.float64, (H, W), dev)
-    else:
-        if not torch.is_tensor(prev) or not torch.is_tensor(cur):
-            raise L.EnslamError(f"{what}: prev and cur must be tensors (or pass `levels`)")
-        for name, t in (('prev', prev), ('cur', cur)):
-            if t.dim() not in (2, 3) or t.shape != cur.shape:
-                raise L.EnslamError(f"{what}: prev and cur must be uint8 tensors of one shape [H,W] or [H,W,C]")
-            shape = (H, W) if t.dim() == 2 else (H, W, int(t.shape[2]))
-            if t.dim() == 3 and shape[2] not in (1, 3):
-                raise L.EnslamError(f"{what}: images must have 1 or 3 channels (got {shape[2]})")
-            _event_sim_tensor(what, name, t, torch.uint8, shape, dev)
-        channels = 3 if cur.dim() == 3 and cur.shape[2] == 3 else 1
-        if channels == 1:
-            if lut is None:
-                raise L.EnslamError(f"{what}: grey images need the host-computed table `lut` (float64 [256])")
-            _event_sim_tensor(what, 'lut', lut, torch.float64, (256,), dev)
-    plan = event_sim_plan(H, W, substeps, eps, c_pos, c_neg, channels=channels, init=init)
-    with torch.cuda.device(dev):
-        events = None if init else torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
-        la, lb = levels if levels is not None else (None, None)
-        L.check(L.lib().enslam_event_sim_images(ctypes.byref(plan), _ptr(prev) if levels is None else None,
-                                                _ptr(cur) if levels is None else None, _ptr(lut), _ptr(la), _ptr(lb),
-                                                _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state), _ptr(events), _stream()),
-                "enslam_event_sim_images")
-    return events
-
-
-def event_sim_boxroom(room, poses, cam, state, eps=1e-3, c_pos=0.2, c_neg=0.2, c_pos_map=None, c_neg_map=None, init=False,
-                      want_frame=False):
-    """One interval of the analytic route (enslam_event_sim_boxroom, enslam_hip.h): the kernel renders synthetic.BoxRoom
-    `room` at the K poses `poses` (float64 [K,3|4,4] camera-to-world on the state's device, or a host array that is uploaded;
-    the last one is the frame the interval ends at) for the camera `cam` (H, W, fx, fy, cx, cy) and returns the events uint8
-    [H,W,2] = (-, +); `state` (L_ref, float64 [H,W]) is updated in place.  want_frame: also (color float64 [H,W,3], depth
-    float32 [H,W]) of the last pose, what BoxRoom.render returns.  init: the first frame -- no events (None), state := L."""
-    what = "event_sim_boxroom"
-    if not torch.is_tensor(state):
-        raise L.EnslamError(f"{what}: state must be a tensor")
-    H, W = int(cam['H']), int(cam['W'])
-    dev = state.device
-    p = poses if torch.is_tensor(poses) else torch.as_tensor(poses)
-    if p.dim() != 3 or p.shape[1] not in (3, 4) or p.shape[2] != 4 or p.dtype != torch.float64:
-        raise L.EnslamError(f"{what}: poses must be float64 [K,3|4,4] (got {p.dtype} {tuple(p.shape)})")
-    _event_sim_checks(what, H, W, int(p.shape[0]), eps, c_pos, c_neg, state, c_pos_map, c_neg_map, init)
-    if torch.is_tensor(poses):
-        _require_hip(poses, f"{what}: a pose tensor")
-    if not (float(cam['fx']) != 0 and float(cam['fy']) != 0):
-        raise L.EnslamError(f"{what}: fx and fy must not be zero")
-    p = p[:, :3, :].to(dev).contiguous()
-    plan = event_sim_plan(H, W, p.shape[0], eps, c_pos, c_neg, init=init, cam=cam, room=room)
-    with torch.cuda.device(dev):
-        events = None if init else torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
-        color = torch.empty((H, W, 3), dtype=torch.float64, device=dev) if want_frame else None
-        depth = torch.empty((H, W), dtype=torch.float32, device=dev) if want_frame else None
-        L.check(L.lib().enslam_event_sim_boxroom(ctypes.byref(plan), _ptr(p), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state),
-                                                 _ptr(events), _ptr(color), _ptr(depth), _stream()), "enslam_event_sim_boxroom")
-    return (events, color, depth) if want_frame else events
-
-
-# ------------------------------------------------------------------------------------------------
-# Time-stamped event streams (csrc/event_stream.hip; event_sim.EventSimulator and event_stream.accumulate drive it)
-# ------------------------------------------------------------------------------------------------
-EVENT_ACCUMULATE_MAX_CELLS = 1 << 25        # B * H * W of one enslam_event_accumulate call (256 MiB of uint32 counts)
-
-
-def _event_stamps(what, stamps):
-    try:
-        t_a, t_b = (float(v) for v in stamps)
-    except (TypeError, ValueError):
-        raise L.EnslamError(f"{what}: stamps must be the pair (t_a, t_b) of the interval's frame times") from None
-    if not (t_a <= t_b and abs(t_a) < float('inf') and abs(t_b) < float('inf')):
-        raise L.EnslamError(f"{what}: stamps must be finite with t_a <= t_b (got {t_a}, {t_b})")
-    return t_a, t_b
-
-
-def _event_stream_run(what, count, emit, state, H, W, stamps):
-    """count -> prefix sum -> one read-back of the total -> emit; returns (events, (t, x, y, p))"""
-    if H > 65536 or W > 65536:
-        raise L.EnslamError(f"{what}: event coordinates are uint16, the sensor is {H} x {W}")
-    dev = state.device
-    with torch.cuda.device(dev):
-        counts = torch.empty((H, W), dtype=torch.int64, device=dev)
-        L.check(count(counts), what + " (count)")
-        ends = torch.cumsum(counts.view(-1), 0)
-        total = int(ends[-1].item())                            # the one read-back of the interval
-        if total > 2 ** 31 - 1:
-            raise L.EnslamError(f"{what}: {total} events in one interval (at most 2^31 - 1)")
-        events = torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
-        t = torch.empty(total, dtype=torch.float64, device=dev)
-        x, y = (torch.empty(total, dtype=torch.uint16, device=dev) for _ in range(2))
-        p = torch.empty(total, dtype=torch.uint8, device=dev)
-        L.check(emit(events, ends, total, stamps[0], stamps[1], t, x, y, p), what + " (emit)")
-    return events, (t, x, y, p)
-
-
-def event_stream_images(prev, cur, state, stamps, substeps=8, eps=1e-3, c_pos=0.2, c_neg=0.2, lut=None, levels=None,
-                        c_pos_map=None, c_neg_map=None):
-    """One interval of the image route with time stamps (enslam_event_stream_images_*, enslam_hip.h): the arguments of
-    `event_sim_images` plus stamps = (t_a, t_b), the times of the two frames.  Returns (events, (t, x, y, p)): the uint8
-    [H,W,2] image `event_sim_images` returns (and the same update of `state`), and the events as device tensors -- t float64,
-    x, y uint16, p uint8 (1 = positive) -- in pixel-major order, time-ordered within a pixel."""
-    what = "event_stream_images"
-    if not torch.is_tensor(state):
-        raise L.EnslamError(f"{what}: state must be a tensor")
-    H, W = (int(v) for v in state.shape) if state.dim() == 2 else (0, 0)
-    _event_sim_checks(what, H, W, substeps, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, False)
-    stamps = _event_stamps(what, stamps)
+    if stamps is not None:
+        stamps = _event_stamps(what, stamps)
     dev = state.device
     channels = 1
     if levels is not None:
@@ -3079,15 +2960,134 @@ def event_stream_images(prev, cur, state, stamps, substeps=8, eps=1e-3, c_pos=0.
             if lut is None:
                 raise L.EnslamError(f"{what}: grey images need the host-computed table `lut` (float64 [256])")
             _event_sim_tensor(what, 'lut', lut, torch.float64, (256,), dev)
-    plan = event_sim_plan(H, W, substeps, eps, c_pos, c_neg, channels=channels)
+    plan = event_sim_plan(H, W, substeps, eps, c_pos, c_neg, channels=channels, init=init)
     la, lb = levels if levels is not None else (None, None)
-    src = (ctypes.byref(plan), _ptr(prev), _ptr(cur), _ptr(lut), _ptr(la), _ptr(lb), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state))
-    lib = L.lib()
-    return _event_stream_run(
-        what, lambda counts: lib.enslam_event_stream_images_count(*src, _ptr(counts), _stream()),
-        lambda events, ends, total, t_a, t_b, t, x, y, p: lib.enslam_event_stream_images_emit(
-            *src, _ptr(events), _ptr(ends), total, t_a, t_b, _ptr(t), _ptr(x), _ptr(y), _ptr(p), _stream()),
-        state, H, W, stamps)
+    return H, W, stamps, (ctypes.byref(plan), _ptr(prev), _ptr(cur), _ptr(lut), _ptr(la), _ptr(lb), _ptr(c_pos_map),
+                          _ptr(c_neg_map), _ptr(state))
+
+
+def _event_room_source(what, room, poses, cam, state, stamps, eps, c_pos, c_neg, c_pos_map, c_neg_map, with_prev, init):
+    """Validates the analytic source of one interval (stamps None: the frame entry; with_prev: row 0 of `poses` is the previous
+    frame's) and returns (H, W, K, stamps, rows, src): rows the poses float64 [K(+1),3,4] on the device, which the caller keeps
+    alive across its launches, and src the arguments the three *_boxroom entries share, from the plan to L_ref."""
+    if not torch.is_tensor(state):
+        raise L.EnslamError(f"{what}: state must be a tensor")
+    H, W = int(cam['H']), int(cam['W'])
+    p = poses if torch.is_tensor(poses) else torch.as_tensor(poses)
+    if p.dim() != 3 or (with_prev and p.shape[0] < 2) or p.shape[1] not in (3, 4) or p.shape[2] != 4 or p.dtype != torch.float64:
+        want = "[K+1,3|4,4], the previous frame's first" if with_prev else "[K,3|4,4]"
+        raise L.EnslamError(f"{what}: poses must be float64 {want} (got {p.dtype} {tuple(p.shape)})")
+    K = int(p.shape[0]) - int(with_prev)
+    _event_sim_checks(what, H, W, K, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, init)
+    if stamps is not None:
+        stamps = _event_stamps(what, stamps)
+    if torch.is_tensor(poses):
+        _require_hip(poses, f"{what}: a pose tensor")
+    if not (float(cam['fx']) != 0 and float(cam['fy']) != 0):
+        raise L.EnslamError(f"{what}: fx and fy must not be zero")
+    rows = p[:, :3, :].to(state.device).contiguous()
+    plan = event_sim_plan(H, W, K, eps, c_pos, c_neg, init=init, cam=cam, room=room)
+    return H, W, K, stamps, rows, (ctypes.byref(plan), _ptr(rows), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state))
+
+
+def event_sim_images(prev, cur, state, substeps=8, eps=1e-3, c_pos=0.2, c_neg=0.2, lut=None, levels=None, c_pos_map=None,
+                     c_neg_map=None, init=False):
+    """One interval of the image route (enslam_event_sim_images, enslam_hip.h): events uint8 [H,W,2] = (-, +) between two
+    decoded images, `state` (L_ref, float64 [H,W] on a HIP device) updated in place.
+
+      prev, cur  uint8 [H,W] / [H,W,1] (grey) or [H,W,3] (RGB) on the state's device
+      lut        float64 [256]: log(v / 255 + eps) of the grey values, computed by the host (required for grey images)
+      levels     (L_prev, L_cur) float64 [H,W]: host-computed log intensities used INSTEAD of the images (prev and cur may
+                 then be None), so that no device log decides a count
+      c_pos_map, c_neg_map  float64 [H,W] per-pixel thresholds replacing the scalars
+      init       the first frame: no events (None is returned), state := L of `cur`"""
+    H, W, _, src = _event_image_source("event_sim_images", prev, cur, state, None, substeps, eps, c_pos, c_neg, c_pos_map,
+                                       c_neg_map, lut, levels, init)
+    dev = state.device
+    with torch.cuda.device(dev):
+        events = None if init else torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
+        L.check(L.lib().enslam_event_sim_images(*src, _ptr(events), _stream()), "enslam_event_sim_images")
+    return events
+
+
+def event_sim_boxroom(room, poses, cam, state, eps=1e-3, c_pos=0.2, c_neg=0.2, c_pos_map=None, c_neg_map=None, init=False,
+                      want_frame=False):
+    """One interval of the analytic route (enslam_event_sim_boxroom, enslam_hip.h): the kernel renders synthetic.BoxRoom
+    `room` at the K poses `poses` (float64 [K,3|4,4] camera-to-world on the state's device, or a host array that is uploaded;
+    the last one is the frame the interval ends at) for the camera `cam` (H, W, fx, fy, cx, cy) and returns the events uint8
+    [H,W,2] = (-, +); `state` (L_ref, float64 [H,W]) is updated in place.  want_frame: also (color float64 [H,W,3], depth
+    float32 [H,W]) of the last pose, what BoxRoom.render returns.  init: the first frame -- no events (None), state := L."""
+    H, W, _, _, rows, src = _event_room_source("event_sim_boxroom", room, poses, cam, state, None, eps, c_pos, c_neg, c_pos_map,
+                                               c_neg_map, False, init)
+    dev = state.device
+    with torch.cuda.device(dev):
+        events = None if init else torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
+        color = torch.empty((H, W, 3), dtype=torch.float64, device=dev) if want_frame else None
+        depth = torch.empty((H, W), dtype=torch.float32, device=dev) if want_frame else None
+        L.check(L.lib().enslam_event_sim_boxroom(*src, _ptr(events), _ptr(color), _ptr(depth), _stream()), "enslam_event_sim_boxroom")
+    return (events, color, depth) if want_frame else events
+
+
+# ------------------------------------------------------------------------------------------------
+# Time-stamped event streams (csrc/event_stream.hip; event_sim.EventSimulator and event_stream.accumulate drive it)
+# ------------------------------------------------------------------------------------------------
+EVENT_ACCUMULATE_MAX_CELLS = 1 << 25        # B * H * W of one enslam_event_accumulate call (256 MiB of uint32 counts)
+
+
+def _event_stamps(what, stamps):
+    try:
+        t_a, t_b = (float(v) for v in stamps)
+    except (TypeError, ValueError):
+        raise L.EnslamError(f"{what}: stamps must be the pair (t_a, t_b) of the interval's frame times") from None
+    if not (t_a <= t_b and abs(t_a) < float('inf') and abs(t_b) < float('inf')):
+        raise L.EnslamError(f"{what}: stamps must be finite with t_a <= t_b (got {t_a}, {t_b})")
+    return t_a, t_b
+
+
+def _event_stream_run(what, route, src, state, H, W, stamps, count_src=None, noise=None, t_last=None, stream=True):
+    """The launches of one interval with time stamps on `route` ('images' / 'boxroom') from the source arguments `src`
+    (`count_src`: what the count entry takes instead).  noise None: enslam_event_stream_*; otherwise the enslam_event_noise of
+    the interval, for enslam_event_noisy_* with `t_last`.  stream: count -> prefix sum -> one read-back of the total -> emit,
+    returns (events, (t, x, y, p)); otherwise (the noisy sensor only) the one launch of the count-image-only form, returns
+    events."""
+    if H > 65536 or W > 65536:
+        raise L.EnslamError(f"{what}: event coordinates are uint16, the sensor is {H} x {W}")
+    count_tail, emit_tail = (), ()
+    if noise is not None:
+        _event_sim_tensor(what, 't_last', t_last, torch.float64, (H, W), state.device)
+        count_tail, emit_tail = (ctypes.byref(noise), *stamps, _ptr(t_last)), (ctypes.byref(noise), _ptr(t_last))
+    lib, family = L.lib(), f"enslam_event_{'stream' if noise is None else 'noisy'}_{route}_"
+    emit = getattr(lib, family + 'emit')
+    dev = state.device
+    with torch.cuda.device(dev):
+        events = torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
+        if not stream:
+            L.check(emit(*src, _ptr(events), None, 0, *stamps, None, None, None, None, *emit_tail, _stream()), what + " (image)")
+            return events
+        counts = torch.empty((H, W), dtype=torch.int64, device=dev)
+        L.check(getattr(lib, family + 'count')(*(count_src or src), _ptr(counts), *count_tail, _stream()), what + " (count)")
+        ends = torch.cumsum(counts.view(-1), 0)
+        total = int(ends[-1].item())                            # the one read-back of the interval
+        if total > 2 ** 31 - 1:
+            raise L.EnslamError(f"{what}: {total} events in one interval (at most 2^31 - 1)")
+        t = torch.empty(total, dtype=torch.float64, device=dev)
+        x, y = (torch.empty(total, dtype=torch.uint16, device=dev) for _ in range(2))
+        p = torch.empty(total, dtype=torch.uint8, device=dev)
+        L.check(emit(*src, _ptr(events), _ptr(ends), total, *stamps, _ptr(t), _ptr(x), _ptr(y), _ptr(p), *emit_tail, _stream()),
+                what + " (emit)")
+    return events, (t, x, y, p)
+
+
+def event_stream_images(prev, cur, state, stamps, substeps=8, eps=1e-3, c_pos=0.2, c_neg=0.2, lut=None, levels=None,
+                        c_pos_map=None, c_neg_map=None):
+    """One interval of the image route with time stamps (enslam_event_stream_images_*, enslam_hip.h): the arguments of
+    `event_sim_images` plus stamps = (t_a, t_b), the times of the two frames.  Returns (events, (t, x, y, p)): the uint8
+    [H,W,2] image `event_sim_images` returns (and the same update of `state`), and the events as device tensors -- t float64,
+    x, y uint16, p uint8 (1 = positive) -- in pixel-major order, time-ordered within a pixel."""
+    what = "event_stream_images"
+    H, W, stamps, src = _event_image_source(what, prev, cur, state, stamps, substeps, eps, c_pos, c_neg, c_pos_map, c_neg_map, lut,
+                                            levels, False)
+    return _event_stream_run(what, 'images', src, state, H, W, stamps)
 
 
 def event_stream_boxroom(room, poses, cam, state, stamps, eps=1e-3, c_pos=0.2, c_neg=0.2, c_pos_map=None, c_neg_map=None):
@@ -3096,31 +3096,10 @@ def event_stream_boxroom(room, poses, cam, state, stamps, eps=1e-3, c_pos=0.2, c
     sub-steps, the last one the frame the interval ends at; stamps = (t_a, t_b).  Returns (events, (t, x, y, p)) as
     `event_stream_images`; `state` is updated as `event_sim_boxroom` updates it."""
     what = "event_stream_boxroom"
-    if not torch.is_tensor(state):
-        raise L.EnslamError(f"{what}: state must be a tensor")
-    H, W = int(cam['H']), int(cam['W'])
-    dev = state.device
-    p = poses if torch.is_tensor(poses) else torch.as_tensor(poses)
-    if p.dim() != 3 or p.shape[0] < 2 or p.shape[1] not in (3, 4) or p.shape[2] != 4 or p.dtype != torch.float64:
-        raise L.EnslamError(f"{what}: poses must be float64 [K+1,3|4,4], the previous frame's first (got {p.dtype} {tuple(p.shape)})")
-    K = int(p.shape[0]) - 1
-    _event_sim_checks(what, H, W, K, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, False)
-    stamps = _event_stamps(what, stamps)
-    if torch.is_tensor(poses):
-        _require_hip(poses, f"{what}: a pose tensor")
-    if not (float(cam['fx']) != 0 and float(cam['fy']) != 0):
-        raise L.EnslamError(f"{what}: fx and fy must not be zero")
-    p = p[:, :3, :].to(dev).contiguous()
-    sub = p[1:]                                                 # contiguous: the K sub-step poses of the count pass
-    plan = event_sim_plan(H, W, K, eps, c_pos, c_neg, cam=cam, room=room)
-    maps = (_ptr(c_pos_map), _ptr(c_neg_map), _ptr(state))
-    lib = L.lib()
-    return _event_stream_run(
-        what, lambda counts: lib.enslam_event_stream_boxroom_count(ctypes.byref(plan), _ptr(sub), *maps, _ptr(counts), _stream()),
-        lambda events, ends, total, t_a, t_b, t, x, y, q: lib.enslam_event_stream_boxroom_emit(
-            ctypes.byref(plan), _ptr(p), *maps, _ptr(events), _ptr(ends), total, t_a, t_b, _ptr(t), _ptr(x), _ptr(y), _ptr(q),
-            _stream()),
-        state, H, W, stamps)
+    H, W, _, stamps, rows, src = _event_room_source(what, room, poses, cam, state, stamps, eps, c_pos, c_neg, c_pos_map, c_neg_map,
+                                                    True, False)
+    sub = rows[1:]                                              # contiguous: the K sub-step poses of the count pass
+    return _event_stream_run(what, 'boxroom', src, state, H, W, stamps, count_src=(src[0], _ptr(sub)) + src[2:])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -3145,31 +3124,6 @@ def event_noise_params(what, noise, substeps, stamps):
     return n
 
 
-def _event_noisy_run(what, count, emit, state, t_last, H, W, stamps, stream):
-    """stream: count -> prefix sum -> one read-back of the total -> emit, returns (events, (t, x, y, p)); otherwise the one
-    launch of the count-image-only form, returns events"""
-    if H > 65536 or W > 65536:
-        raise L.EnslamError(f"{what}: event coordinates are uint16, the sensor is {H} x {W}")
-    _event_sim_tensor(what, 't_last', t_last, torch.float64, (H, W), state.device)
-    dev = state.device
-    with torch.cuda.device(dev):
-        events = torch.empty((H, W, 2), dtype=torch.uint8, device=dev)
-        if not stream:
-            L.check(emit(events, None, 0, stamps[0], stamps[1], None, None, None, None), what + " (image)")
-            return events
-        counts = torch.empty((H, W), dtype=torch.int64, device=dev)
-        L.check(count(counts, stamps[0], stamps[1]), what + " (count)")
-        ends = torch.cumsum(counts.view(-1), 0)
-        total = int(ends[-1].item())                            # the one read-back of the interval
-        if total > 2 ** 31 - 1:
-            raise L.EnslamError(f"{what}: {total} events in one interval (at most 2^31 - 1)")
-        t = torch.empty(total, dtype=torch.float64, device=dev)
-        x, y = (torch.empty(total, dtype=torch.uint16, device=dev) for _ in range(2))
-        p = torch.empty(total, dtype=torch.uint8, device=dev)
-        L.check(emit(events, ends, total, stamps[0], stamps[1], t, x, y, p), what + " (emit)")
-    return events, (t, x, y, p)
-
-
 def event_noisy_images(prev, cur, state, t_last, stamps, noise, substeps=8, eps=1e-3, c_pos=0.2, c_neg=0.2, lut=None, levels=None,
                        c_pos_map=None, c_neg_map=None, stream=True):
     """One interval of the image route through the noisy sensor (enslam_event_noisy_images_*, enslam_hip.h): the arguments of
@@ -3177,46 +3131,10 @@ def event_noisy_images(prev, cur, state, t_last, stamps, noise, substeps=8, eps=
     leak_rate, shot_rate, seed, interval).  stream=True: (events, (t, x, y, p)) of the EMITTED events, two launches;
     stream=False: events alone, one launch."""
     what = "event_noisy_images"
-    if not torch.is_tensor(state):
-        raise L.EnslamError(f"{what}: state must be a tensor")
-    H, W = (int(v) for v in state.shape) if state.dim() == 2 else (0, 0)
-    _event_sim_checks(what, H, W, substeps, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, False)
-    stamps = _event_stamps(what, stamps)
-    dev = state.device
-    channels = 1
-    if levels is not None:
-        if len(levels) != 2:
-            raise L.EnslamError(f"{what}: levels must be the pair (L_prev, L_cur)")
-        for name, t in zip(('L_prev', 'L_cur'), levels):
-            _event_sim_tensor(what, name, t, torch.float64, (H, W), dev)
-        prev = cur = None
-    else:
-        if not torch.is_tensor(prev) or not torch.is_tensor(cur):
-            raise L.EnslamError(f"{what}: prev and cur must be tensors (or pass `levels`)")
-        for name, t in (('prev', prev), ('cur', cur)):
-            if t.dim() not in (2, 3) or t.shape != cur.shape:
-                raise L.EnslamError(f"{what}: prev and cur must be uint8 tensors of one shape [H,W] or [H,W,C]")
-            shape = (H, W) if t.dim() == 2 else (H, W, int(t.shape[2]))
-            if t.dim() == 3 and shape[2] not in (1, 3):
-                raise L.EnslamError(f"{what}: images must have 1 or 3 channels (got {shape[2]})")
-            _event_sim_tensor(what, name, t, torch.uint8, shape, dev)
-        channels = 3 if cur.dim() == 3 and cur.shape[2] == 3 else 1
-        if channels == 1:
-            if lut is None:
-                raise L.EnslamError(f"{what}: grey images need the host-computed table `lut` (float64 [256])")
-            _event_sim_tensor(what, 'lut', lut, torch.float64, (256,), dev)
-    plan = event_sim_plan(H, W, substeps, eps, c_pos, c_neg, channels=channels)
+    H, W, stamps, src = _event_image_source(what, prev, cur, state, stamps, substeps, eps, c_pos, c_neg, c_pos_map, c_neg_map, lut,
+                                            levels, False)
     params = event_noise_params(what, noise, int(substeps), stamps)
-    la, lb = levels if levels is not None else (None, None)
-    src = (ctypes.byref(plan), _ptr(prev), _ptr(cur), _ptr(lut), _ptr(la), _ptr(lb), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state))
-    lib = L.lib()
-    return _event_noisy_run(
-        what, lambda counts, t_a, t_b: lib.enslam_event_noisy_images_count(*src, _ptr(counts), ctypes.byref(params), t_a, t_b,
-                                                                           _ptr(t_last), _stream()),
-        lambda events, ends, total, t_a, t_b, t, x, y, p: lib.enslam_event_noisy_images_emit(
-            *src, _ptr(events), _ptr(ends), total, t_a, t_b, _ptr(t), _ptr(x), _ptr(y), _ptr(p), ctypes.byref(params), _ptr(t_last),
-            _stream()),
-        state, t_last, H, W, stamps, stream)
+    return _event_stream_run(what, 'images', src, state, H, W, stamps, noise=params, t_last=t_last, stream=stream)
 
 
 def event_noisy_boxroom(room, poses, cam, state, t_last, stamps, noise, eps=1e-3, c_pos=0.2, c_neg=0.2, c_pos_map=None,
@@ -3225,32 +3143,10 @@ def event_noisy_boxroom(room, poses, cam, state, t_last, stamps, noise, eps=1e-3
     of `event_stream_boxroom` (poses float64 [K+1,3|4,4], the previous frame's first) plus `t_last` and `noise` as in
     `event_noisy_images`; both passes read all K + 1 poses."""
     what = "event_noisy_boxroom"
-    if not torch.is_tensor(state):
-        raise L.EnslamError(f"{what}: state must be a tensor")
-    H, W = int(cam['H']), int(cam['W'])
-    dev = state.device
-    p = poses if torch.is_tensor(poses) else torch.as_tensor(poses)
-    if p.dim() != 3 or p.shape[0] < 2 or p.shape[1] not in (3, 4) or p.shape[2] != 4 or p.dtype != torch.float64:
-        raise L.EnslamError(f"{what}: poses must be float64 [K+1,3|4,4], the previous frame's first (got {p.dtype} {tuple(p.shape)})")
-    K = int(p.shape[0]) - 1
-    _event_sim_checks(what, H, W, K, eps, c_pos, c_neg, state, c_pos_map, c_neg_map, False)
-    stamps = _event_stamps(what, stamps)
-    if torch.is_tensor(poses):
-        _require_hip(poses, f"{what}: a pose tensor")
-    if not (float(cam['fx']) != 0 and float(cam['fy']) != 0):
-        raise L.EnslamError(f"{what}: fx and fy must not be zero")
-    p = p[:, :3, :].to(dev).contiguous()
-    plan = event_sim_plan(H, W, K, eps, c_pos, c_neg, cam=cam, room=room)
+    H, W, K, stamps, rows, src = _event_room_source(what, room, poses, cam, state, stamps, eps, c_pos, c_neg, c_pos_map, c_neg_map,
+                                                    True, False)
     params = event_noise_params(what, noise, K, stamps)
-    src = (ctypes.byref(plan), _ptr(p), _ptr(c_pos_map), _ptr(c_neg_map), _ptr(state))
-    lib = L.lib()
-    return _event_noisy_run(
-        what, lambda counts, t_a, t_b: lib.enslam_event_noisy_boxroom_count(*src, _ptr(counts), ctypes.byref(params), t_a, t_b,
-                                                                            _ptr(t_last), _stream()),
-        lambda events, ends, total, t_a, t_b, t, x, y, q: lib.enslam_event_noisy_boxroom_emit(
-            *src, _ptr(events), _ptr(ends), total, t_a, t_b, _ptr(t), _ptr(x), _ptr(y), _ptr(q), ctypes.byref(params), _ptr(t_last),
-            _stream()),
-        state, t_last, H, W, stamps, stream)
+    return _event_stream_run(what, 'boxroom', src, state, H, W, stamps, noise=params, t_last=t_last, stream=stream)
 
 
 def event_accumulate(t, x, y, p, edges, H, W, want_unsaturated=False):
