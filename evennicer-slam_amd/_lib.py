@@ -351,6 +351,11 @@ _SIGS = {
     "enslam_ssim_workspace": (ctypes.c_int, [c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "enslam_ssim": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                    c_void_p]),
+    "enslam_event_model_workspace": (ctypes.c_int, [c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "enslam_event_model_loss": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, ctypes.c_float, ctypes.c_float,
+                                               ctypes.c_float, c_int32, POINTER(c_int32), POINTER(ctypes.c_float),
+                                               POINTER(ctypes.c_float), c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

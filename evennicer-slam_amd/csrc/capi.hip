@@ -1236,3 +1236,48 @@ int enslam_plan_backward(const enslam_step_plan* plan, const enslam_step_layout*
     return enslam_step_finish_native(nc, csrc, cdst, cvox, cneed, nullptr, npk, kinds, pk, parts, gs, plan->stage, ray_pending ? N : 0, S, rays_o,
                                      rays_d, z, &sc, ray_pending ? dgw : nullptr, p_ro, p_rd, work, wcount, nullptr, nullptr, 0, stream);
 }
+
+// ---- event-generation-model loss (event_model.hip) ------------------------------------------------------------------
+namespace {
+// ENSLAM_OK, or the refusal of the header for these sizes and scalars (no pointer is looked at)
+int event_model_sizes(int32_t h, int32_t w, int32_t K) {
+    if (h <= 0 || w <= 0 || K < 0) return ENSLAM_EINVAL;
+    if (K > ENSLAM_EVENT_MODEL_MAX_KERNELS || h > 32768 || w > 32768 || (int64_t)h * w > ((int64_t)1 << 28)) return ENSLAM_EUNSUPPORTED;
+    return ENSLAM_OK;
+}
+}  // namespace
+
+int enslam_event_model_workspace(int32_t h, int32_t w, int32_t K, int64_t* bytes_host) {
+    if (!bytes_host) return ENSLAM_EINVAL;
+    const int rc = event_model_sizes(h, w, K);
+    if (rc != ENSLAM_OK) return rc;
+    *bytes_host = ens_event_model_workspace_bytes(h, w, K);
+    return ENSLAM_OK;
+}
+
+int enslam_event_model_loss(const float* cur, const float* prev, const float* gt, int32_t h, int32_t w, float c_neg, float c_pos,
+                            float eps, int32_t K, const int32_t* ksizes, const float* weights, const float* taps, void* workspace,
+                            int64_t workspace_bytes, float* pred, double* sums, float* grad, float* blur_gt, float* blur_pred,
+                            void* stream) {
+    if (!cur || !prev || !gt || !workspace || !pred || !sums || !grad) return ENSLAM_EINVAL;
+    if ((blur_gt == nullptr) != (blur_pred == nullptr)) return ENSLAM_EINVAL;
+    if (!(c_neg > 0.f) || !(c_pos > 0.f) || !(eps > 0.f)) return ENSLAM_EINVAL;
+    if (h <= 0 || w <= 0 || K < 0) return ENSLAM_EINVAL;
+    if (K > 0 && (!ksizes || !weights || !taps)) return ENSLAM_EINVAL;
+    if (K > ENSLAM_EVENT_MODEL_MAX_KERNELS) return ENSLAM_EUNSUPPORTED;
+    for (int i = 0; i < K; ++i)
+        if (ksizes[i] <= 0 || ksizes[i] % 2 == 0) return ENSLAM_EINVAL;
+    for (int i = 0; i < K; ++i)
+        if (ksizes[i] > ENSLAM_EVENT_MODEL_MAX_KSIZE) return ENSLAM_EUNSUPPORTED;
+    for (int i = 0; i < K; ++i)
+        if (ksizes[i] / 2 >= (h < w ? h : w)) return ENSLAM_EINVAL;
+    const int rc = event_model_sizes(h, w, K);
+    if (rc != ENSLAM_OK) return rc;
+    if (workspace_bytes < ens_event_model_workspace_bytes(h, w, K) || ((uintptr_t)workspace & 7u) || ((uintptr_t)sums & 7u))
+        return ENSLAM_EINVAL;
+    EventModelJob J;
+    J.cur = cur; J.prev = prev; J.gt = gt; J.h = h; J.w = w; J.K = K; J.c_neg = c_neg; J.c_pos = c_pos; J.eps = eps;
+    J.ksizes = ksizes; J.weights = weights; J.taps = taps; J.workspace = workspace; J.pred = pred; J.sums = sums; J.grad = grad;
+    J.blur_gt = blur_gt; J.blur_pred = blur_pred;
+    return ens_launch_event_model(J, (hipStream_t)stream);
+}

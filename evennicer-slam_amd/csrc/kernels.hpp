@@ -207,3 +207,23 @@ int ens_launch_decoder_bwd(int stage, int ntl, int n_rays, const float* ro, cons
 int ens_launch_grid_scatter(int stage, int ntl, int n_rays, const float* ro, const float* rd, const double* z, const DevScene& sc,
                             const float* dgrid_ws, const float* d_raw, const DevGrid* grad_grids, hipStream_t st);
 int ens_bwd_max_workgroups();      // upper bound of the workgroups of one decoder role (rows of a partial buffer)
+
+// event-generation-model loss (event_model.hip; enslam_event_model_loss of the header).  ksizes, weights and taps are host arrays.
+struct EventModelJob {
+    const float* cur;
+    const float* prev;
+    const float* gt;
+    int h, w, K;
+    float c_neg, c_pos, eps;
+    const int32_t* ksizes;          // [K]
+    const float* weights;           // [K]
+    const float* taps;              // [K][ENSLAM_EVENT_MODEL_MAX_KSIZE]
+    void* workspace;                // ens_event_model_workspace_bytes
+    float* pred;
+    double* sums;                   // [K + 2]
+    float* grad;
+    float* blur_gt;                 // [K,h,w,2], both or neither
+    float* blur_pred;
+};
+int64_t ens_event_model_workspace_bytes(int h, int w, int K);
+int ens_launch_event_model(const EventModelJob& job, hipStream_t st);

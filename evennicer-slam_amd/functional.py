@@ -3424,3 +3424,77 @@ def ssim(x, y, want_map=False):
         L.check(lib.enslam_ssim(_ptr(a), _ptr(b), H, W, C, _ptr(ws), nbytes.value, _ptr(mean), _ptr(smap), _stream()),
                 "enslam_ssim")
     return (mean, smap) if want_map else mean
+
+
+# ------------------------------------------------------------------------------------------------
+# event-generation-model loss (csrc/event_model.hip; event_model.py is the caller)
+# ------------------------------------------------------------------------------------------------
+EVENT_MODEL_TILE, EVENT_MODEL_MAX_KERNELS, EVENT_MODEL_MAX_KSIZE = 16, 4, 31
+_event_model_host = {}
+
+
+def event_model_kernels(kernel_sizes, kernel_weights):
+    """The host arrays of enslam_event_model_loss for these Gaussian kernels: (K, ksizes int32 [K], weights float32 [K], taps
+    float32 [K][EVENT_MODEL_MAX_KSIZE]) with the taps of event.gaussian_kernel1d (float32, the numbers event.gaussian_blur
+    convolves with).  Raises EnslamError for what the entry refuses.  Cached per (sizes, weights)."""
+    key = (tuple(int(k) for k in kernel_sizes), tuple(float(x) for x in kernel_weights))
+    got = _event_model_host.get(key)
+    if got is not None:
+        return got
+    from .event import gaussian_kernel1d
+    ks, ws = key
+    if len(ks) != len(ws):
+        raise L.EnslamError(f"event_model_loss: {len(ks)} kernel sizes but {len(ws)} kernel weights")
+    if len(ks) > EVENT_MODEL_MAX_KERNELS:
+        raise L.EnslamError(f"event_model_loss: at most {EVENT_MODEL_MAX_KERNELS} Gaussian kernels (got {len(ks)})")
+    for k in ks:
+        if k <= 0 or k % 2 == 0:
+            raise L.EnslamError(f"event_model_loss: kernel sizes must be odd and positive (got {k})")
+        if k > EVENT_MODEL_MAX_KSIZE:
+            raise L.EnslamError(f"event_model_loss: kernel sizes up to {EVENT_MODEL_MAX_KSIZE} (got {k})")
+    K = len(ks)
+    taps = (ctypes.c_float * (max(K, 1) * EVENT_MODEL_MAX_KSIZE))()
+    for i, k in enumerate(ks):
+        for t, v in enumerate(gaussian_kernel1d(k, dtype=torch.float32).tolist()):
+            taps[i * EVENT_MODEL_MAX_KSIZE + t] = v
+    got = _event_model_host[key] = (K, (ctypes.c_int32 * max(K, 1))(*ks), (ctypes.c_float * max(K, 1))(*ws), taps)
+    return got
+
+
+def event_model_loss(cur, prev, gt, c_neg=0.2, c_pos=0.2, eps=1e-3, kernel_sizes=(9,), kernel_weights=(1.0,), want_blurred=False):
+    """enslam_event_model_loss (enslam_hip.h) on contiguous float32 HIP tensors cur, prev [h,w,3] and gt [h,w,2]: (pred
+    float32 [h,w,2], sums float64 [K + 2] = the raw term, the K blurred terms, the loss, grad float32 [h,w,3] = dloss/dcur,
+    blur_gt, blur_pred float32 [K,h,w,2] or None).  Two launches on the current stream, no synchronisation."""
+    what = "event_model_loss"
+    for name, t, ch in (('cur', cur, 3), ('prev', prev, 3), ('gt', gt, 2)):
+        if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != ch or t.dtype is not torch.float32 or not t.is_contiguous():
+            raise L.EnslamError(f"{what}: {name} must be a contiguous float32 tensor [h,w,{ch}] (got "
+                                f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__})")
+        _require_hip(t, name)
+    h, w = int(cur.shape[0]), int(cur.shape[1])
+    if tuple(prev.shape[:2]) != (h, w) or tuple(gt.shape[:2]) != (h, w) or prev.device != cur.device or gt.device != cur.device:
+        raise L.EnslamError(f"{what}: cur, prev and gt must share one resolution and device (got {tuple(cur.shape)}, "
+                            f"{tuple(prev.shape)}, {tuple(gt.shape)})")
+    if not (c_neg > 0 and c_pos > 0 and eps > 0):
+        raise L.EnslamError(f"{what}: c_neg, c_pos and eps must be positive (got {c_neg}, {c_pos}, {eps})")
+    K, ksizes, weights, taps = event_model_kernels(kernel_sizes, kernel_weights)
+    for i in range(K):
+        if ksizes[i] // 2 >= min(h, w):
+            raise L.EnslamError(f"{what}: kernel size {ksizes[i]} needs reflect padding of {ksizes[i] // 2} >= min(h, w) = "
+                                f"{min(h, w)}, which is undefined")
+    dev = cur.device
+    nbytes = ctypes.c_int64(0)
+    L.check(L.lib().enslam_event_model_workspace(h, w, K, ctypes.byref(nbytes)), "enslam_event_model_workspace")
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes.value // 8, 1), dtype=torch.float64, device=dev)
+        pred = torch.empty((h, w, 2), dtype=torch.float32, device=dev)
+        grad = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        sums = torch.empty(K + 2, dtype=torch.float64, device=dev)
+        bg = bp = None
+        if want_blurred and K > 0:
+            bg = torch.empty((K, h, w, 2), dtype=torch.float32, device=dev)
+            bp = torch.empty((K, h, w, 2), dtype=torch.float32, device=dev)
+        L.check(L.lib().enslam_event_model_loss(_ptr(cur), _ptr(prev), _ptr(gt), h, w, ctypes.c_float(c_neg), ctypes.c_float(c_pos),
+                                                ctypes.c_float(eps), K, ksizes, weights, taps, _ptr(ws), ws.numel() * 8, _ptr(pred),
+                                                _ptr(sums), _ptr(grad), _ptr(bg), _ptr(bp), _stream()), "enslam_event_model_loss")
+    return pred, sums, grad, bg, bp

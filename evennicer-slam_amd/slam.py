@@ -147,7 +147,9 @@ class SLAM:
             est = delta @ pre
         else:
             est = pre
-        use_event = self.event_net is not None and self.cfg['event'].get('activate_events', False)
+        # (predictor 'model': the contrast-threshold model predicts the events, no network is needed)
+        has_predictor = self.event_net is not None or self.cfg['event'].get('predictor', 'net') == 'model'
+        use_event = has_predictor and self.cfg['event'].get('activate_events', False)
         if t.get('graphed', False) and int(t['iters']) > 0:
             return self._track_graphed(idx, est, gt_color, gt_depth, gt_event, gt_mask, pre_gt_color, t, use_event)
         camera_tensor = get_tensor_from_camera(est.detach()).to(self.device).requires_grad_(True)

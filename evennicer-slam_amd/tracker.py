@@ -153,6 +153,13 @@ class TrackerIteration(object):
         self.blur = e['blur']
         self.kernel_sizes, self.kernel_weights = e['kernel_sizes'], e['kernel_weights']
         self.unblurred_weight = e['unblurred_weight']
+        # 'net' (the default): the event image is predicted by slam.event_net; 'model': by the contrast-threshold model
+        # (event_model.EventModelLoss), with the thresholds and eps the events were generated with -- no network
+        self.event_predictor = e.get('predictor', 'net')
+        if self.event_predictor not in ('net', 'model'):
+            raise ValueError(f"cfg['event']['predictor'] must be 'net' or 'model' (got {self.event_predictor!r})")
+        self.event_c_pos, self.event_c_neg = float(e.get('c_pos', 0.2)), float(e.get('c_neg', 0.2))
+        self.event_eps = float(e.get('eps', 1e-3))
         self.c = None
         self.decoders = None
         # (int64 [n_draws, n] pixel indices, int32 [1] counter) when the draws of a frame are made ahead (GraphedCameraIteration)
@@ -288,26 +295,37 @@ class TrackerIteration(object):
                          scale_factor=0.1, static_shapes=False):
         """Loss tensors of one camera iteration, nothing synchronised: dict with `total` (what is back-propagated;
         None when nothing is), `rgbd`, `event` (balanced), `mask`, `full_event`, `event_mask`, `gts_blurred`,
-        `preds_blurred`, `terms`.  `frame` = prepare_event_frame(...) (needed when event)."""
+        `preds_blurred`, `terms`.  `frame` = prepare_event_frame(...) (needed when event).  With `predictor: 'model'` the
+        event image comes from the contrast-threshold model: `mask` and `event_mask` stay None and no event_net is needed."""
         from . import event as EV
         out = dict(total=None, rgbd=None, event=None, mask=None, full_event=None, event_mask=None, gts_blurred=[],
                    preds_blurred=[], terms=[])
+        by_model = self.event_predictor == 'model'
         if event:
-            if self.event_net is None:
+            if self.event_net is None and not by_model:
                 raise RuntimeError("event=True needs slam.event_net")
             gt_event, gt_mask, full_color_previous = frame
             if self.low_gpu_mem and not static_shapes:
                 torch.cuda.empty_cache()
             full_color_current = self._render_rescaled(camera_tensor, gt_depth, scale_factor)      # :150
-            out['full_event'], out['event_mask'] = EV.inference_event(
-                net=self.event_net, img1=full_color_previous, img2=full_color_current, device=self.device, scale_factor=1.0,
-                out_threshold=0.5)                                                                  # :153
+            if not by_model:
+                out['full_event'], out['event_mask'] = EV.inference_event(
+                    net=self.event_net, img1=full_color_previous, img2=full_color_current, device=self.device, scale_factor=1.0,
+                    out_threshold=0.5)                                                              # :153
         if rgbd:
             out['rgbd'] = out['total'] = self._rgbd_loss(camera_tensor, gt_color, gt_depth, batch_size, static_shapes)
-        if event:
+        if event and by_model:
+            # prediction, loss and its gradient in one call; no mask loss (the reference never back-propagates it).  The blurred
+            # images are for the figure writer: a captured iteration does not return them and does not compute them
+            from .event_model import EventModelLoss
+            loss_event, out['full_event'], out['terms'], out['gts_blurred'], out['preds_blurred'] = EventModelLoss.apply(
+                full_color_current, full_color_previous, gt_event, self.event_c_neg, self.event_c_pos, self.event_eps, self.blur,
+                tuple(self.kernel_sizes), tuple(self.kernel_weights), self.unblurred_weight, not static_shapes)
+        elif event:
             loss_event, out['gts_blurred'], out['preds_blurred'], out['terms'] = EV.event_loss(     # :206-221
                 gt_event, out['full_event'], self.blur, self.kernel_sizes, self.unblurred_weight, self.kernel_weights)
             out['mask'] = torch.nn.functional.cross_entropy(out['event_mask'], gt_mask.permute(2, 0, 1).long())   # :224-225
+        if event:
             out['event'] = loss_event * self.cfg['event']['balancer']                               # :228-229
             if self.activate_events:
                 out['total'] = out['event'] if out['total'] is None else out['total'] + out['event'].to(out['total'].dtype)
@@ -319,7 +337,8 @@ class TrackerIteration(object):
         optimiser step.  Returns the reference's tuple:
         blur off: (loss_rgbd, loss_event, loss_mask, gt_event, full_event, gt_mask, P(event)[h,w]);
         blur on : (loss_rgbd, loss_event, loss_mask, gt_event, full_event, gts_blurred, preds_blurred, term_values,
-                   gt_mask, P(event)[h,w]).  With `event=False` the event entries are None (the reference raises a
+                   gt_mask, P(event)[h,w]).  With `predictor: 'model'` loss_mask and P(event) are None (there is no mask
+        head).  With `event=False` the event entries are None (the reference raises a
         NameError on its undefined lists in that case when blur is on)."""
         optimizer.zero_grad()
         frame = None

@@ -1275,6 +1275,47 @@ int enslam_ssim_workspace(int32_t H, int32_t W, int32_t C, int64_t *bytes_host);
 int enslam_ssim(const float *x, const float *y, int32_t H, int32_t W, int32_t C, void *workspace, int64_t workspace_bytes,
                 double *mean_out, double *map_out, void *stream);
 
+/* Event-generation-model loss (event_model.py, csrc/event_model.hip): the tracker's event term without a network.  The
+ * event image between the previous colour frame and the colour rendered at the pose under optimisation is predicted with
+ * the contrast-threshold model of event_sim.py and compared with the recorded one.
+ *
+ * Inputs at the event resolution: cur float32 [h,w,3] (the rendered colour, carries the gradient), prev float32 [h,w,3],
+ * gt float32 [h,w,2] with channels (-, +).  Scalars c_neg, c_pos, eps > 0; K <= ENSLAM_EVENT_MODEL_MAX_KERNELS Gaussian
+ * kernels of odd size k_i <= ENSLAM_EVENT_MODEL_MAX_KSIZE with weight w_i.  ksizes (int32 [K]), weights (float32 [K]) and
+ * taps (float32 [K][ENSLAM_EVENT_MODEL_MAX_KSIZE], row i holds the k_i taps of kernel i from its first column) are HOST
+ * arrays, copied into the launch: the taps are event.gaussian_kernel1d's own numbers.  Per pixel, float32, every
+ * operation on its own (no contraction):
+ *     Y(a)   = max((0.299 a_R + 0.587 a_G) + 0.114 a_B, 0)
+ *     d      = log(Y(cur) + eps) - log(Y(prev) + eps)
+ *     pred_- = max(-d, 0) / c_neg,   pred_+ = max(d, 0) / c_pos          (d == 0: both 0, gradient 0)
+ *     r      = pred - gt
+ *     loss   = sum r^2 + sum_i w_i sum (B_i r)^2
+ * B_i is the separable Gaussian blur with reflect padding, per channel (event.gaussian_blur): rows first, then columns.
+ * Gradient: dloss/dr = 2 r + sum_i 2 w_i B_i^T B_i r with B^T the adjoint of the reflect-padded blur (a pixel p within
+ * k / 2 of a border also receives what was reflected onto it: in one dimension of length n, with C the zero-padded
+ * correlation of the taps, (B^T v)[p] = C(p) + [1 <= p <= k/2] C(-p) + [n - 1 - k/2 <= p <= n - 2] C(2 (n - 1) - p));
+ * d pred_+ / d cur_ch = [d > 0] w_ch / (c_pos (Y(cur) + eps)), d pred_- / d cur_ch = -[d < 0] w_ch / (c_neg (Y(cur) + eps)),
+ * zero where the luminance of cur was clamped (below 0).
+ *
+ * Outputs: pred float32 [h,w,2]; sums float64 [K + 2] = the raw term sum r^2, the K blurred terms sum (B_i r)^2, then the
+ * loss; grad float32 [h,w,3] = dloss/dcur; and, both or neither, blur_gt and blur_pred float32 [K,h,w,2] = B_i gt, B_i pred.
+ * One workgroup per ENSLAM_EVENT_MODEL_TILE x ENSLAM_EVENT_MODEL_TILE tile and channel stages r with a halo of 2 (k_max / 2)
+ * in LDS and runs the four passes out of it; squares are added in float64 per workgroup, then over the workgroups in index
+ * order by a second launch: no float atomics, no fences, the same bits in every run.  workspace: enslam_event_model_workspace
+ * bytes, 8-byte aligned.  Two launches, no host synchronisation: safe inside a stream capture.
+ * ENSLAM_EINVAL without a launch: a NULL pointer where data is required (K > 0: ksizes, weights, taps), only one of the
+ * blurred outputs, h or w <= 0, K < 0, a k that is even or <= 0, k / 2 >= min(h, w) (reflect padding is undefined), c_neg,
+ * c_pos or eps not > 0 (a NaN included), a workspace too small or misaligned.  ENSLAM_EUNSUPPORTED without a launch:
+ * K > ENSLAM_EVENT_MODEL_MAX_KERNELS, k > ENSLAM_EVENT_MODEL_MAX_KSIZE, h or w above 32768, more than 2^28 pixels. */
+#define ENSLAM_EVENT_MODEL_TILE 16
+#define ENSLAM_EVENT_MODEL_MAX_KERNELS 4
+#define ENSLAM_EVENT_MODEL_MAX_KSIZE 31
+int enslam_event_model_workspace(int32_t h, int32_t w, int32_t K, int64_t *bytes_host);
+int enslam_event_model_loss(const float *cur, const float *prev, const float *gt, int32_t h, int32_t w, float c_neg,
+                            float c_pos, float eps, int32_t K, const int32_t *ksizes, const float *weights,
+                            const float *taps, void *workspace, int64_t workspace_bytes, float *pred, double *sums,
+                            float *grad, float *blur_gt, float *blur_pred, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

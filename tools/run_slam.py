@@ -2,7 +2,7 @@
 
     python tools/run_slam.py CONFIG [--default-config PATH] [--input_folder DIR] [--event_folder DIR] [--output DIR]
                                     [--max-frames N] [--prepare host|device] [--prefit ITERS] [--device cuda:0]
-                                    [--event-net PATH] [--net-backend hip|torch] [--vis]
+                                    [--event-net PATH] [--net-backend hip|torch] [--event-predictor net|model] [--vis]
 
 CONFIG may name parents with `inherit_from` (config.load_config); --default-config is the root under a chain that names
 none (the reference passes configs/nice_slam.yaml).  The reference's YAML files are not part of this repository: point at
@@ -10,7 +10,9 @@ your own copy.  --prepare overrides `data.prepare` (frame preparation on the hos
 the decoders to a handful of ground-truth-posed frames first (SLAM.prefit_decoders, the stand-in for the reference's
 pretrained decoders); --event-net loads a state_dict (tools/train_event_net.py, or a reference checkpoint) into a frozen
 eval-mode UNet_2heads(6, 2, 2) and hands it to the harness as its event network, --net-backend picks `event.net_backend`
-for it (hip: event.compile_event_net); without --event-net the harness runs without one, as before.  Prints one JSON line: checkpoint path, frames, frames per second and the ATE."""
+for it (hip: event.compile_event_net); without --event-net the harness runs without one, as before; --event-predictor
+model sets `event.predictor`: the event term from the contrast-threshold model (event_model.py; thresholds `event.c_pos`,
+`event.c_neg`, `event.eps` of the configuration), which needs no network.  Prints one JSON line: checkpoint path, frames, frames per second and the ATE."""
 import argparse
 import copy
 import json
@@ -47,6 +49,7 @@ def main(argv=None):
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--event-net', default=None)
     ap.add_argument('--net-backend', choices=('hip', 'torch'), default=None)
+    ap.add_argument('--event-predictor', choices=('net', 'model'), default=None)
     ap.add_argument('--vis', action='store_true')
     args = ap.parse_args(argv)
 
@@ -59,6 +62,8 @@ def main(argv=None):
     cfg = load_config(args.config, args.default_config)
     if args.prepare is not None:
         cfg.setdefault('data', {})['prepare'] = args.prepare
+    if args.event_predictor is not None:
+        cfg.setdefault('event', {})['predictor'] = args.event_predictor
     output = args.output or cfg.get('data', {}).get('output') or 'output'
     ds = D.get_dataset(cfg, types.SimpleNamespace(input_folder=args.input_folder, event_folder=args.event_folder), cfg['scale'],
                        device=args.device)

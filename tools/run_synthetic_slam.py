@@ -9,11 +9,13 @@ the mapping window with mapping.keyframe_selection_method 'overlap' (mapper.keyf
 [--events simulate] writes the sequence with events simulated on the device (event_sim.EventSimulator over the trajectory,
 thresholds EVENT_C, default 0.2) instead of all-zero event images and sets event.activate_events; [--event-net PATH] loads a
 state_dict (tools/train_event_net.py) into a frozen eval-mode UNet_2heads(6, 2, 2) and hands it to the harness, which the
-event term needs; [--net-backend hip|torch] picks event.net_backend for it; [--vis DIR] keeps the tracked run's per-iteration
+event term needs; [--net-backend hip|torch] picks event.net_backend for it; [--event-predictor net|model]
+sets event.predictor ('model': the event term from the contrast-threshold model of event_model.py, no network needed) and
+[--c-pos C] [--c-neg C] its thresholds (default: what the simulator was given); [--vis DIR] keeps the tracked run's per-iteration
 figures (frame_vis.Visualizer: DIR/tracking_vis, DIR/mapping_vis; VIS_FREQ and VIS_INSIDE_FREQ, default 5 and 10, set both
 stages' vis_freq / vis_inside_freq); with --events simulate, [--refractory S] [--leak-rate HZ] [--shot-rate HZ] [--noise-seed N]
 switch the simulator to the noisy sensor (event_sim.EventNoise; the frame times are i / 30 s, those of
-tools/simulate_events.py's default --fps)."""
+tools/simulate_events.py's default --fps).  SEED (environment, default 0) seeds torch and numpy for each run."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -73,7 +75,7 @@ def mesh_metrics(slam, path, n_gt=200000, tsdf=False):
 
 
 def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=None, event_net=None, net_backend=None, vis=None,
-        noise=None):
+        noise=None, event_predictor=None, c_pos=None, c_neg=None):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -91,6 +93,10 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=Non
         extra = {}
         if events == 'simulate':
             cfg['event'] = dict(cfg['event'], activate_events=True)
+        if event_predictor is not None:
+            c_sim = float(os.environ.get('EVENT_C', 0.2))
+            cfg['event'] = dict(cfg['event'], predictor=event_predictor, c_pos=c_sim if c_pos is None else float(c_pos),
+                                c_neg=c_sim if c_neg is None else float(c_neg))
         if event_net is not None:
             from evennicer_slam_amd.event import UNet_2heads
             net = UNet_2heads(6, 2, 2)
@@ -105,7 +111,8 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=Non
             cfg['mapping'], cfg['tracking'] = dict(cfg['mapping'], **freq), dict(cfg['tracking'], **freq)
         ds = D.get_dataset(cfg, types.SimpleNamespace(input_folder=None, event_folder=None), 1, device=DEV)
         for tag, iters in ((('tracked', None),) if os.environ.get('SKIP_BASE') == '1' else (('tracked', None), ('const_speed_init', 0))):
-            torch.manual_seed(0); np.random.seed(0)
+            seed = int(os.environ.get('SEED', 0))
+            torch.manual_seed(seed); np.random.seed(seed)
             shown = vis is not None and tag == 'tracked'
             slam = SLAM(cfg, ds, vis if shown else os.path.join(tmp, 'out_' + tag), device=DEV, static_shapes=True,
                         verbose=os.environ.get('VERBOSE') == '1', **(dict(extra, vis=True) if shown else extra))
@@ -138,13 +145,16 @@ if __name__ == '__main__':
     if tsdf:
         args.remove('--tsdf')
     opts = {}
-    for flag, key in (('--events', 'events'), ('--event-net', 'event_net'), ('--net-backend', 'net_backend'), ('--vis', 'vis')):
+    for flag, key in (('--events', 'events'), ('--event-net', 'event_net'), ('--net-backend', 'net_backend'), ('--vis', 'vis'),
+                      ('--event-predictor', 'event_predictor'), ('--c-pos', 'c_pos'), ('--c-neg', 'c_neg')):
         if flag in args:
             k = args.index(flag)
             opts[key] = args[k + 1]
             del args[k:k + 2]
     if opts.get('events') not in (None, 'simulate'):
         raise SystemExit("--events takes 'simulate'")
+    if opts.get('event_predictor') not in (None, 'net', 'model'):
+        raise SystemExit("--event-predictor takes 'net' or 'model'")
     noise = {}
     for flag, key, kind in (('--refractory', 'refractory', float), ('--leak-rate', 'leak_rate', float), ('--shot-rate', 'shot_rate', float),
                             ('--noise-seed', 'seed', int)):
