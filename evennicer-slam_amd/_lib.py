@@ -356,6 +356,11 @@ _SIGS = {
                                                ctypes.c_float, c_int32, POINTER(c_int32), POINTER(ctypes.c_float),
                                                POINTER(ctypes.c_float), c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p]),
+    "enslam_event_cmax_workspace": (ctypes.c_int, [c_int32, c_int32, c_int64, c_int32, POINTER(c_int64)]),
+    "enslam_event_cmax_eval": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_double,
+                                              c_double, c_double, c_double, c_int32, POINTER(c_double), c_double, c_int32,
+                                              c_int32, POINTER(c_double), c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_int32, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

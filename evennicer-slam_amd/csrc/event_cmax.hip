@@ -1,0 +1,326 @@
+// Event motion compensation by contrast maximisation (enslam_event_cmax_eval; enslam_hip.h holds the model and fixes the order
+// of every float64 operation): the image of warped events of a stream under a candidate motion, the variance of its blur and
+// the gradient of that variance in the motion.  One evaluation is a fixed chain of launches on one stream:
+//
+//   vote     one thread per event: sensor check, time check, warp, the float64 range check, then up to four 64-bit integer
+//            atomic adds of llrint(w 2^32) into the int64 IWE (corners of weight 0 are not sent).  The three drop counters are
+//            summed per workgroup in LDS, then one global integer add per workgroup and counter.
+//   rows     one thread per pixel: r = the row pass of the zero-padded blur (of the IWE times 2^-32, or of J - mu)
+//   columns  one thread per pixel: the column pass; for J also the first level of SUM(J) (256 consecutive pixels per
+//            workgroup, halving tree in LDS, one partial per workgroup)
+//   upper    one workgroup: the partials 256 at a time through the same tree, thread 0 adds the results in ascending order
+//            and writes mu, f or the gradient
+//   centre   one thread per pixel: J - mu, and the first level of SUM((J - mu)^2)
+//   gather   one thread per event: the same warp, the four D values of its corners, its P products into the block tree in LDS
+// Integer atomics for the image, fixed trees for every float64 sum, no float atomics, no fences: two runs give the same
+// bits, and the numpy route of event_cmax.py, which performs the same operations in the same order, gives them too.
+// Every address comes from a checked value: the event's own x, y against the sensor before anything else, the warped
+// position against (-1, W) x (-1, H) in float64 before floor() and the conversion, every corner against the image.
+#include "../../include/enslam_hip.h"
+#include "common.hpp"
+
+#include <cmath>
+
+namespace {
+
+constexpr int CM_BLOCK = 256;
+constexpr int CM_KMAX = ENSLAM_CMAX_MAX_KSIZE;
+constexpr int CM_PMAX = 3;
+constexpr int64_t CM_MAX_EVENTS = 2147483647;
+constexpr int64_t CM_MAX_PIXELS = (int64_t)1 << 28;
+constexpr double CM_TWO32 = 4294967296.0;
+constexpr double CM_INV_TWO32 = 1.0 / 4294967296.0;
+
+struct CmStream {
+    const double* t;
+    const uint16_t* x;
+    const uint16_t* y;
+    const uint8_t* p;
+    int64_t N;
+    int32_t H, W, model, sign_votes;
+    double fx, fy, cx, cy, t_ref;
+    double theta[CM_PMAX];
+};
+
+struct CmBlur {
+    int32_t H, W, k;
+    double taps[CM_KMAX];
+};
+
+// what the header calls a vote: the cell (x0, y0), the fractions and the factors of the gradient
+struct CmWarp {
+    int x0, y0;
+    double a, b, oa, ob, mx, my, s;
+    double Bu[CM_PMAX], Bv[CM_PMAX];
+};
+
+enum { CM_OK = -1 };
+
+// CM_OK, or the drop counter of event i.  The operations and their order are the header's.
+__device__ __forceinline__ int cm_warp(const CmStream& S, int64_t i, CmWarp& Q) {
+    const unsigned ex = S.x[i], ey = S.y[i];
+    if (ex >= (unsigned)S.W || ey >= (unsigned)S.H) return ENSLAM_CMAX_DROP_SENSOR;
+    const double tv = S.t[i];
+    if (!std::isfinite(tv)) return ENSLAM_CMAX_DROP_TIME;
+    const double xd = (double)ex, yd = (double)ey;
+    const double dt = tv - S.t_ref;
+    double du, dv;
+    if (S.model == ENSLAM_CMAX_FLOW) {
+        Q.Bu[0] = 1.0 / S.fx; Q.Bu[1] = 0.0; Q.Bu[2] = 0.0;
+        Q.Bv[0] = 0.0; Q.Bv[1] = 1.0 / S.fy; Q.Bv[2] = 0.0;
+        du = S.theta[0] / S.fx;
+        dv = S.theta[1] / S.fy;
+    } else {
+        const double u = (xd - S.cx) / S.fx, v = (yd - S.cy) / S.fy;
+        const double uv = u * v, pu = 1.0 + u * u, pv = 1.0 + v * v;
+        Q.Bu[0] = uv; Q.Bu[1] = -pu; Q.Bu[2] = v;
+        Q.Bv[0] = pv; Q.Bv[1] = -uv; Q.Bv[2] = -u;
+        du = (uv * S.theta[0] - pu * S.theta[1]) + v * S.theta[2];
+        dv = (pv * S.theta[0] - uv * S.theta[1]) - u * S.theta[2];
+    }
+    Q.mx = -(dt * S.fx);
+    Q.my = -(dt * S.fy);
+    const double xw = xd + Q.mx * du, yw = yd + Q.my * dv;
+    if (!(xw > -1.0 && xw < (double)S.W && yw > -1.0 && yw < (double)S.H)) return ENSLAM_CMAX_DROP_WARP;
+    const double fx0 = floor(xw), fy0 = floor(yw);            // in [-1, W - 1] x [-1, H - 1]: the conversion is safe
+    Q.x0 = (int)fx0;
+    Q.y0 = (int)fy0;
+    Q.a = xw - fx0;
+    Q.b = yw - fy0;
+    Q.oa = 1.0 - Q.a;
+    Q.ob = 1.0 - Q.b;
+    Q.s = (S.sign_votes && !S.p[i]) ? -1.0 : 1.0;
+    return CM_OK;
+}
+
+__device__ __forceinline__ bool cm_corner(const CmStream& S, const CmWarp& Q, int c, int64_t& cell) {
+    const int px = Q.x0 + (c & 1), py = Q.y0 + (c >> 1);
+    if (px < 0 || px >= S.W || py < 0 || py >= S.H) return false;
+    cell = (int64_t)py * S.W + px;
+    return true;
+}
+
+__global__ __launch_bounds__(CM_BLOCK) void cmax_vote_kernel(CmStream S, unsigned long long* iwe, unsigned long long* dropped) {
+    __shared__ unsigned s_drop[3];
+    if (threadIdx.x < 3) s_drop[threadIdx.x] = 0u;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
+    if (i < S.N) {
+        CmWarp Q;
+        const int why = cm_warp(S, i, Q);
+        if (why != CM_OK) {
+            atomicAdd(&s_drop[why], 1u);
+        } else {
+            const double w[4] = {Q.oa * Q.ob, Q.a * Q.ob, Q.oa * Q.b, Q.a * Q.b};
+            for (int c = 0; c < 4; ++c) {
+                int64_t cell;
+                if (!cm_corner(S, Q, c, cell)) continue;
+                long long q = llrint(w[c] * CM_TWO32);
+                if (q == 0) continue;
+                if (Q.s < 0.0) q = -q;
+                atomicAdd(&iwe[cell], (unsigned long long)q);       // two's complement: the wrapped sum is the signed sum
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && s_drop[threadIdx.x]) atomicAdd(&dropped[threadIdx.x], (unsigned long long)s_drop[threadIdx.x]);
+}
+
+// the halving tree of the header over the workgroup's 256 values; every thread gets the result
+__device__ __forceinline__ double cm_block_sum(double* red, double v) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = CM_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double out = red[0];
+    __syncthreads();
+    return out;
+}
+
+__device__ __forceinline__ double cm_value(const long long* src, int64_t o) { return (double)src[o] * CM_INV_TWO32; }
+__device__ __forceinline__ double cm_value(const double* src, int64_t o) { return src[o]; }
+
+template <typename T>
+__global__ __launch_bounds__(CM_BLOCK) void cmax_rows_kernel(CmBlur B, const T* __restrict__ src, double* __restrict__ dst) {
+    const int64_t o = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
+    if (o >= (int64_t)B.H * B.W) return;
+    const int y = (int)(o / B.W), x = (int)(o - (int64_t)y * B.W), R = B.k / 2;
+    double acc = 0.0;
+    for (int i = 0; i < B.k; ++i) {
+        const int xs = x - R + i;
+        const double val = (xs >= 0 && xs < B.W) ? cm_value(src, (int64_t)y * B.W + xs) : 0.0;
+        acc += B.taps[i] * val;
+    }
+    dst[o] = acc;
+}
+
+// the column pass; SUM: also the workgroup's partial of SUM(dst)
+template <bool SUM>
+__global__ __launch_bounds__(CM_BLOCK) void cmax_cols_kernel(CmBlur B, const double* __restrict__ src, double* __restrict__ dst,
+                                                             double* __restrict__ partials) {
+    __shared__ double s_red[CM_BLOCK];
+    const int64_t o = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
+    const bool inside = o < (int64_t)B.H * B.W;
+    double acc = 0.0;
+    if (inside) {
+        const int y = (int)(o / B.W), x = (int)(o - (int64_t)y * B.W), R = B.k / 2;
+        for (int i = 0; i < B.k; ++i) {
+            const int ys = y - R + i;
+            const double val = (ys >= 0 && ys < B.H) ? src[(int64_t)ys * B.W + x] : 0.0;
+            acc += B.taps[i] * val;
+        }
+        dst[o] = acc;
+    }
+    if (SUM) {
+        const double tot = cm_block_sum(s_red, acc);
+        if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+    }
+}
+
+__global__ __launch_bounds__(CM_BLOCK) void cmax_centre_kernel(const double* __restrict__ J, const double* __restrict__ stats,
+                                                               int64_t npix, double* __restrict__ C, double* __restrict__ partials) {
+    __shared__ double s_red[CM_BLOCK];
+    const int64_t o = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
+    double sq = 0.0;
+    if (o < npix) {
+        const double c = J[o] - stats[0];
+        C[o] = c;
+        sq = c * c;
+    }
+    const double tot = cm_block_sum(s_red, sq);
+    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+}
+
+// The upper levels of SUM for `cols` interleaved columns of n partials: 256 at a time through the tree, the results added in
+// ascending order.  out[c] = scale_first ? scale * sum : sum / scale.
+__global__ __launch_bounds__(CM_BLOCK) void cmax_upper_kernel(const double* __restrict__ partials, int64_t n, int cols, double scale,
+                                                              int scale_first, double* __restrict__ out) {
+    __shared__ double s_red[CM_BLOCK];
+    for (int c = 0; c < cols; ++c) {
+        double acc = 0.0;
+        for (int64_t base = 0; base < n; base += CM_BLOCK) {
+            const int64_t i = base + threadIdx.x;
+            acc += cm_block_sum(s_red, i < n ? partials[i * cols + c] : 0.0);
+        }
+        if (threadIdx.x == 0) out[c] = scale_first ? scale * acc : acc / scale;
+    }
+}
+
+__global__ __launch_bounds__(CM_BLOCK) void cmax_gather_kernel(CmStream S, int P, const double* __restrict__ D, double* __restrict__ partials) {
+    __shared__ double s_red[CM_PMAX * CM_BLOCK];
+    const int64_t i = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
+    double g[CM_PMAX] = {0.0, 0.0, 0.0};
+    if (i < S.N) {
+        CmWarp Q;
+        if (cm_warp(S, i, Q) == CM_OK) {
+            const double dwx[4] = {-Q.ob, Q.ob, -Q.b, Q.b}, dwy[4] = {-Q.oa, -Q.a, Q.oa, Q.a};
+            double Gx = 0.0, Gy = 0.0;
+            for (int c = 0; c < 4; ++c) {
+                int64_t cell;
+                if (!cm_corner(S, Q, c, cell)) continue;
+                const double d = D[cell];
+                Gx += d * dwx[c];
+                Gy += d * dwy[c];
+            }
+            for (int k = 0; k < P; ++k) g[k] = Q.s * (Gx * (Q.mx * Q.Bu[k]) + Gy * (Q.my * Q.Bv[k]));
+        }
+    }
+    for (int k = 0; k < P; ++k) s_red[k * CM_BLOCK + threadIdx.x] = g[k];
+    __syncthreads();
+    for (int s = CM_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int k = 0; k < P; ++k) s_red[k * CM_BLOCK + threadIdx.x] += s_red[k * CM_BLOCK + threadIdx.x + s];
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < P) partials[(int64_t)blockIdx.x * P + threadIdx.x] = s_red[threadIdx.x * CM_BLOCK];
+}
+
+int64_t cm_blocks(int64_t n) { return (n + CM_BLOCK - 1) / CM_BLOCK; }
+
+int cm_sizes(int32_t H, int32_t W, int64_t N) {
+    if (N < 0 || H <= 0 || W <= 0) return ENSLAM_EINVAL;
+    if (N > CM_MAX_EVENTS || H > 65536 || W > 65536 || (int64_t)H * W > CM_MAX_PIXELS) return ENSLAM_EUNSUPPORTED;
+    return ENSLAM_OK;
+}
+
+// three float64 images (J or D, the row pass, J - mu) and the partials of the widest first level
+int64_t cm_workspace_bytes(int32_t H, int32_t W, int64_t N, int32_t P) {
+    const int64_t npix = (int64_t)H * W, a = cm_blocks(npix), b = cm_blocks(N) * P;
+    return (3 * npix + (a > b ? a : b)) * (int64_t)sizeof(double);
+}
+
+bool cm_finite(double v) { return std::isfinite(v); }
+
+}  // namespace
+
+extern "C" {
+
+int enslam_event_cmax_workspace(int32_t H, int32_t W, int64_t N, int32_t P, int64_t* bytes_host) {
+    if (!bytes_host || P < 2 || P > CM_PMAX) return ENSLAM_EINVAL;
+    const int rc = cm_sizes(H, W, N);
+    if (rc != ENSLAM_OK) return rc;
+    *bytes_host = cm_workspace_bytes(H, W, N, P);
+    return ENSLAM_OK;
+}
+
+int enslam_event_cmax_eval(const double* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t N, int32_t H, int32_t W,
+                           double fx, double fy, double cx, double cy, int32_t model, const double* theta_host, double t_ref,
+                           int32_t sign_votes, int32_t k, const double* taps_host, void* workspace, int64_t workspace_bytes,
+                           int64_t* iwe, double* blurred, double* stats, uint64_t* dropped, int32_t want_grad, void* stream) {
+    if (!theta_host || !taps_host || !workspace || !iwe || !stats || !dropped) return ENSLAM_EINVAL;
+    if (N > 0 && (!t || !x || !y || !p)) return ENSLAM_EINVAL;
+    if (model != ENSLAM_CMAX_FLOW && model != ENSLAM_CMAX_ROTATION) return ENSLAM_EINVAL;
+    if (k <= 0 || k % 2 == 0) return ENSLAM_EINVAL;
+    int rc = cm_sizes(H, W, N);
+    if (rc == ENSLAM_EINVAL) return rc;
+    const int P = model == ENSLAM_CMAX_FLOW ? 2 : 3;
+    if (!cm_finite(fx) || !cm_finite(fy) || !cm_finite(cx) || !cm_finite(cy) || !cm_finite(t_ref) || fx == 0.0 || fy == 0.0)
+        return ENSLAM_EINVAL;
+    for (int i = 0; i < P; ++i)
+        if (!cm_finite(theta_host[i])) return ENSLAM_EINVAL;
+    if (rc != ENSLAM_OK) return rc;
+    if (k > CM_KMAX) return ENSLAM_EUNSUPPORTED;
+    for (int i = 0; i < k; ++i)
+        if (!cm_finite(taps_host[i])) return ENSLAM_EINVAL;
+    if (workspace_bytes < cm_workspace_bytes(H, W, N, P) || ((uintptr_t)workspace & 7u)) return ENSLAM_EINVAL;
+    if (((uintptr_t)iwe & 7u) || ((uintptr_t)blurred & 7u) || ((uintptr_t)stats & 7u) || ((uintptr_t)dropped & 7u)) return ENSLAM_EINVAL;
+
+    const int64_t npix = (int64_t)H * W, pix_blocks = cm_blocks(npix), ev_blocks = cm_blocks(N);
+    double* bufA = (double*)workspace;                      // J when the caller wants none, then D
+    double* bufR = bufA + npix;                             // the row pass
+    double* bufC = bufR + npix;                             // J - mu
+    double* partials = bufC + npix;
+    double* J = blurred ? blurred : bufA;
+    hipStream_t st = (hipStream_t)stream;
+
+    CmStream S;
+    S.t = t; S.x = x; S.y = y; S.p = p; S.N = N; S.H = H; S.W = W; S.model = model; S.sign_votes = sign_votes;
+    S.fx = fx; S.fy = fy; S.cx = cx; S.cy = cy; S.t_ref = t_ref;
+    for (int i = 0; i < CM_PMAX; ++i) S.theta[i] = i < P ? theta_host[i] : 0.0;
+    CmBlur B;
+    B.H = H; B.W = W; B.k = k;
+    for (int i = 0; i < CM_KMAX; ++i) B.taps[i] = i < k ? taps_host[i] : 0.0;
+
+    if (hipMemsetAsync(iwe, 0, (size_t)npix * sizeof(int64_t), st) != hipSuccess) return ENSLAM_ELAUNCH;
+    if (hipMemsetAsync(dropped, 0, 3 * sizeof(uint64_t), st) != hipSuccess) return ENSLAM_ELAUNCH;
+    if (hipMemsetAsync(stats, 0, (size_t)(2 + P) * sizeof(double), st) != hipSuccess) return ENSLAM_ELAUNCH;
+    if (N > 0)
+        cmax_vote_kernel<<<(unsigned)ev_blocks, CM_BLOCK, 0, st>>>(S, reinterpret_cast<unsigned long long*>(iwe),
+                                                                  reinterpret_cast<unsigned long long*>(dropped));
+    cmax_rows_kernel<long long><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, reinterpret_cast<const long long*>(iwe), bufR);
+    cmax_cols_kernel<true><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, bufR, J, partials);
+    cmax_upper_kernel<<<1, CM_BLOCK, 0, st>>>(partials, pix_blocks, 1, (double)npix, 0, stats);
+    cmax_centre_kernel<<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(J, stats, npix, bufC, partials);
+    cmax_upper_kernel<<<1, CM_BLOCK, 0, st>>>(partials, pix_blocks, 1, (double)npix, 0, stats + 1);
+    if (want_grad) {
+        cmax_rows_kernel<double><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, bufC, bufR);
+        cmax_cols_kernel<false><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, bufR, bufA, nullptr);
+        if (N > 0) cmax_gather_kernel<<<(unsigned)ev_blocks, CM_BLOCK, 0, st>>>(S, P, bufA, partials);
+        cmax_upper_kernel<<<1, CM_BLOCK, 0, st>>>(partials, ev_blocks, P, 2.0 / (double)npix, 1, stats + 2);
+    }
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+}  // extern "C"

@@ -3498,3 +3498,49 @@ def event_model_loss(cur, prev, gt, c_neg=0.2, c_pos=0.2, eps=1e-3, kernel_sizes
                                                 ctypes.c_float(eps), K, ksizes, weights, taps, _ptr(ws), ws.numel() * 8, _ptr(pred),
                                                 _ptr(sums), _ptr(grad), _ptr(bg), _ptr(bp), _stream()), "enslam_event_model_loss")
     return pred, sums, grad, bg, bp
+
+
+# ------------------------------------------------------------------------------------------------
+# event motion compensation by contrast maximisation (csrc/event_cmax.hip; event_cmax.py is the caller)
+# ------------------------------------------------------------------------------------------------
+EVENT_CMAX_MODELS = {'flow': (0, 2), 'rotation': (1, 3)}            # name -> (ENSLAM_CMAX_*, P)
+EVENT_CMAX_MAX_KSIZE = 31
+
+
+def event_cmax_eval(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False, want_grad=True, want_blurred=False):
+    """enslam_event_cmax_eval (enslam_hip.h) on a stream on one HIP device: t float64 [N], x, y uint16 [N], p uint8 [N].  calib =
+    (fx, fy, cx, cy) pinhole, model 'flow' or 'rotation', theta its P host numbers, taps the k float64 taps of the blur (a
+    host sequence).  Returns (iwe int64 [H,W], blurred float64 [H,W] or None, stats float64 [2 + P] = (mu, f, df/dtheta...),
+    dropped int64 [3] = (time, sensor, warp)) as device tensors; no synchronisation."""
+    what = "event_cmax_eval"
+    _event_arrays(what, t, x, y, p)
+    H, W = _event_sensor(what, H, W)
+    if model not in EVENT_CMAX_MODELS:
+        raise L.EnslamError(f"{what}: model must be one of {sorted(EVENT_CMAX_MODELS)} (got {model!r})")
+    code, P = EVENT_CMAX_MODELS[model]
+    import math
+    th = [float(v) for v in theta]
+    cal = [float(v) for v in calib]
+    tp = [float(v) for v in taps]
+    if len(th) != P or len(cal) != 4:
+        raise L.EnslamError(f"{what}: model {model!r} takes {P} parameters and calib = (fx, fy, cx, cy) (got {len(th)}, {len(cal)})")
+    if not all(math.isfinite(v) for v in th + cal + tp + [float(t_ref)]) or cal[0] == 0.0 or cal[1] == 0.0:
+        raise L.EnslamError(f"{what}: theta, t_ref, the intrinsics and the taps must be finite, fx and fy not 0")
+    k = len(tp)
+    if k % 2 == 0 or k > EVENT_CMAX_MAX_KSIZE:
+        raise L.EnslamError(f"{what}: the blur takes an odd number of taps up to {EVENT_CMAX_MAX_KSIZE} (got {k})")
+    N, dev = int(t.shape[0]), t.device
+    lib = L.lib()
+    nbytes = ctypes.c_int64(0)
+    L.check(lib.enslam_event_cmax_workspace(H, W, N, P, ctypes.byref(nbytes)), "enslam_event_cmax_workspace")
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes.value // 8, 1), dtype=torch.float64, device=dev)
+        iwe = torch.empty((H, W), dtype=torch.int64, device=dev)
+        blurred = torch.empty((H, W), dtype=torch.float64, device=dev) if want_blurred else None
+        stats = torch.empty(2 + P, dtype=torch.float64, device=dev)
+        dropped = torch.empty(3, dtype=torch.int64, device=dev)
+        L.check(lib.enslam_event_cmax_eval(_ptr(t), _ptr(x), _ptr(y), _ptr(p), N, H, W, cal[0], cal[1], cal[2], cal[3], code,
+                                           (ctypes.c_double * P)(*th), float(t_ref), 1 if signed else 0, k,
+                                           (ctypes.c_double * k)(*tp), _ptr(ws), ws.numel() * 8, _ptr(iwe), _ptr(blurred),
+                                           _ptr(stats), _ptr(dropped), 1 if want_grad else 0, _stream()), "enslam_event_cmax_eval")
+    return iwe, blurred, stats, dropped

@@ -1316,6 +1316,66 @@ int enslam_event_model_loss(const float *cur, const float *prev, const float *gt
                             const float *taps, void *workspace, int64_t workspace_bytes, float *pred, double *sums,
                             float *grad, float *blur_gt, float *blur_pred, void *stream);
 
+/* Event motion compensation by contrast maximisation (event_cmax.py, csrc/event_cmax.hip; Gallego et al., CVPR 2018): every
+ * event of a stream is warped along a candidate motion theta to the reference time t_ref and voted into an image of warped
+ * events (IWE); the objective is the variance of the blurred IWE, returned with its gradient in theta.
+ *
+ * Stream: t float64 [N], x, y uint16 [N], p uint8 [N] on the device, in any order.  Pinhole intrinsics fx, fy, cx, cy (x
+ * right, y down, z forward).  theta_host is a HOST float64 [P] array, P = 2 for ENSLAM_CMAX_FLOW, 3 for ENSLAM_CMAX_ROTATION.
+ * ALL arithmetic is float64 and every operation stands on its own (no contraction), in exactly this order, with xd, yd the
+ * event's x, y as float64:
+ *     u  = (xd - cx) / fx                   v  = (yd - cy) / fy                  dt = t - t_ref
+ *     FLOW      Bu = (1 / fx, 0)            Bv = (0, 1 / fy)
+ *               du = theta0 / fx            dv = theta1 / fy                                       (pixels per second)
+ *     ROTATION  uv = u * v                  pu = 1 + u * u                       pv = 1 + v * v
+ *               Bu = (uv, -pu, v)           Bv = (pv, -uv, -u)
+ *               du = (uv * w_x - pu * w_y) + v * w_z          dv = (pv * w_x - uv * w_y) - u * w_z   (theta = w, rad / s)
+ *     mx = -(dt * fx)                       my = -(dt * fy)
+ *     x' = xd + mx * du                     y' = yd + my * dv
+ * Checks, in this order, each with its counter in dropped uint64 [3]: x >= W or y >= H -> dropped[1] (before the time is
+ * looked at, as enslam_event_accumulate does); t not finite -> dropped[0]; then, in float64 and BEFORE any conversion to an
+ * integer, x' > -1 && x' < W && y' > -1 && y' < H, else -> dropped[2] (no corner inside the image; a NaN fails).  No address
+ * is formed from an unchecked value.
+ * Vote: x0 = floor(x'), a = x' - x0, oa = 1 - a, likewise y0, b, ob.  Corners c = 0..3 at (x0, y0), (x0 + 1, y0),
+ * (x0, y0 + 1), (x0 + 1, y0 + 1) with weights w_c = oa * ob, a * ob, oa * b, a * b; a corner outside [0, W) x [0, H) is
+ * skipped.  q_c = llrint(w_c * 2^32), negated when sign_votes != 0 and p == 0, is added to iwe int64 [H,W] with 64-bit
+ * integer atomics: integer sums do not depend on arrival order (the IWE is bit-reproducible) and N <= 2^31 - 1 votes of
+ * weight <= 1 cannot overflow.  I = (float64)iwe * 2^-32.
+ * Objective: J = G I, the separable Gaussian blur with ZERO padding, rows first then columns:
+ *     r[y][x] = sum_{i = 0..k-1, ascending, from 0.0} taps[i] * I[y][x - k/2 + i]        (0.0 outside the image)
+ *     J[y][x] = sum_{i = 0..k-1, ascending, from 0.0} taps[i] * r[y - k/2 + i][x]
+ * taps_host is a HOST float64 [k] array (event.gaussian_kernel1d's own numbers), k odd, k <= ENSLAM_CMAX_MAX_KSIZE; k = 1
+ * with tap 1 is no blur.  mu = SUM(J) / (H W), f = SUM((J - mu) * (J - mu)) / (H W) over the row-major pixels.
+ * Gradient (want_grad != 0): D = G (J - mu) (zero padding makes the blur its own adjoint).  Per event that voted, with
+ * dwx_c = -ob, ob, -b, b and dwy_c = -oa, -a, oa, a:
+ *     Gx = sum over the corners inside, c ascending, from 0.0, of D_c * dwx_c;      Gy likewise with dwy_c
+ *     g_k = s * (Gx * (mx * Bu_k) + Gy * (my * Bv_k)),   s = -1 for a negated vote, else 1;   g_k = 0.0 for a dropped event
+ *     df / dtheta_k = (2 / (H W)) * SUM(g_k) over the events in stream order.
+ * SUM, the one order of every float64 sum here: the elements in consecutive blocks of 256, the last block padded with 0.0;
+ * each block reduced by the halving tree v[i] += v[i + s] for s = 128, 64, .. 1; the block results reduced 256 at a time by
+ * the same tree; what is then left (one value per 65536 elements) added in ascending order from 0.0.  No float atomics.
+ *
+ * Outputs: iwe; blurred float64 [H,W] = J, or NULL; stats float64 [2 + P] = (mu, f, df/dtheta..., the latter 0.0 without
+ * want_grad); dropped.  workspace: enslam_event_cmax_workspace bytes, 8-byte aligned.  A fixed set of launches and memsets on
+ * the stream, no host synchronisation: safe inside a stream capture.  Inputs are only read.
+ * ENSLAM_EINVAL without a launch: a NULL theta_host, taps_host, workspace, iwe, stats or dropped; a NULL stream array with
+ * N > 0; N < 0; H or W <= 0; a non-finite theta, t_ref or intrinsic; fx or fy equal to 0; an unknown model; k even or <= 0
+ * (checked before its size); a non-finite tap; a workspace too small or misaligned; iwe, blurred, stats or dropped not 8-byte
+ * aligned.  ENSLAM_EUNSUPPORTED without a launch: N > 2^31 - 1, H or W > 65536, more than 2^28 pixels, k >
+ * ENSLAM_CMAX_MAX_KSIZE.  enslam_event_cmax_workspace refuses the same sizes and P outside 2..3. */
+#define ENSLAM_CMAX_FLOW 0
+#define ENSLAM_CMAX_ROTATION 1
+#define ENSLAM_CMAX_MAX_KSIZE 31
+#define ENSLAM_CMAX_DROP_TIME 0
+#define ENSLAM_CMAX_DROP_SENSOR 1
+#define ENSLAM_CMAX_DROP_WARP 2
+int enslam_event_cmax_workspace(int32_t H, int32_t W, int64_t N, int32_t P, int64_t *bytes_host);
+int enslam_event_cmax_eval(const double *t, const uint16_t *x, const uint16_t *y, const uint8_t *p, int64_t N, int32_t H,
+                           int32_t W, double fx, double fy, double cx, double cy, int32_t model, const double *theta_host,
+                           double t_ref, int32_t sign_votes, int32_t k, const double *taps_host, void *workspace,
+                           int64_t workspace_bytes, int64_t *iwe, double *blurred, double *stats, uint64_t *dropped,
+                           int32_t want_grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
