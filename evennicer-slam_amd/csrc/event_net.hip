@@ -1,10 +1,17 @@
-// Event network on the device: UNet_2heads(6, 2, 2), bilinear, eval mode, batch 1, float32 -- forward and the gradient
-// with respect to the input image (event.py: UNet_2heads; reference event_net/unet_model.py:72-122, unet_parts.py).
+// Event network on the device: UNet_2heads(6, 2, 2), bilinear, float32 -- forward, the gradient with respect to the input
+// image and the gradients of the parameters (event.py: UNet_2heads; reference event_net/unet_model.py:72-122, unet_parts.py).
 //
-// Frozen weights and eval-mode BatchNorm make every conv - BN - ReLU triple one 3x3 convolution with folded weights
-// w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps) (event.py folds in float64 and rounds once).
-// Activations are channels-last ([H*W][C]) so the reduction axis of a tap is contiguous; the public tensors stay
-// [1,C,H,W] (en_pack_x / en_unpack_gx / the heads convert).
+// The network is written down once, as a table (EN_CONV: per convolution its level and where its one or two inputs come
+// from).  One planner lays out the workspace from it, and one forward walk and one backward walk launch the kernels from
+// it, per image.  Two routes bind the walks:
+//   folded         eval-mode BatchNorm, one image (enslam_eventnet_forward / _backward / _backward_weights).  Every
+//                  conv - BN - ReLU triple is one 3x3 convolution with folded weights w' = w * gamma / sqrt(var + eps),
+//                  b' = beta - mean * gamma / sqrt(var + eps) (event.py folds in float64 and rounds once; fold_pack does it on
+//                  the device for live parameters), bias and ReLU in the convolution's epilogue.
+//   training mode  batch statistics, B images (enslam_eventnet_train_forward / _train_backward).  The convolutions run
+//                  unfolded and write the raw z; the BatchNorm kernels, which alone see the whole batch, follow each one.
+// Activations are channels-last ([H*W][C], images one after the other) so the reduction axis of a tap is contiguous; the
+// public tensors stay [B,C,H,W] (en_pack_x / en_unpack_gx / the heads convert).
 //
 //   conv3x3_kernel   implicit GEMM  out[p][n] = sum_{tap, c} in[p + tap][c] * w[(tap, c)][n]  on v_mfma_f32_32x32x2_f32
 //                    (exact f32, an fmaf chain in k order).  One workgroup (4 waves as 2 x 2) owns 64 pixels x 64 output
@@ -22,7 +29,7 @@
 //                    up: torch's float32 source-coordinate expression, so the interpolation weights are F.interpolate's).
 //   heads            the two 1x1 heads fused (sigmoid on head 2), and their backward into the 64-channel features.
 //
-// Training (enslam_eventnet_backward_weights) adds the gradients of the packed image itself:
+// The weight gradients (of the packed image on the folded route, of the parameters in training mode):
 //   conv3x3_wgrad_kernel   implicit GEMM  dWf[tap * Cin + c][n] = sum_p in[p + tap][c] * G[p][n],  G = g where saved_out > 0,
 //                    on the same MFMA.  One workgroup (4 waves as 2 x 2) owns 64 weight rows x 64 output channels; the
 //                    reduction runs over the pixels in chunks of 32 staged in LDS, both operands as [pixel][row] (both are
@@ -33,8 +40,8 @@
 //                    in split order (no atomics).
 //   heads_wgrad      gradients of the heads block, a fixed-order two-stage reduction over the pixels.
 //
-// Training-mode BatchNorm and batches (the unfolded net, enslam_eventnet_bn_* / enslam_eventnet_train_*) are the last section
-// of this file, with their own notes.
+// The BatchNorm kernels (enslam_eventnet_bn_*) and the unfolded weights' packing have their own notes further down; the
+// planner, the two walks and the whole-network entries of both routes are the last section of this file.
 #include "../../include/enslam_hip.h"
 #include "common.hpp"
 #include <algorithm>
@@ -611,70 +618,68 @@ __global__ __launch_bounds__(EN_HEADS_FLOATS) void heads_pack_kernel(float* w1, 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-struct SplitPlan { int ptiles, ntiles, nchunks, cps, splits; };
+inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
+inline int tiles_of(int64_t n, int tile) { return (int)((n + tile - 1) / tile); }
+bool chan_ok(int c) { return c >= 8 && c <= 1024 && c % 8 == 0; }
+bool all_set(const void* const* p, int n) {
+    for (int k = 0; k < n; ++k)
+        if (!p[k]) return false;
+    return true;
+}
 
-SplitPlan split_plan(int64_t P, int Cin, int N) {
-    SplitPlan s;
-    s.ptiles = (int)((P + EN_TM - 1) / EN_TM);
-    s.ntiles = (N + EN_TN - 1) / EN_TN;
-    s.nchunks = (9 * Cin + EN_KC - 1) / EN_KC;
-    s.cps = s.nchunks;
-    const int64_t tiles = (int64_t)s.ptiles * s.ntiles;
+// The one split rule: a launch with fewer than EN_SPLIT_BELOW output tiles splits its reduction (nchunks chunks) over
+// blockIdx.z, to about EN_SPLIT_TARGET workgroups; cps chunks per split.
+struct Split { int nchunks, cps, splits; };
+Split split_plan(int64_t tiles, int nchunks) {
+    Split s = {nchunks, nchunks, 1};
     if (tiles < EN_SPLIT_BELOW) {
-        const int want = (int)std::min<int64_t>(s.nchunks, (EN_SPLIT_TARGET + tiles - 1) / tiles);
-        s.cps = (s.nchunks + want - 1) / want;
+        const int want = (int)std::min<int64_t>(nchunks, (EN_SPLIT_TARGET + tiles - 1) / tiles);
+        s.cps = (nchunks + want - 1) / want;
     }
-    s.splits = (s.nchunks + s.cps - 1) / s.cps;
+    s.splits = (nchunks + s.cps - 1) / s.cps;
     return s;
 }
+// convolution: the tiles cover pixels x output channels, the reduction over 9 Cin runs in chunks of EN_KC
+dim3 conv_grid(int64_t P, int Cin, int N, Split& s) {
+    const int ptiles = tiles_of(P, EN_TM), ntiles = tiles_of(N, EN_TN);
+    s = split_plan((int64_t)ptiles * ntiles, tiles_of(9 * Cin, EN_KC));
+    return dim3(ptiles, ntiles, s.splits);
+}
+// weight gradient: the tiles cover the 9 Cin x N weight block, so the PIXEL axis is what splits, in chunks of EN_WG_PC pixels
+dim3 wgrad_grid(int64_t P, int Cin, int N, Split& s) {
+    const int mtiles = tiles_of(9 * Cin, EN_TM), ntiles = tiles_of(N, EN_TN);
+    s = split_plan((int64_t)mtiles * ntiles, tiles_of(P, EN_WG_PC));
+    return dim3(mtiles, ntiles, s.splits);
+}
 int64_t split_floats(int64_t P, int Cin, int N) {
-    const SplitPlan s = split_plan(P, Cin, N);
+    Split s;
+    conv_grid(P, Cin, N, s);
     return s.splits > 1 ? (int64_t)s.splits * P * N : 0;
 }
-
-bool chan_ok(int c) { return c >= 8 && c <= 1024 && c % 8 == 0; }
+int64_t wgrad_floats(int64_t P, int Cin, int N) {
+    Split s;
+    wgrad_grid(P, Cin, N, s);
+    return s.splits > 1 ? (int64_t)s.splits * ((int64_t)9 * Cin * N + N) : 0;
+}
 
 int launch_conv(ConvArgs a, hipStream_t st) {
     const int64_t P = (int64_t)a.H * a.W;
-    const SplitPlan s = split_plan(P, a.C0 + a.C1, a.N);
+    Split s;
+    const dim3 grid = conv_grid(P, a.C0 + a.C1, a.N, s);
     a.nchunks = s.nchunks;
     a.cps = s.cps;
-    conv3x3_kernel<<<dim3(s.ptiles, s.ntiles, s.splits), EN_THREADS, 0, st>>>(a);
-    if (s.splits > 1) conv3x3_reduce_kernel<<<(unsigned)((P * a.N + 255) / 256), 256, 0, st>>>(a, s.splits);
+    conv3x3_kernel<<<grid, EN_THREADS, 0, st>>>(a);
+    if (s.splits > 1) conv3x3_reduce_kernel<<<blocks_of(P * a.N), 256, 0, st>>>(a, s.splits);
     return 0;
-}
-
-inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// Weight gradient: the tiles cover the 9 Cin x N weight block and the reduction runs over the pixels, so the PIXEL axis is
-// what a layer with few tiles splits -- the same rule as split_plan (below EN_SPLIT_BELOW tiles, to about EN_SPLIT_TARGET
-// workgroups), counted in chunks of EN_WG_PC pixels.
-struct WgradPlan { int mtiles, ntiles, nchunks, cps, splits; };
-WgradPlan wgrad_plan(int64_t P, int Cin, int N) {
-    WgradPlan s;
-    s.mtiles = (9 * Cin + EN_TM - 1) / EN_TM;
-    s.ntiles = (N + EN_TN - 1) / EN_TN;
-    s.nchunks = (int)((P + EN_WG_PC - 1) / EN_WG_PC);
-    s.cps = s.nchunks;
-    const int64_t tiles = (int64_t)s.mtiles * s.ntiles;
-    if (tiles < EN_SPLIT_BELOW) {
-        const int want = (int)std::min<int64_t>(s.nchunks, (EN_SPLIT_TARGET + tiles - 1) / tiles);
-        s.cps = (s.nchunks + want - 1) / want;
-    }
-    s.splits = (s.nchunks + s.cps - 1) / s.cps;
-    return s;
-}
-int64_t wgrad_floats(int64_t P, int Cin, int N) {
-    const WgradPlan s = wgrad_plan(P, Cin, N);
-    return s.splits > 1 ? (int64_t)s.splits * ((int64_t)9 * Cin * N + N) : 0;
 }
 
 void launch_wgrad(WgradArgs a, hipStream_t st) {
     const int Cin = a.C0 + a.C1;
-    const WgradPlan s = wgrad_plan((int64_t)a.H * a.W, Cin, a.N);
+    Split s;
+    const dim3 grid = wgrad_grid((int64_t)a.H * a.W, Cin, a.N, s);
     a.nchunks = s.nchunks;
     a.cps = s.cps;
-    conv3x3_wgrad_kernel<<<dim3(s.mtiles, s.ntiles, s.splits), EN_THREADS, 0, st>>>(a);
+    conv3x3_wgrad_kernel<<<grid, EN_THREADS, 0, st>>>(a);
     if (s.splits > 1)
         conv3x3_wgrad_reduce_kernel<<<blocks_of((int64_t)9 * Cin * a.N + a.N), 256, 0, st>>>(a, s.splits);
 }
@@ -685,15 +690,44 @@ int heads_wgrad_blocks(int64_t P, int& per_block) {
     return (int)((P + per_block - 1) / per_block);
 }
 
-// the 26 convolutions in packing order: encoder (inc, down1..4), then per head up1..up4
-struct ConvDim { int cin, cout; };
-const ConvDim EN_CONV[EN_NCONV] = {
-    {8, 64}, {64, 64}, {64, 128}, {128, 128}, {128, 256}, {256, 256}, {256, 512}, {512, 512}, {512, 512}, {512, 512},
-    {1024, 512}, {512, 256}, {512, 256}, {256, 128}, {256, 128}, {128, 64}, {128, 64}, {64, 64},
-    {1024, 512}, {512, 256}, {512, 256}, {256, 128}, {256, 128}, {128, 64}, {128, 64}, {64, 64}};
-const int EN_ENC_C[5] = {64, 128, 256, 512, 512};       // channels of the encoder features f0..f4
-const int EN_DEC_CD[4] = {512, 256, 128, 64};           // per decoder stage: channels of the deep input (= skip = mid)
-const int EN_DEC_OUT[4] = {256, 128, 64, 64};
+// ---------------------------------------------------------------------------------------------------------------
+// The network, once.  The 26 convolutions in packing order: encoder (inc, down1..4), then per head up1..up4.  Each reads
+// one or two sources (torch.cat / F.pad are not materialised: the convolution kernels read both in place):
+//   SRC_X8    the packed input image (6 channels padded to 8)
+//   SRC_OUT   the output of convolution `conv`
+//   SRC_POOL  MaxPool2d(2) of the output of convolution `conv`
+//   SRC_UP    the x2 bilinear up-sample of the output of convolution `conv`, centred in the skip's extent (the skip is at
+//             most one pixel larger per axis, so the centring offset diff / 2 is zero)
+// and `ch` channels come from that source.  Everything the planner and the two walks know about the wiring is read here.
+// ---------------------------------------------------------------------------------------------------------------
+enum SrcKind { SRC_NONE, SRC_X8, SRC_OUT, SRC_POOL, SRC_UP };
+struct Source { SrcKind kind; int conv, ch; };
+struct ConvDesc {
+    int cout, level;              // output channels; resolution level: H >> level x W >> level
+    Source src[2];
+    int cin() const { return src[0].ch + src[1].ch; }
+};
+constexpr Source NO_SRC = {SRC_NONE, -1, 0};
+const ConvDesc EN_CONV[EN_NCONV] = {
+    {64, 0, {{SRC_X8, -1, 8}, NO_SRC}},                {64, 0, {{SRC_OUT, 0, 64}, NO_SRC}},
+    {128, 1, {{SRC_POOL, 1, 64}, NO_SRC}},             {128, 1, {{SRC_OUT, 2, 128}, NO_SRC}},
+    {256, 2, {{SRC_POOL, 3, 128}, NO_SRC}},            {256, 2, {{SRC_OUT, 4, 256}, NO_SRC}},
+    {512, 3, {{SRC_POOL, 5, 256}, NO_SRC}},            {512, 3, {{SRC_OUT, 6, 512}, NO_SRC}},
+    {512, 4, {{SRC_POOL, 7, 512}, NO_SRC}},            {512, 4, {{SRC_OUT, 8, 512}, NO_SRC}},
+    // head 0: the skip and the up-sampled deep feature, then the stage's second convolution
+    {512, 3, {{SRC_OUT, 7, 512}, {SRC_UP, 9, 512}}},   {256, 3, {{SRC_OUT, 10, 512}, NO_SRC}},
+    {256, 2, {{SRC_OUT, 5, 256}, {SRC_UP, 11, 256}}},  {128, 2, {{SRC_OUT, 12, 256}, NO_SRC}},
+    {128, 1, {{SRC_OUT, 3, 128}, {SRC_UP, 13, 128}}},  {64, 1, {{SRC_OUT, 14, 128}, NO_SRC}},
+    {64, 0, {{SRC_OUT, 1, 64}, {SRC_UP, 15, 64}}},     {64, 0, {{SRC_OUT, 16, 64}, NO_SRC}},
+    // head 1
+    {512, 3, {{SRC_OUT, 7, 512}, {SRC_UP, 9, 512}}},   {256, 3, {{SRC_OUT, 18, 512}, NO_SRC}},
+    {256, 2, {{SRC_OUT, 5, 256}, {SRC_UP, 19, 256}}},  {128, 2, {{SRC_OUT, 20, 256}, NO_SRC}},
+    {128, 1, {{SRC_OUT, 3, 128}, {SRC_UP, 21, 128}}},  {64, 1, {{SRC_OUT, 22, 128}, NO_SRC}},
+    {64, 0, {{SRC_OUT, 1, 64}, {SRC_UP, 23, 64}}},     {64, 0, {{SRC_OUT, 24, 64}, NO_SRC}}};
+// each head's decoder is the convolutions first..last; the 1x1 head reads the 64-channel output of `last`.  The encoder is
+// every convolution before EN_HEAD[0].first.
+struct HeadDesc { int first, last; };
+const HeadDesc EN_HEAD[2] = {{10, 17}, {18, 25}};
 
 // packed image: per convolution  Wf [9 cin][cout] | b [cout] | Wt [9 cout][cin],  then the heads block
 struct PackOff { int64_t wf[EN_NCONV], b[EN_NCONV], wt[EN_NCONV], heads, total; };
@@ -701,7 +735,7 @@ PackOff pack_offsets() {
     PackOff o;
     int64_t q = 0;
     for (int i = 0; i < EN_NCONV; ++i) {
-        const int64_t n = (int64_t)9 * EN_CONV[i].cin * EN_CONV[i].cout;
+        const int64_t n = (int64_t)9 * EN_CONV[i].cin() * EN_CONV[i].cout;
         o.wf[i] = q; q += n;
         o.b[i] = q; q += EN_CONV[i].cout;
         o.wt[i] = q; q += n;
@@ -711,61 +745,31 @@ PackOff pack_offsets() {
     return o;
 }
 
-// workspace (float offsets, every region a multiple of 64 floats)
-struct Plan {
-    int H[5], W[5];
-    int64_t P[5];
-    int64_t x8, a[5], f[5], pl[5], u[2][4], m[2][4], d[2][4], probs, df[5], t[3], part, total;
-};
-Plan make_plan(int H, int W) {
-    Plan pl;
-    for (int l = 0; l < 5; ++l) {
-        pl.H[l] = l ? pl.H[l - 1] / 2 : H;
-        pl.W[l] = l ? pl.W[l - 1] / 2 : W;
-        pl.P[l] = (int64_t)pl.H[l] * pl.W[l];
+constexpr int EN_FOLD_PART = 32 * 512;        // float64 partials per convolution: at most 32 cin tiles x 512 cout
+// the table's shapes and workgroup ranges; `stride` addresses per convolution in params, the first of them w.  The caller
+// fills the remaining addresses.
+int fold_shapes(const void* const* params, int stride, FoldTable& tb) {
+    int blocks = 0;
+    for (int i = 0; i < EN_NCONV; ++i) {
+        FoldArgs& a = tb.a[i];
+        a = FoldArgs{};
+        a.w = (const float*)params[stride * i];
+        a.cinp = EN_CONV[i].cin(); a.cin = i ? a.cinp : 6; a.cout = EN_CONV[i].cout;
+        tb.first[i] = blocks;
+        blocks += tiles_of(a.cinp, EN_FT) * tiles_of(a.cout, EN_FT);
     }
-    int64_t q = 0, part = 0;
-    auto take = [&](int64_t n) { const int64_t at = q; q += (n + 63) / 64 * 64; return at; };
-    auto conv = [&](int64_t P, int cin, int cout) {
-        part = std::max(part, std::max(split_floats(P, cin, cout), split_floats(P, cout, cin)));
-    };
-    pl.x8 = take(pl.P[0] * 8);
-    for (int l = 0; l < 5; ++l) {
-        pl.pl[l] = l ? take(pl.P[l] * EN_ENC_C[l - 1]) : -1;
-        pl.a[l] = take(pl.P[l] * EN_ENC_C[l]);
-        pl.f[l] = take(pl.P[l] * EN_ENC_C[l]);
-        pl.df[l] = take(pl.P[l] * EN_ENC_C[l]);
-        conv(pl.P[l], EN_CONV[2 * l].cin, EN_CONV[2 * l].cout);
-        conv(pl.P[l], EN_CONV[2 * l + 1].cin, EN_CONV[2 * l + 1].cout);
-    }
-    for (int hd = 0; hd < 2; ++hd)
-        for (int j = 0; j < 4; ++j) {
-            const int ls = 3 - j, cd = EN_DEC_CD[j];
-            pl.u[hd][j] = take(4 * pl.P[ls + 1] * cd);
-            pl.m[hd][j] = take(pl.P[ls] * cd);
-            pl.d[hd][j] = take(pl.P[ls] * EN_DEC_OUT[j]);
-            conv(pl.P[ls], 2 * cd, cd);
-            conv(pl.P[ls], cd, EN_DEC_OUT[j]);
-        }
-    pl.probs = take(2 * pl.P[0]);
-    // transient gradients: at most P0 * 64 floats each (level l has P0 / 4^l pixels and at most 64 * 2^l channels)
-    for (int k = 0; k < 3; ++k) pl.t[k] = take(pl.P[0] * 64);
-    pl.part = take(part);
-    pl.total = q;
-    return pl;
+    tb.first[EN_NCONV] = blocks;
+    return blocks;
 }
-
-bool size_ok(int H, int W) { return H >= 16 && W >= 16 && (int64_t)H * W <= (1 << 21); }
-
-// scratch of the weight gradients of an H x W image: the largest split-partial block of the 26 convolutions, or the heads'
-int64_t wgrad_scratch_floats(const Plan& pl) {
-    int per_block;
-    int64_t need = (int64_t)heads_wgrad_blocks(pl.P[0], per_block) * 260;
-    for (int l = 0; l < 5; ++l)
-        for (int k = 0; k < 2; ++k) need = std::max(need, wgrad_floats(pl.P[l], EN_CONV[2 * l + k].cin, EN_CONV[2 * l + k].cout));
-    for (int j = 0; j < 4; ++j)
-        for (int k = 0; k < 2; ++k) need = std::max(need, wgrad_floats(pl.P[3 - j], EN_CONV[10 + 2 * j + k].cin, EN_CONV[10 + 2 * j + k].cout));
-    return (need + 63) / 64 * 64;
+// the folded route's table: 5 addresses per convolution (w, gamma, beta, sq float64, shift float64)
+int fold_table(const void* const* params, FoldTable& tb) {
+    const int blocks = fold_shapes(params, 5, tb);
+    for (int i = 0; i < EN_NCONV; ++i) {
+        FoldArgs& a = tb.a[i];
+        a.gamma = (const float*)params[5 * i + 1]; a.beta = (const float*)params[5 * i + 2];
+        a.sq = (const double*)params[5 * i + 3]; a.shift = (const double*)params[5 * i + 4];
+    }
+    return blocks;
 }
 
 }  // namespace
@@ -774,192 +778,10 @@ extern "C" {
 
 size_t enslam_eventnet_pack_floats(void) { return (size_t)pack_offsets().total; }
 
-size_t enslam_eventnet_workspace_floats(int32_t H, int32_t W) {
-    if (!size_ok(H, W)) return 0;
-    return (size_t)make_plan(H, W).total;
-}
-
-int enslam_eventnet_forward(const float* packed, const float* x, int32_t H, int32_t W, float* workspace, float* events,
-                            float* probs, void* stream) {
-    if (!packed || !x || !workspace || !events || !probs) return ENSLAM_EINVAL;
-    if (!size_ok(H, W)) return ENSLAM_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const Plan pl = make_plan(H, W);
-    const PackOff po = pack_offsets();
-    float* ws = workspace;
-    auto conv = [&](int i, int Hc, int Wc, const float* s0, int C0, const float* s1, int C1, int sH1, int sW1, float* dst) {
-        ConvArgs a = {};
-        a.w = packed + po.wf[i]; a.bias = packed + po.b[i];
-        a.s0 = s0; a.s1 = s1; a.d0 = dst; a.part = ws + pl.part;
-        a.H = Hc; a.W = Wc; a.C0 = C0; a.C1 = C1; a.sH1 = sH1; a.sW1 = sW1;
-        a.N = a.N0 = EN_CONV[i].cout; a.relu = 1;
-        launch_conv(a, st);
-    };
-    en_pack_x_kernel<<<blocks_of(pl.P[0] * 8), 256, 0, st>>>(x, (int)pl.P[0], ws + pl.x8);
-    for (int l = 0; l < 5; ++l) {
-        const float* in = ws + pl.x8;
-        int cin = 8;
-        if (l) {
-            cin = EN_ENC_C[l - 1];
-            pool2_fwd_kernel<<<blocks_of(pl.P[l] * cin), 256, 0, st>>>(ws + pl.f[l - 1], pl.H[l - 1], pl.W[l - 1], cin,
-                                                                       ws + pl.pl[l]);
-            in = ws + pl.pl[l];
-        }
-        conv(2 * l, pl.H[l], pl.W[l], in, cin, nullptr, 0, 0, 0, ws + pl.a[l]);
-        conv(2 * l + 1, pl.H[l], pl.W[l], ws + pl.a[l], EN_ENC_C[l], nullptr, 0, 0, 0, ws + pl.f[l]);
-    }
-    for (int hd = 0; hd < 2; ++hd) {
-        const float* deep = ws + pl.f[4];
-        for (int j = 0; j < 4; ++j) {
-            const int ls = 3 - j, ld = ls + 1, cd = EN_DEC_CD[j];
-            up2_fwd_kernel<<<blocks_of(4 * pl.P[ld] * cd), 256, 0, st>>>(deep, pl.H[ld], pl.W[ld], cd, ws + pl.u[hd][j]);
-            conv(10 + 8 * hd + 2 * j, pl.H[ls], pl.W[ls], ws + pl.f[ls], cd, ws + pl.u[hd][j], cd, 2 * pl.H[ld],
-                 2 * pl.W[ld], ws + pl.m[hd][j]);
-            conv(11 + 8 * hd + 2 * j, pl.H[ls], pl.W[ls], ws + pl.m[hd][j], cd, nullptr, 0, 0, 0, ws + pl.d[hd][j]);
-            deep = ws + pl.d[hd][j];
-        }
-    }
-    heads_fwd_kernel<<<blocks_of(2 * pl.P[0]), 256, 0, st>>>(packed + po.heads, ws + pl.d[0][3], ws + pl.d[1][3],
-                                                             (int)pl.P[0], events, probs, ws + pl.probs);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The backward pass.  g_packed == null: the input gradient only (enslam_eventnet_backward).  Otherwise every layer's weight
-// gradient is launched next to its transposed convolution, while the layer's incoming gradient is still in the transient
-// buffers; g_x == null then skips the first layer's transposed convolution and the unpack.
-int run_backward(const float* packed, float* ws, const float* g_events, const float* g_probs, float* g_x, float* g_packed,
-                 float* scratch, int H, int W, hipStream_t st) {
-    const Plan pl = make_plan(H, W);
-    const PackOff po = pack_offsets();
-    float *tA = ws + pl.t[0], *tB = ws + pl.t[1], *tC = ws + pl.t[2];
-    // d(input of convolution i) from g (masked by the convolution's saved output): N0 channels to d0, the rest to d1
-    auto convT = [&](int i, int Hc, int Wc, const float* g, const float* saved, float* d0, int N0, int acc0, float* d1,
-                     int dH1, int dW1) {
-        ConvArgs a = {};
-        a.w = packed + po.wt[i];
-        a.s0 = g; a.mask = saved; a.C0 = EN_CONV[i].cout;
-        a.d0 = d0; a.d1 = d1; a.part = ws + pl.part;
-        a.H = Hc; a.W = Wc; a.N = EN_CONV[i].cin; a.N0 = N0; a.dH1 = dH1; a.dW1 = dW1; a.acc0 = acc0;
-        launch_conv(a, st);
-    };
-    // d(Wf, b of convolution i) from the same g and saved output, and the input(s) the forward read
-    auto wgrad = [&](int i, int Hc, int Wc, const float* s0, int C0, const float* s1, int C1, int sH1, int sW1, const float* g,
-                     const float* saved) {
-        if (!g_packed) return;
-        WgradArgs a = {};
-        a.s0 = s0; a.s1 = s1; a.g = g; a.saved = saved;
-        a.dw = g_packed + po.wf[i]; a.db = g_packed + po.b[i]; a.part = scratch;
-        a.H = Hc; a.W = Wc; a.C0 = C0; a.C1 = C1; a.sH1 = sH1; a.sW1 = sW1; a.N = EN_CONV[i].cout;
-        launch_wgrad(a, st);
-        (void)hipMemsetAsync(g_packed + po.wt[i], 0, sizeof(float) * 9 * EN_CONV[i].cin * EN_CONV[i].cout, st);   // hipGetLastError below
-    };
-    if (g_packed) {
-        int per_block;
-        const int blocks = heads_wgrad_blocks(pl.P[0], per_block);
-        heads_wgrad_kernel<<<blocks, 256, 0, st>>>(g_events, g_probs, ws + pl.probs, ws + pl.d[0][3], ws + pl.d[1][3],
-                                                   (int)pl.P[0], per_block, scratch);
-        heads_wgrad_reduce_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>(scratch, blocks, g_packed + po.heads);
-    }
-    for (int hd = 0; hd < 2; ++hd) {
-        heads_bwd_kernel<<<blocks_of(pl.P[0] * 64), 256, 0, st>>>(packed + po.heads, hd, hd ? g_probs : g_events,
-                                                                  ws + pl.probs, (int)pl.P[0], tA);
-        for (int j = 3; j >= 0; --j) {
-            const int ls = 3 - j, ld = ls + 1, cd = EN_DEC_CD[j];
-            const int i1 = 11 + 8 * hd + 2 * j, i0 = i1 - 1;
-            wgrad(i1, pl.H[ls], pl.W[ls], ws + pl.m[hd][j], cd, nullptr, 0, 0, 0, tA, ws + pl.d[hd][j]);
-            convT(i1, pl.H[ls], pl.W[ls], tA, ws + pl.d[hd][j], tB, cd, 0, nullptr, 0, 0);
-            wgrad(i0, pl.H[ls], pl.W[ls], ws + pl.f[ls], cd, ws + pl.u[hd][j], cd, 2 * pl.H[ld], 2 * pl.W[ld], tB,
-                  ws + pl.m[hd][j]);
-            convT(i0, pl.H[ls], pl.W[ls], tB, ws + pl.m[hd][j], ws + pl.df[ls], cd, hd, tC, 2 * pl.H[ld], 2 * pl.W[ld]);
-            float* dst = j ? tA : ws + pl.df[4];
-            up2_bwd_kernel<<<blocks_of(pl.P[ld] * cd), 256, 0, st>>>(tC, pl.H[ld], pl.W[ld], cd, dst, j ? 0 : hd);
-        }
-    }
-    for (int l = 4; l >= 0; --l) {
-        const int c = EN_ENC_C[l], cin = EN_CONV[2 * l].cin;
-        wgrad(2 * l + 1, pl.H[l], pl.W[l], ws + pl.a[l], c, nullptr, 0, 0, 0, ws + pl.df[l], ws + pl.f[l]);
-        convT(2 * l + 1, pl.H[l], pl.W[l], ws + pl.df[l], ws + pl.f[l], tA, c, 0, nullptr, 0, 0);
-        wgrad(2 * l, pl.H[l], pl.W[l], l ? ws + pl.pl[l] : ws + pl.x8, cin, nullptr, 0, 0, 0, tA, ws + pl.a[l]);
-        if (l || g_x) convT(2 * l, pl.H[l], pl.W[l], tA, ws + pl.a[l], tB, cin, 0, nullptr, 0, 0);
-        if (l)
-            pool2_bwd_kernel<<<blocks_of(pl.P[l - 1] * cin), 256, 0, st>>>(ws + pl.f[l - 1], pl.H[l - 1], pl.W[l - 1], cin, tB,
-                                                                           ws + pl.df[l - 1], 1);
-    }
-    if (g_x) en_unpack_gx_kernel<<<blocks_of(pl.P[0] * 6), 256, 0, st>>>(tB, (int)pl.P[0], g_x);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
-}
-
-}  // namespace
-
-extern "C" {
-
-int enslam_eventnet_backward(const float* packed, float* workspace, const float* g_events, const float* g_probs,
-                             float* g_x, int32_t H, int32_t W, void* stream) {
-    if (!packed || !workspace || !g_events || !g_probs || !g_x) return ENSLAM_EINVAL;
-    if (!size_ok(H, W)) return ENSLAM_EINVAL;
-    return run_backward(packed, workspace, g_events, g_probs, g_x, nullptr, nullptr, H, W, (hipStream_t)stream);
-}
-
-size_t enslam_eventnet_wgrad_scratch_floats(int32_t H, int32_t W) {
-    if (!size_ok(H, W)) return 0;
-    return (size_t)wgrad_scratch_floats(make_plan(H, W));
-}
-
-int enslam_eventnet_backward_weights(const float* packed, float* workspace, const float* g_events, const float* g_probs,
-                                     float* g_x, float* g_packed, float* scratch, int64_t scratch_floats, int32_t H, int32_t W,
-                                     void* stream) {
-    if (!packed || !workspace || !g_events || !g_probs || !g_packed || !scratch) return ENSLAM_EINVAL;
-    if (!size_ok(H, W)) return ENSLAM_EINVAL;
-    if (scratch_floats < wgrad_scratch_floats(make_plan(H, W))) return ENSLAM_EINVAL;
-    return run_backward(packed, workspace, g_events, g_probs, g_x, g_packed, scratch, H, W, (hipStream_t)stream);
-}
-
-int enslam_eventnet_heads_wgrad(const float* workspace, const float* g_events, const float* g_probs, float* g_heads,
-                                float* scratch, int64_t scratch_floats, int32_t H, int32_t W, void* stream) {
-    if (!workspace || !g_events || !g_probs || !g_heads || !scratch) return ENSLAM_EINVAL;
-    if (!size_ok(H, W)) return ENSLAM_EINVAL;
-    const Plan pl = make_plan(H, W);
-    int per_block;
-    const int blocks = heads_wgrad_blocks(pl.P[0], per_block);
-    if (scratch_floats < (int64_t)blocks * 260) return ENSLAM_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    heads_wgrad_kernel<<<blocks, 256, 0, st>>>(g_events, g_probs, workspace + pl.probs, workspace + pl.d[0][3],
-                                               workspace + pl.d[1][3], (int)pl.P[0], per_block, scratch);
-    heads_wgrad_reduce_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>(scratch, blocks, g_heads);
-    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
-}
-
-}  // extern "C"
-
-namespace {
-constexpr int EN_FOLD_PART = 32 * 512;        // float64 partials per convolution: at most 32 cin tiles x 512 cout
-int fold_table(const void* const* params, FoldTable& tb) {
-    int blocks = 0;
-    for (int i = 0; i < EN_NCONV; ++i) {
-        FoldArgs& a = tb.a[i];
-        a = FoldArgs{};
-        a.w = (const float*)params[5 * i]; a.gamma = (const float*)params[5 * i + 1]; a.beta = (const float*)params[5 * i + 2];
-        a.sq = (const double*)params[5 * i + 3]; a.shift = (const double*)params[5 * i + 4];
-        a.cinp = EN_CONV[i].cin; a.cin = i ? a.cinp : 6; a.cout = EN_CONV[i].cout;
-        tb.first[i] = blocks;
-        blocks += ((a.cinp + EN_FT - 1) / EN_FT) * ((a.cout + EN_FT - 1) / EN_FT);
-    }
-    tb.first[EN_NCONV] = blocks;
-    return blocks;
-}
-}  // namespace
-
-extern "C" {
-
 /* params: per convolution 5 device addresses (w, gamma, beta, sq float64, shift float64), then W1, W2, b1, b2 of the heads */
 int enslam_eventnet_fold_pack(const void* const* params, float* packed, void* stream) {
     if (!params || !packed) return ENSLAM_EINVAL;
-    for (int k = 0; k < 5 * EN_NCONV + 4; ++k)
-        if (!params[k]) return ENSLAM_EINVAL;
+    if (!all_set(params, 5 * EN_NCONV + 4)) return ENSLAM_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const PackOff po = pack_offsets();
     FoldTable tb;
@@ -977,10 +799,8 @@ int enslam_eventnet_fold_pack(const void* const* params, float* packed, void* st
 int enslam_eventnet_fold_pack_backward(const void* const* params, const float* g_packed, void* const* grads, double* scratch,
                                        void* stream) {
     if (!params || !g_packed || !grads || !scratch) return ENSLAM_EINVAL;
-    for (int k = 0; k < 5 * EN_NCONV + 4; ++k)
-        if (!params[k]) return ENSLAM_EINVAL;
-    for (int k = 0; k < 3 * EN_NCONV + 4; ++k)
-        if (!grads[k]) return ENSLAM_EINVAL;
+    if (!all_set(params, 5 * EN_NCONV + 4)) return ENSLAM_EINVAL;
+    if (!all_set(grads, 3 * EN_NCONV + 4)) return ENSLAM_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const PackOff po = pack_offsets();
     FoldTable tb;
@@ -1382,82 +1202,266 @@ __global__ __launch_bounds__(256) void train_add_kernel(float* __restrict__ acc,
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// the training workspace (float offsets; every region a multiple of 64 floats, so the float64 regions are 8-byte aligned)
+// The workspace of a batch of B images (float offsets; every region a multiple of 64 floats, so the float64 regions are
+// 8-byte aligned), from the description.  A convolution's saved output is y[conv] on both routes.  The folded route
+// (bn == false, B == 1) fuses bias and ReLU into the convolution's epilogue, so z[conv] IS y[conv]; the training-mode route
+// keeps the raw z and the BatchNorm + ReLU y, and the unfolded weights, BatchNorm statistics and gradient staging besides.
 // ---------------------------------------------------------------------------------------------------------------
-int conv_level(int i) { return i < 10 ? i / 2 : 3 - ((i - 10) % 8) / 2; }
-
-struct TrainPlan {
+struct Plan {
     int B, H[5], W[5];
     int64_t P[5];
-    int64_t x8, z[EN_NCONV], y[EN_NCONV], pool[5], up[2][4], probs, df[5], t[3], part, wscr, wscr_floats, gw, gwtmp, heads, hgrad,
-        wf[EN_NCONV], wt[EN_NCONV], dummy, stat, bnscr, total;
     int first[EN_NCONV];          // first channel of each BatchNorm in the concatenated statistics
+    int64_t x8, z[EN_NCONV], y[EN_NCONV];
+    int64_t in[EN_NCONV][2];      // where the convolution's two sources are read: x8, a y[], or the pooled / up-sampled copy
+    int64_t df[EN_NCONV];         // the summed gradient of an output that more than one layer reads (else -1)
+    int64_t probs, t[3], part, wscr_floats, total;
+    int64_t wf[EN_NCONV], wt[EN_NCONV], wscr, gw, gwtmp, heads, hgrad, dummy, stat, bnscr;      // bn only
 };
+bool size_ok(int H, int W) { return H >= 16 && W >= 16 && (int64_t)H * W <= (1 << 21); }
+// the batch statistics of the deepest level need two values per channel
 bool train_size_ok(int B, int H, int W) {
-    return B >= 1 && B <= 8 && H >= 16 && W >= 16 && (int64_t)B * H * W <= (1 << 21);
+    return B >= 1 && B <= 8 && H >= 16 && W >= 16 && (int64_t)B * H * W <= (1 << 21) && (int64_t)B * (H / 16) * (W / 16) >= 2;
 }
-TrainPlan make_train_plan(int B, int H, int W) {
-    TrainPlan tp;
-    tp.B = B;
+Plan make_plan(int B, int H, int W, bool bn) {
+    Plan pl = {};
+    pl.B = B;
     for (int l = 0; l < 5; ++l) {
-        tp.H[l] = l ? tp.H[l - 1] / 2 : H;
-        tp.W[l] = l ? tp.W[l - 1] / 2 : W;
-        tp.P[l] = (int64_t)tp.H[l] * tp.W[l];
+        pl.H[l] = l ? pl.H[l - 1] / 2 : H;
+        pl.W[l] = l ? pl.W[l - 1] / 2 : W;
+        pl.P[l] = (int64_t)pl.H[l] * pl.W[l];
     }
     int64_t q = 0, part = 0, wscr = 0, gw = 0, bnscr = 0;
     auto take = [&](int64_t n) { const int64_t at = q; q += (n + 63) / 64 * 64; return at; };
-    tp.x8 = take(B * tp.P[0] * 8);
-    int ch = 0;
+    int readers[EN_NCONV] = {}, ch = 0;
+    for (const ConvDesc& c : EN_CONV)
+        for (const Source& s : c.src)
+            if (s.conv >= 0) ++readers[s.conv];
+    pl.x8 = take(B * pl.P[0] * 8);
     for (int i = 0; i < EN_NCONV; ++i) {
-        const int l = conv_level(i), cin = EN_CONV[i].cin, cout = EN_CONV[i].cout;
-        tp.z[i] = take(B * tp.P[l] * cout);
-        tp.y[i] = take(B * tp.P[l] * cout);
-        tp.wf[i] = take((int64_t)9 * cin * cout);
-        tp.wt[i] = take((int64_t)9 * cin * cout);
-        tp.first[i] = ch;
+        const ConvDesc& c = EN_CONV[i];
+        const int cin = c.cin(), cout = c.cout;
+        const int64_t P = pl.P[c.level], n = B * P * cout, nw = (int64_t)9 * cin * cout;
+        pl.y[i] = take(n);
+        pl.z[i] = bn ? take(n) : pl.y[i];
+        pl.df[i] = readers[i] > 1 ? take(n) : -1;
+        for (int s = 0; s < 2; ++s) {
+            const Source& sc = c.src[s];
+            pl.in[i][s] = sc.kind == SRC_X8     ? pl.x8
+                          : sc.kind == SRC_OUT  ? pl.y[sc.conv]
+                          : sc.kind == SRC_POOL ? take(B * P * sc.ch)
+                          : sc.kind == SRC_UP   ? take(B * 4 * pl.P[EN_CONV[sc.conv].level] * sc.ch)
+                                                : -1;
+        }
+        if (bn) {
+            pl.wf[i] = take(nw);
+            pl.wt[i] = take(nw);
+        }
+        pl.first[i] = ch;
         ch += cout;
-        part = std::max(part, std::max(split_floats(tp.P[l], cin, cout), split_floats(tp.P[l], cout, cin)));
-        wscr = std::max(wscr, wgrad_floats(tp.P[l], cin, cout));
-        gw = std::max(gw, (int64_t)9 * cin * cout);
-        bnscr = std::max(bnscr, bn_part_doubles(B * tp.P[l], cout) + 2 * cout);
+        part = std::max(part, std::max(split_floats(P, cin, cout), split_floats(P, cout, cin)));
+        wscr = std::max(wscr, wgrad_floats(P, cin, cout));
+        gw = std::max(gw, nw);
+        bnscr = std::max(bnscr, bn_part_doubles(B * P, cout) + 2 * cout);
     }
-    for (int l = 0; l < 5; ++l) {
-        tp.pool[l] = l ? take(B * tp.P[l] * EN_ENC_C[l - 1]) : -1;
-        tp.df[l] = take(B * tp.P[l] * EN_ENC_C[l]);
-    }
-    for (int hd = 0; hd < 2; ++hd)
-        for (int j = 0; j < 4; ++j) tp.up[hd][j] = take(B * 4 * tp.P[4 - j] * EN_DEC_CD[j]);
-    tp.probs = take(B * 2 * tp.P[0]);
-    for (int k = 0; k < 3; ++k) tp.t[k] = take(B * tp.P[0] * 64);
-    tp.part = take(part);
+    pl.probs = take(B * 2 * pl.P[0]);
+    // transient gradients: at most P0 * 64 floats each per image (level l has P0 / 4^l pixels and at most 64 * 2^l channels)
+    for (int k = 0; k < 3; ++k) pl.t[k] = take(B * pl.P[0] * 64);
+    pl.part = take(part);
+    // scratch of the weight gradients: the largest split-partial block of the 26 convolutions, or the heads'
     int per_block;
-    wscr = std::max(wscr, (int64_t)B * heads_wgrad_blocks(tp.P[0], per_block) * 260);
-    tp.wscr_floats = wscr;
-    tp.wscr = take(wscr);
-    tp.gw = take(gw);
-    tp.gwtmp = take(gw);
-    tp.heads = take(EN_HEADS_FLOATS);
-    tp.hgrad = take(EN_HEADS_FLOATS);
-    tp.dummy = take(2 * 1024);
-    tp.stat = take(2 * 2 * EN_BN_CHANNELS);         // float64 mean [5888] | var [5888]
-    tp.bnscr = take(2 * bnscr);                      // float64
-    tp.total = q;
-    return tp;
+    pl.wscr_floats = std::max(wscr, (int64_t)B * heads_wgrad_blocks(pl.P[0], per_block) * 260);
+    if (bn) {
+        pl.wscr = take(pl.wscr_floats);
+        pl.gw = take(gw);
+        pl.gwtmp = take(gw);
+        pl.heads = take(EN_HEADS_FLOATS);
+        pl.hgrad = take(EN_HEADS_FLOATS);
+        pl.dummy = take(2 * 1024);
+        pl.stat = take(2 * 2 * EN_BN_CHANNELS);         // float64 mean [5888] | var [5888]
+        pl.bnscr = take(2 * bnscr);                      // float64
+    }
+    pl.total = q;
+    return pl;
 }
 
-int train_fold_table(const void* const* params, float* ws, const TrainPlan& tp, FoldTable& tb) {
-    int blocks = 0;
+// ---------------------------------------------------------------------------------------------------------------
+// The two walks over the description.  Every launch is per image (BatchNorm alone sees the whole batch); with B == 1 each loop
+// body runs once.  A route binds where the weights live and what surrounds a convolution:
+//   folded (enslam_eventnet_forward / _backward / _backward_weights): weights in the packed image, bias + ReLU in the
+//     convolution's epilogue; the backward masks the incoming gradient by the saved output at load (relu'(0) = 0 as in torch).
+//   training mode (enslam_eventnet_train_*): the unfolded copies in the workspace, BatchNorm statistics + apply after every
+//     convolution; the backward runs BatchNorm + ReLU backwards in place first, and needs no mask.
+// ---------------------------------------------------------------------------------------------------------------
+struct Route {
+    const float *wf[EN_NCONV], *bias[EN_NCONV], *wt[EN_NCONV], *heads;
+    int relu;
+};
+Route packed_route(const float* packed, const PackOff& po) {
+    Route r;
     for (int i = 0; i < EN_NCONV; ++i) {
-        FoldArgs& a = tb.a[i];
-        a = FoldArgs{};
-        a.w = (const float*)params[3 * i];
-        a.wf = ws + tp.wf[i]; a.wt = ws + tp.wt[i];
-        a.cinp = EN_CONV[i].cin; a.cin = i ? a.cinp : 6; a.cout = EN_CONV[i].cout;
-        tb.first[i] = blocks;
-        blocks += ((a.cinp + EN_FT - 1) / EN_FT) * ((a.cout + EN_FT - 1) / EN_FT);
+        r.wf[i] = packed + po.wf[i]; r.bias[i] = packed + po.b[i]; r.wt[i] = packed + po.wt[i];
     }
-    tb.first[EN_NCONV] = blocks;
-    return blocks;
+    r.heads = packed + po.heads;
+    r.relu = 1;
+    return r;
+}
+Route workspace_route(const float* ws, const Plan& pl) {
+    Route r;
+    for (int i = 0; i < EN_NCONV; ++i) {
+        r.wf[i] = ws + pl.wf[i]; r.bias[i] = nullptr; r.wt[i] = ws + pl.wt[i];
+    }
+    r.heads = ws + pl.heads;
+    r.relu = 0;
+    return r;
+}
+
+// a convolution's geometry: its level's extent, the channels of its two sources, and the extent of the up-sampled one
+struct ConvGeom { int H, W, C0, C1, lk, sH1, sW1; int64_t P; };
+ConvGeom conv_geom(const Plan& pl, const ConvDesc& c) {
+    ConvGeom g = {pl.H[c.level], pl.W[c.level], c.src[0].ch, c.src[1].ch, -1, 0, 0, pl.P[c.level]};
+    const Source& s = c.src[0].kind == SRC_POOL ? c.src[0] : c.src[1];      // src[0] is never SRC_UP, src[1] nothing else
+    if (s.conv >= 0) g.lk = EN_CONV[s.conv].level;
+    if (c.src[1].kind == SRC_UP) {
+        g.sH1 = 2 * pl.H[g.lk];
+        g.sW1 = 2 * pl.W[g.lk];
+    }
+    return g;
+}
+
+// after(i): what follows convolution i's B launches into z[i] (training mode: BatchNorm over the whole batch, z[i] -> y[i])
+template <class After>
+void walk_forward(const Plan& pl, const Route& r, float* ws, const float* x, float* events, float* probs, hipStream_t st,
+                  After after) {
+    const int B = pl.B;
+    const int64_t P0 = pl.P[0];
+    for (int b = 0; b < B; ++b)
+        en_pack_x_kernel<<<blocks_of(P0 * 8), 256, 0, st>>>(x + b * 6 * P0, (int)P0, ws + pl.x8 + b * P0 * 8);
+    for (int i = 0; i < EN_NCONV; ++i) {
+        const ConvDesc& c = EN_CONV[i];
+        const ConvGeom cg = conv_geom(pl, c);
+        const float *s0 = ws + pl.in[i][0], *s1 = cg.C1 ? ws + pl.in[i][1] : nullptr;
+        if (c.src[0].kind == SRC_POOL) {
+            const float* from = ws + pl.y[c.src[0].conv];
+            for (int b = 0; b < B; ++b)
+                pool2_fwd_kernel<<<blocks_of(cg.P * cg.C0), 256, 0, st>>>(from + b * pl.P[cg.lk] * cg.C0, pl.H[cg.lk], pl.W[cg.lk],
+                                                                          cg.C0, ws + pl.in[i][0] + b * cg.P * cg.C0);
+        }
+        if (c.src[1].kind == SRC_UP) {
+            const float* from = ws + pl.y[c.src[1].conv];
+            const int64_t n = pl.P[cg.lk] * cg.C1;
+            for (int b = 0; b < B; ++b)
+                up2_fwd_kernel<<<blocks_of(4 * n), 256, 0, st>>>(from + b * n, pl.H[cg.lk], pl.W[cg.lk], cg.C1,
+                                                                 ws + pl.in[i][1] + b * 4 * n);
+        }
+        for (int b = 0; b < B; ++b) {
+            ConvArgs a = {};
+            a.w = r.wf[i]; a.bias = r.bias[i];
+            a.s0 = s0 + b * cg.P * cg.C0;
+            a.s1 = s1 ? s1 + (int64_t)b * cg.sH1 * cg.sW1 * cg.C1 : nullptr;
+            a.d0 = ws + pl.z[i] + b * cg.P * c.cout; a.part = ws + pl.part;
+            a.H = cg.H; a.W = cg.W; a.C0 = cg.C0; a.C1 = cg.C1; a.sH1 = cg.sH1; a.sW1 = cg.sW1;
+            a.N = a.N0 = c.cout; a.relu = r.relu;
+            launch_conv(a, st);
+        }
+        after(i);
+    }
+    for (int b = 0; b < B; ++b)
+        heads_fwd_kernel<<<blocks_of(2 * P0), 256, 0, st>>>(r.heads, ws + pl.y[EN_HEAD[0].last] + b * P0 * 64,
+                                                            ws + pl.y[EN_HEAD[1].last] + b * P0 * 64, (int)P0, events + b * 2 * P0,
+                                                            probs + b * 2 * P0, ws + pl.probs + b * 2 * P0);
+}
+
+// the heads block's gradient: per image into scratch [B][blocks][260], summed in that order into dst [EN_HEADS_FLOATS]
+void launch_heads_wgrad(const Plan& pl, const float* ws, const float* g_events, const float* g_probs, float* scratch, float* dst,
+                        hipStream_t st) {
+    const int64_t P0 = pl.P[0];
+    int per_block;
+    const int blocks = heads_wgrad_blocks(P0, per_block);
+    for (int b = 0; b < pl.B; ++b)
+        heads_wgrad_kernel<<<blocks, 256, 0, st>>>(g_events + b * 2 * P0, g_probs + b * 2 * P0, ws + pl.probs + b * 2 * P0,
+                                                   ws + pl.y[EN_HEAD[0].last] + b * P0 * 64,
+                                                   ws + pl.y[EN_HEAD[1].last] + b * P0 * 64, (int)P0, per_block,
+                                                   scratch + (int64_t)b * blocks * 260);
+    heads_wgrad_reduce_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>(scratch, pl.B * blocks, dst);
+}
+
+// The backward walk: each head's decoder from its last convolution down, then the encoder.  g is the gradient of the current
+// convolution's output.  It travels through the transients tA / tB (a transposed convolution writes the one it does not
+// read); the up-sampled source's gradient goes through tC and up2_bwd; an output that several layers read collects its
+// gradient in df[]: the first writer of this walk stores, the later ones add (the skips: acc0 = head; the bottleneck's
+// up2_bwd likewise; pool2_bwd always comes after a skip and adds).  Per layer the order is fixed:
+//   before(i, g)      folded: returns the saved output, the ReLU mask of g.  Training mode: BatchNorm + ReLU backwards in
+//                     place, g becomes the gradient of z[i]; returns null.
+//   wgrad(i, b, a)    image b's weight gradient from a (sources, g, mask, shapes filled in); it reads g before the transposed
+//                     convolution overwrites a transient.  The route supplies the destination, or skips an unwanted one.
+//   the transposed convolution, into the sources' gradients.  g_x == null skips the first layer's and the unpack.
+template <class Before, class Wgrad>
+void walk_backward(const Plan& pl, const Route& r, float* ws, const float* g_events, const float* g_probs, float* g_x,
+                   hipStream_t st, Before before, Wgrad wgrad) {
+    const int B = pl.B;
+    const int64_t P0 = pl.P[0];
+    float *tA = ws + pl.t[0], *tB = ws + pl.t[1], *tC = ws + pl.t[2], *g = nullptr;
+    bool stored[EN_NCONV] = {};
+    auto add_to = [&](int k) { const int acc = stored[k]; stored[k] = true; return acc; };
+    auto back = [&](int i) {
+        const ConvDesc& c = EN_CONV[i];
+        const ConvGeom cg = conv_geom(pl, c);
+        const int k0 = c.src[0].conv, k1 = c.src[1].conv;
+        const int64_t n_out = cg.P * c.cout;
+        if (pl.df[i] >= 0) g = ws + pl.df[i];
+        const float* mask = before(i, g);
+        for (int b = 0; b < B; ++b) {
+            WgradArgs a = {};
+            a.s0 = ws + pl.in[i][0] + b * cg.P * cg.C0;
+            a.s1 = cg.C1 ? ws + pl.in[i][1] + (int64_t)b * cg.sH1 * cg.sW1 * cg.C1 : nullptr;
+            a.g = g + b * n_out; a.saved = mask ? mask + b * n_out : nullptr;
+            a.H = cg.H; a.W = cg.W; a.C0 = cg.C0; a.C1 = cg.C1; a.sH1 = cg.sH1; a.sW1 = cg.sW1; a.N = c.cout;
+            wgrad(i, b, a);
+        }
+        // d(sources) from g: C0 channels to d0 (a skip's straight into its df), the up-sampled source's C1 to tC
+        const bool skip = c.src[0].kind == SRC_OUT && pl.df[k0] >= 0;
+        float* d0 = skip ? ws + pl.df[k0] : g == tA ? tB : tA;
+        const int acc0 = skip ? add_to(k0) : 0;
+        if (c.src[0].kind != SRC_X8 || g_x)
+            for (int b = 0; b < B; ++b) {
+                ConvArgs a = {};
+                a.w = r.wt[i];
+                a.s0 = g + b * n_out; a.mask = mask ? mask + b * n_out : nullptr; a.C0 = c.cout;
+                a.d0 = d0 + b * cg.P * cg.C0;
+                a.d1 = cg.C1 ? tC + (int64_t)b * cg.sH1 * cg.sW1 * cg.C1 : nullptr;
+                a.part = ws + pl.part;
+                a.H = cg.H; a.W = cg.W; a.N = c.cin(); a.N0 = cg.C0; a.dH1 = cg.sH1; a.dW1 = cg.sW1; a.acc0 = acc0;
+                launch_conv(a, st);
+            }
+        if (c.src[0].kind == SRC_POOL) {
+            const int64_t n = pl.P[cg.lk] * cg.C0;
+            const int acc = add_to(k0);
+            for (int b = 0; b < B; ++b)
+                pool2_bwd_kernel<<<blocks_of(n), 256, 0, st>>>(ws + pl.y[k0] + b * n, pl.H[cg.lk], pl.W[cg.lk], cg.C0,
+                                                               d0 + b * cg.P * cg.C0, ws + pl.df[k0] + b * n, acc);
+        }
+        if (c.src[1].kind == SRC_UP) {
+            const int64_t n = pl.P[cg.lk] * cg.C1;
+            float* dst = pl.df[k1] >= 0 ? ws + pl.df[k1] : tA;
+            const int acc = pl.df[k1] >= 0 ? add_to(k1) : 0;
+            for (int b = 0; b < B; ++b)
+                up2_bwd_kernel<<<blocks_of(n), 256, 0, st>>>(tC + b * 4 * n, pl.H[cg.lk], pl.W[cg.lk], cg.C1, dst + b * n, acc);
+            g = tA;
+        } else {
+            g = d0;
+        }
+    };
+    for (int hd = 0; hd < 2; ++hd) {
+        for (int b = 0; b < B; ++b)
+            heads_bwd_kernel<<<blocks_of(P0 * 64), 256, 0, st>>>(r.heads, hd, (hd ? g_probs : g_events) + b * 2 * P0,
+                                                                 ws + pl.probs + b * 2 * P0, (int)P0, tA + b * P0 * 64);
+        g = tA;
+        for (int i = EN_HEAD[hd].last; i >= EN_HEAD[hd].first; --i) back(i);
+    }
+    for (int i = EN_HEAD[0].first - 1; i >= 0; --i) back(i);
+    if (g_x)
+        for (int b = 0; b < B; ++b)
+            en_unpack_gx_kernel<<<blocks_of(P0 * 6), 256, 0, st>>>(g + b * P0 * 8, (int)P0, g_x + b * 6 * P0);
 }
 
 }  // namespace
@@ -1493,214 +1497,182 @@ int enslam_eventnet_bn_backward(const float* z, const float* y, const float* g_y
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
 
+// ---- the folded route: frozen BatchNorm, one image ----
+
+size_t enslam_eventnet_workspace_floats(int32_t H, int32_t W) {
+    if (!size_ok(H, W)) return 0;
+    return (size_t)make_plan(1, H, W, false).total;
+}
+
+int enslam_eventnet_forward(const float* packed, const float* x, int32_t H, int32_t W, float* workspace, float* events,
+                            float* probs, void* stream) {
+    if (!packed || !x || !workspace || !events || !probs) return ENSLAM_EINVAL;
+    if (!size_ok(H, W)) return ENSLAM_EINVAL;
+    const Plan pl = make_plan(1, H, W, false);
+    walk_forward(pl, packed_route(packed, pack_offsets()), workspace, x, events, probs, (hipStream_t)stream, [](int) {});
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+}  // extern "C"
+
+namespace {
+// g_packed == null: the input gradient only (enslam_eventnet_backward).  Otherwise every layer's weight gradient goes
+// straight into g_packed, whose Wt blocks (the same weights again) are zeroed.
+int run_backward(const float* packed, float* ws, const float* g_events, const float* g_probs, float* g_x, float* g_packed,
+                 float* scratch, int H, int W, hipStream_t st) {
+    const Plan pl = make_plan(1, H, W, false);
+    const PackOff po = pack_offsets();
+    if (g_packed) launch_heads_wgrad(pl, ws, g_events, g_probs, scratch, g_packed + po.heads, st);
+    walk_backward(
+        pl, packed_route(packed, po), ws, g_events, g_probs, g_x, st, [&](int i, float*) { return ws + pl.y[i]; },
+        [&](int i, int, WgradArgs a) {
+            if (!g_packed) return;
+            a.dw = g_packed + po.wf[i]; a.db = g_packed + po.b[i]; a.part = scratch;
+            launch_wgrad(a, st);
+            // the launch's status is read by hipGetLastError below
+            (void)hipMemsetAsync(g_packed + po.wt[i], 0, sizeof(float) * 9 * EN_CONV[i].cin() * EN_CONV[i].cout, st);
+        });
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+int64_t wgrad_scratch_floats(int H, int W) { return (make_plan(1, H, W, false).wscr_floats + 63) / 64 * 64; }
+}  // namespace
+
+extern "C" {
+
+int enslam_eventnet_backward(const float* packed, float* workspace, const float* g_events, const float* g_probs,
+                             float* g_x, int32_t H, int32_t W, void* stream) {
+    if (!packed || !workspace || !g_events || !g_probs || !g_x) return ENSLAM_EINVAL;
+    if (!size_ok(H, W)) return ENSLAM_EINVAL;
+    return run_backward(packed, workspace, g_events, g_probs, g_x, nullptr, nullptr, H, W, (hipStream_t)stream);
+}
+
+size_t enslam_eventnet_wgrad_scratch_floats(int32_t H, int32_t W) {
+    if (!size_ok(H, W)) return 0;
+    return (size_t)wgrad_scratch_floats(H, W);
+}
+
+int enslam_eventnet_backward_weights(const float* packed, float* workspace, const float* g_events, const float* g_probs,
+                                     float* g_x, float* g_packed, float* scratch, int64_t scratch_floats, int32_t H, int32_t W,
+                                     void* stream) {
+    if (!packed || !workspace || !g_events || !g_probs || !g_packed || !scratch) return ENSLAM_EINVAL;
+    if (!size_ok(H, W)) return ENSLAM_EINVAL;
+    if (scratch_floats < wgrad_scratch_floats(H, W)) return ENSLAM_EINVAL;
+    return run_backward(packed, workspace, g_events, g_probs, g_x, g_packed, scratch, H, W, (hipStream_t)stream);
+}
+
+int enslam_eventnet_heads_wgrad(const float* workspace, const float* g_events, const float* g_probs, float* g_heads,
+                                float* scratch, int64_t scratch_floats, int32_t H, int32_t W, void* stream) {
+    if (!workspace || !g_events || !g_probs || !g_heads || !scratch) return ENSLAM_EINVAL;
+    if (!size_ok(H, W)) return ENSLAM_EINVAL;
+    const Plan pl = make_plan(1, H, W, false);
+    int per_block;
+    if (scratch_floats < (int64_t)heads_wgrad_blocks(pl.P[0], per_block) * 260) return ENSLAM_EINVAL;
+    launch_heads_wgrad(pl, workspace, g_events, g_probs, scratch, g_heads, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+// ---- the training-mode route: batch statistics, B images ----
+
 int enslam_eventnet_bn_running(void* const* buffers, const double* batch_mean, const double* batch_var, int32_t B, int32_t H,
                                int32_t W, double momentum, void* stream) {
     if (!buffers || !batch_mean || !batch_var || !train_size_ok(B, H, W)) return ENSLAM_EINVAL;
-    if ((int64_t)B * (H / 16) * (W / 16) < 2 || !(momentum >= 0.0 && momentum <= 1.0)) return ENSLAM_EINVAL;
-    const TrainPlan tp = make_train_plan(B, H, W);
+    if (!(momentum >= 0.0 && momentum <= 1.0) || !all_set(buffers, 2 * EN_NCONV)) return ENSLAM_EINVAL;
+    const Plan pl = make_plan(B, H, W, true);
     BnRunArgs a;
     for (int i = 0; i < EN_NCONV; ++i) {
-        if (!buffers[2 * i] || !buffers[2 * i + 1]) return ENSLAM_EINVAL;
         a.rm[i] = (float*)buffers[2 * i];
         a.rv[i] = (float*)buffers[2 * i + 1];
-        a.first[i] = tp.first[i];
+        a.first[i] = pl.first[i];
         a.C[i] = EN_CONV[i].cout;
-        a.M[i] = (int)(B * tp.P[conv_level(i)]);
+        a.M[i] = (int)(B * pl.P[EN_CONV[i].level]);
     }
     bn_running_kernel<<<dim3(2, EN_NCONV), 256, 0, (hipStream_t)stream>>>(a, batch_mean, batch_var, momentum);
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
 
 size_t enslam_eventnet_bn_workspace_floats(int32_t B, int32_t H, int32_t W) {
-    if (!train_size_ok(B, H, W) || (int64_t)B * (H / 16) * (W / 16) < 2) return 0;
-    return (size_t)make_train_plan(B, H, W).total;
+    if (!train_size_ok(B, H, W)) return 0;
+    return (size_t)make_plan(B, H, W, true).total;
 }
 
 int64_t enslam_eventnet_bn_saved_offset(int32_t B, int32_t H, int32_t W, int32_t conv) {
-    if (!train_size_ok(B, H, W) || (int64_t)B * (H / 16) * (W / 16) < 2 || conv < 0 || conv >= EN_NCONV) return -1;
-    return make_train_plan(B, H, W).y[conv];
+    if (!train_size_ok(B, H, W) || conv < 0 || conv >= EN_NCONV) return -1;
+    return make_plan(B, H, W, true).y[conv];
 }
 
+/* params: per convolution 3 device addresses (w, gamma, beta), then W1, W2, b1, b2 of the heads */
 int enslam_eventnet_train_forward(const void* const* params, const float* x, int32_t B, int32_t H, int32_t W, double eps,
                                   float* workspace, float* events, float* probs, double* batch_mean, double* batch_var,
                                   void* stream) {
     if (!params || !x || !workspace || !events || !probs || !batch_mean || !batch_var) return ENSLAM_EINVAL;
-    for (int k = 0; k < 3 * EN_NCONV + 4; ++k)
-        if (!params[k]) return ENSLAM_EINVAL;
-    if (!train_size_ok(B, H, W) || (int64_t)B * (H / 16) * (W / 16) < 2 || !(eps >= 0.0)) return ENSLAM_EINVAL;
+    if (!all_set(params, 3 * EN_NCONV + 4)) return ENSLAM_EINVAL;
+    if (!train_size_ok(B, H, W) || !(eps >= 0.0)) return ENSLAM_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const TrainPlan tp = make_train_plan(B, H, W);
+    const Plan pl = make_plan(B, H, W, true);
     float* ws = workspace;
-    double* mean = reinterpret_cast<double*>(ws + tp.stat);
+    double* mean = reinterpret_cast<double*>(ws + pl.stat);
     double* var = mean + EN_BN_CHANNELS;
-    double* bnscr = reinterpret_cast<double*>(ws + tp.bnscr);
-    {
-        FoldTable tb;
-        const int blocks = train_fold_table(params, ws, tp, tb);
-        train_pack_kernel<<<blocks, 256, 0, st>>>(tb);
-        const void* const* h = params + 3 * EN_NCONV;
-        heads_pack_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>((float*)h[0], (float*)h[1], (float*)h[2], (float*)h[3], ws + tp.heads, 0);
+    double* bnscr = reinterpret_cast<double*>(ws + pl.bnscr);
+    FoldTable tb;
+    const int blocks = fold_shapes(params, 3, tb);
+    for (int i = 0; i < EN_NCONV; ++i) {
+        tb.a[i].wf = ws + pl.wf[i]; tb.a[i].wt = ws + pl.wt[i];
     }
-    // convolution i of every image, then BatchNorm over the whole batch: z[i] -> y[i]
-    auto layer = [&](int i, const float* s0, int C0, const float* s1, int C1, int sH1, int sW1) {
-        const int l = conv_level(i), cout = EN_CONV[i].cout;
-        for (int b = 0; b < B; ++b) {
-            ConvArgs a = {};
-            a.w = ws + tp.wf[i];
-            a.s0 = s0 + b * tp.P[l] * C0;
-            a.s1 = s1 ? s1 + (int64_t)b * sH1 * sW1 * C1 : nullptr;
-            a.d0 = ws + tp.z[i] + b * tp.P[l] * cout; a.part = ws + tp.part;
-            a.H = tp.H[l]; a.W = tp.W[l]; a.C0 = C0; a.C1 = C1; a.sH1 = sH1; a.sW1 = sW1;
-            a.N = a.N0 = cout;
-            launch_conv(a, st);
-        }
-        const int M = (int)(B * tp.P[l]);
-        launch_bn_stats(ws + tp.z[i], M, cout, mean + tp.first[i], var + tp.first[i], bnscr, st);
-        launch_bn_apply(ws + tp.z[i], (const float*)params[3 * i + 1], (const float*)params[3 * i + 2], mean + tp.first[i],
-                        var + tp.first[i], eps, M, cout, 1, ws + tp.y[i], st);
-    };
-    for (int b = 0; b < B; ++b)
-        en_pack_x_kernel<<<blocks_of(tp.P[0] * 8), 256, 0, st>>>(x + b * 6 * tp.P[0], (int)tp.P[0], ws + tp.x8 + b * tp.P[0] * 8);
-    for (int l = 0; l < 5; ++l) {
-        const float* in = ws + tp.x8;
-        int cin = 8;
-        if (l) {
-            cin = EN_ENC_C[l - 1];
-            for (int b = 0; b < B; ++b)
-                pool2_fwd_kernel<<<blocks_of(tp.P[l] * cin), 256, 0, st>>>(ws + tp.y[2 * l - 1] + b * tp.P[l - 1] * cin, tp.H[l - 1],
-                                                                           tp.W[l - 1], cin, ws + tp.pool[l] + b * tp.P[l] * cin);
-            in = ws + tp.pool[l];
-        }
-        layer(2 * l, in, cin, nullptr, 0, 0, 0);
-        layer(2 * l + 1, ws + tp.y[2 * l], EN_ENC_C[l], nullptr, 0, 0, 0);
-    }
-    for (int hd = 0; hd < 2; ++hd) {
-        const float* deep = ws + tp.y[9];
-        for (int j = 0; j < 4; ++j) {
-            const int ls = 3 - j, ld = ls + 1, cd = EN_DEC_CD[j], i0 = 10 + 8 * hd + 2 * j;
-            for (int b = 0; b < B; ++b)
-                up2_fwd_kernel<<<blocks_of(4 * tp.P[ld] * cd), 256, 0, st>>>(deep + b * tp.P[ld] * cd, tp.H[ld], tp.W[ld], cd,
-                                                                             ws + tp.up[hd][j] + b * 4 * tp.P[ld] * cd);
-            layer(i0, ws + tp.y[2 * ls + 1], cd, ws + tp.up[hd][j], cd, 2 * tp.H[ld], 2 * tp.W[ld]);
-            layer(i0 + 1, ws + tp.y[i0], cd, nullptr, 0, 0, 0);
-            deep = ws + tp.y[i0 + 1];
-        }
-    }
-    for (int b = 0; b < B; ++b)
-        heads_fwd_kernel<<<blocks_of(2 * tp.P[0]), 256, 0, st>>>(ws + tp.heads, ws + tp.y[17] + b * tp.P[0] * 64,
-                                                                 ws + tp.y[25] + b * tp.P[0] * 64, (int)tp.P[0],
-                                                                 events + b * 2 * tp.P[0], probs + b * 2 * tp.P[0],
-                                                                 ws + tp.probs + b * 2 * tp.P[0]);
+    train_pack_kernel<<<blocks, 256, 0, st>>>(tb);
+    const void* const* h = params + 3 * EN_NCONV;
+    heads_pack_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>((float*)h[0], (float*)h[1], (float*)h[2], (float*)h[3], ws + pl.heads, 0);
+    walk_forward(pl, workspace_route(ws, pl), ws, x, events, probs, st, [&](int i) {
+        const int M = (int)(B * pl.P[EN_CONV[i].level]), cout = EN_CONV[i].cout;
+        launch_bn_stats(ws + pl.z[i], M, cout, mean + pl.first[i], var + pl.first[i], bnscr, st);
+        launch_bn_apply(ws + pl.z[i], (const float*)params[3 * i + 1], (const float*)params[3 * i + 2], mean + pl.first[i],
+                        var + pl.first[i], eps, M, cout, 1, ws + pl.y[i], st);
+    });
     (void)hipMemcpyAsync(batch_mean, mean, sizeof(double) * EN_BN_CHANNELS, hipMemcpyDeviceToDevice, st);
     (void)hipMemcpyAsync(batch_var, var, sizeof(double) * EN_BN_CHANNELS, hipMemcpyDeviceToDevice, st);
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
 
+/* grads: per convolution 3 device addresses (dw, dgamma, dbeta), then dW1, dW2, db1, db2; a null address skips that gradient
+   (the heads' four are wanted together or not at all) */
 int enslam_eventnet_train_backward(const void* const* params, float* workspace, const float* g_events, const float* g_probs,
                                    int32_t B, int32_t H, int32_t W, double eps, float* g_x, void* const* grads, void* stream) {
     if (!params || !workspace || !g_events || !g_probs || !grads) return ENSLAM_EINVAL;
-    for (int k = 0; k < 3 * EN_NCONV + 4; ++k)
-        if (!params[k]) return ENSLAM_EINVAL;
-    const bool heads_hot = grads[3 * EN_NCONV] != nullptr;
+    if (!all_set(params, 3 * EN_NCONV + 4)) return ENSLAM_EINVAL;
+    void* const* h = grads + 3 * EN_NCONV;
     for (int k = 1; k < 4; ++k)
-        if ((grads[3 * EN_NCONV + k] != nullptr) != heads_hot) return ENSLAM_EINVAL;
-    if (!train_size_ok(B, H, W) || (int64_t)B * (H / 16) * (W / 16) < 2 || !(eps >= 0.0)) return ENSLAM_EINVAL;
+        if ((h[k] != nullptr) != (h[0] != nullptr)) return ENSLAM_EINVAL;
+    if (!train_size_ok(B, H, W) || !(eps >= 0.0)) return ENSLAM_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const TrainPlan tp = make_train_plan(B, H, W);
+    const Plan pl = make_plan(B, H, W, true);
     float* ws = workspace;
-    const double* mean = reinterpret_cast<const double*>(ws + tp.stat);
+    const double* mean = reinterpret_cast<const double*>(ws + pl.stat);
     const double* var = mean + EN_BN_CHANNELS;
-    double* bnscr = reinterpret_cast<double*>(ws + tp.bnscr);
-    float *tA = ws + tp.t[0], *tB = ws + tp.t[1], *tC = ws + tp.t[2];
-    // BatchNorm + ReLU of convolution i backwards, in place: g (gradient of y[i]) becomes the gradient of z[i]
-    auto bn_bwd = [&](int i, float* g) {
-        const int l = conv_level(i), cout = EN_CONV[i].cout;
-        float* dg = grads[3 * i + 1] ? (float*)grads[3 * i + 1] : ws + tp.dummy;
-        float* db = grads[3 * i + 2] ? (float*)grads[3 * i + 2] : ws + tp.dummy + 1024;
-        launch_bn_backward(ws + tp.z[i], ws + tp.y[i], g, (const float*)params[3 * i + 1], mean + tp.first[i], var + tp.first[i],
-                           eps, (int)(B * tp.P[l]), cout, g, dg, db, bnscr, st);
-    };
-    // d(w of convolution i): per image in Wf's layout, summed in image order, then moved to the parameter's layout
-    auto wgrad = [&](int i, const float* s0, int C0, const float* s1, int C1, int sH1, int sW1, const float* g) {
-        if (!grads[3 * i]) return;
-        const int l = conv_level(i), cin = EN_CONV[i].cin, cout = EN_CONV[i].cout;
-        const int64_t n = (int64_t)9 * cin * cout;
-        for (int b = 0; b < B; ++b) {
-            WgradArgs a = {};
-            a.s0 = s0 + b * tp.P[l] * C0;
-            a.s1 = s1 ? s1 + (int64_t)b * sH1 * sW1 * C1 : nullptr;
-            a.g = g + b * tp.P[l] * cout;
-            a.dw = ws + (b ? tp.gwtmp : tp.gw); a.part = ws + tp.wscr;
-            a.H = tp.H[l]; a.W = tp.W[l]; a.C0 = C0; a.C1 = C1; a.sH1 = sH1; a.sW1 = sW1; a.N = cout;
+    double* bnscr = reinterpret_cast<double*>(ws + pl.bnscr);
+    if (h[0]) {
+        launch_heads_wgrad(pl, ws, g_events, g_probs, ws + pl.wscr, ws + pl.hgrad, st);
+        heads_pack_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>((float*)h[0], (float*)h[1], (float*)h[2], (float*)h[3], ws + pl.hgrad, 1);
+    }
+    walk_backward(
+        pl, workspace_route(ws, pl), ws, g_events, g_probs, g_x, st,
+        [&](int i, float* g) -> const float* {
+            float* dg = grads[3 * i + 1] ? (float*)grads[3 * i + 1] : ws + pl.dummy;
+            float* db = grads[3 * i + 2] ? (float*)grads[3 * i + 2] : ws + pl.dummy + 1024;
+            launch_bn_backward(ws + pl.z[i], ws + pl.y[i], g, (const float*)params[3 * i + 1], mean + pl.first[i],
+                               var + pl.first[i], eps, (int)(B * pl.P[EN_CONV[i].level]), EN_CONV[i].cout, g, dg, db, bnscr, st);
+            return nullptr;
+        },
+        // d(w of convolution i): per image in Wf's layout, summed in image order, then moved to the parameter's layout
+        [&](int i, int b, WgradArgs a) {
+            if (!grads[3 * i]) return;
+            const int cin = EN_CONV[i].cin(), cout = EN_CONV[i].cout;
+            const int64_t n = (int64_t)9 * cin * cout;
+            a.dw = ws + (b ? pl.gwtmp : pl.gw); a.part = ws + pl.wscr;
             launch_wgrad(a, st);
-            if (b) train_add_kernel<<<blocks_of(n), 256, 0, st>>>(ws + tp.gw, ws + tp.gwtmp, n);
-        }
-        train_unpack_dw_kernel<<<dim3((cin + EN_FT - 1) / EN_FT, (cout + EN_FT - 1) / EN_FT), 256, 0, st>>>(
-            ws + tp.gw, i ? cin : 6, cin, cout, (float*)grads[3 * i]);
-    };
-    // d(input of convolution i) from g = the gradient of z[i]: N0 channels to d0, the rest to d1
-    auto convT = [&](int i, const float* g, float* d0, int N0, int acc0, float* d1, int dH1, int dW1) {
-        const int l = conv_level(i), cin = EN_CONV[i].cin, cout = EN_CONV[i].cout;
-        for (int b = 0; b < B; ++b) {
-            ConvArgs a = {};
-            a.w = ws + tp.wt[i];
-            a.s0 = g + b * tp.P[l] * cout; a.C0 = cout;
-            a.d0 = d0 + b * tp.P[l] * N0;
-            a.d1 = d1 ? d1 + (int64_t)b * dH1 * dW1 * (cin - N0) : nullptr;
-            a.part = ws + tp.part;
-            a.H = tp.H[l]; a.W = tp.W[l]; a.N = cin; a.N0 = N0; a.dH1 = dH1; a.dW1 = dW1; a.acc0 = acc0;
-            launch_conv(a, st);
-        }
-    };
-    if (heads_hot) {
-        int per_block;
-        const int blocks = heads_wgrad_blocks(tp.P[0], per_block);
-        for (int b = 0; b < B; ++b)
-            heads_wgrad_kernel<<<blocks, 256, 0, st>>>(g_events + b * 2 * tp.P[0], g_probs + b * 2 * tp.P[0],
-                                                       ws + tp.probs + b * 2 * tp.P[0], ws + tp.y[17] + b * tp.P[0] * 64,
-                                                       ws + tp.y[25] + b * tp.P[0] * 64, (int)tp.P[0], per_block,
-                                                       ws + tp.wscr + (int64_t)b * blocks * 260);
-        heads_wgrad_reduce_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>(ws + tp.wscr, B * blocks, ws + tp.hgrad);
-        void* const* h = grads + 3 * EN_NCONV;
-        heads_pack_kernel<<<1, EN_HEADS_FLOATS, 0, st>>>((float*)h[0], (float*)h[1], (float*)h[2], (float*)h[3], ws + tp.hgrad, 1);
-    }
-    for (int hd = 0; hd < 2; ++hd) {
-        for (int b = 0; b < B; ++b)
-            heads_bwd_kernel<<<blocks_of(tp.P[0] * 64), 256, 0, st>>>(ws + tp.heads, hd, (hd ? g_probs : g_events) + b * 2 * tp.P[0],
-                                                                      ws + tp.probs + b * 2 * tp.P[0], (int)tp.P[0],
-                                                                      tA + b * tp.P[0] * 64);
-        for (int j = 3; j >= 0; --j) {
-            const int ls = 3 - j, ld = ls + 1, cd = EN_DEC_CD[j];
-            const int i1 = 11 + 8 * hd + 2 * j, i0 = i1 - 1;
-            bn_bwd(i1, tA);
-            wgrad(i1, ws + tp.y[i0], cd, nullptr, 0, 0, 0, tA);
-            convT(i1, tA, tB, cd, 0, nullptr, 0, 0);
-            bn_bwd(i0, tB);
-            wgrad(i0, ws + tp.y[2 * ls + 1], cd, ws + tp.up[hd][j], cd, 2 * tp.H[ld], 2 * tp.W[ld], tB);
-            convT(i0, tB, ws + tp.df[ls], cd, hd, tC, 2 * tp.H[ld], 2 * tp.W[ld]);
-            float* dst = j ? tA : ws + tp.df[4];
-            for (int b = 0; b < B; ++b)
-                up2_bwd_kernel<<<blocks_of(tp.P[ld] * cd), 256, 0, st>>>(tC + b * 4 * tp.P[ld] * cd, tp.H[ld], tp.W[ld], cd,
-                                                                         dst + b * tp.P[ld] * cd, j ? 0 : hd);
-        }
-    }
-    for (int l = 4; l >= 0; --l) {
-        const int c = EN_ENC_C[l], cin = EN_CONV[2 * l].cin;
-        bn_bwd(2 * l + 1, ws + tp.df[l]);
-        wgrad(2 * l + 1, ws + tp.y[2 * l], c, nullptr, 0, 0, 0, ws + tp.df[l]);
-        convT(2 * l + 1, ws + tp.df[l], tA, c, 0, nullptr, 0, 0);
-        bn_bwd(2 * l, tA);
-        wgrad(2 * l, l ? ws + tp.pool[l] : ws + tp.x8, cin, nullptr, 0, 0, 0, tA);
-        if (l || g_x) convT(2 * l, tA, tB, cin, 0, nullptr, 0, 0);
-        if (l)
-            for (int b = 0; b < B; ++b)
-                pool2_bwd_kernel<<<blocks_of(tp.P[l - 1] * cin), 256, 0, st>>>(ws + tp.y[2 * l - 1] + b * tp.P[l - 1] * cin,
-                                                                               tp.H[l - 1], tp.W[l - 1], cin, tB + b * tp.P[l] * cin,
-                                                                               ws + tp.df[l - 1] + b * tp.P[l - 1] * cin, 1);
-    }
-    if (g_x)
-        for (int b = 0; b < B; ++b)
-            en_unpack_gx_kernel<<<blocks_of(tp.P[0] * 6), 256, 0, st>>>(tB + b * tp.P[0] * 8, (int)tp.P[0], g_x + b * 6 * tp.P[0]);
+            if (b) train_add_kernel<<<blocks_of(n), 256, 0, st>>>(ws + pl.gw, ws + pl.gwtmp, n);
+            if (b == B - 1)
+                train_unpack_dw_kernel<<<dim3(tiles_of(cin, EN_FT), tiles_of(cout, EN_FT)), 256, 0, st>>>(
+                    ws + pl.gw, i ? cin : 6, cin, cout, (float*)grads[3 * i]);
+        });
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
 

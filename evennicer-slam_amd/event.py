@@ -220,6 +220,40 @@ def _conv_pairs(net):
     return pairs
 
 
+def _conv_bn_pairs(net):
+    """The 26 (convolution, BatchNorm) pairs in packing order."""
+    return [(p.double_conv[i], p.double_conv[i + 1]) for p in _conv_pairs(net) for i in (0, 3)]
+
+
+def _param_list(net):
+    """The 82 parameters in the order of the device entries: per convolution w, gamma, beta; then W1, W2, b1, b2 of the heads."""
+    params = [t for conv, bn in _conv_bn_pairs(net) for t in (conv.weight, bn.weight, bn.bias)]
+    return params + [net.outc_1.conv.weight, net.outc_2.conv.weight, net.outc_1.conv.bias, net.outc_2.conv.bias]
+
+
+def _check_input(x, max_batch=1):
+    """Raise NotImplementedError unless x is a device tensor [B,6,H >= 16,W >= 16] with 1 <= B <= max_batch."""
+    if not x.is_cuda:
+        raise NotImplementedError(f"the HIP event network needs its input on a HIP device (got {x.device}); use the torch "
+                                  "module on the CPU")
+    if max_batch == 1 and (x.dim() != 4 or x.shape[0] != 1):
+        raise NotImplementedError(f"the HIP event network runs batch 1 only (got an input of shape {tuple(x.shape)})")
+    if x.dim() != 4 or x.shape[1] != 6 or x.shape[2] < 16 or x.shape[3] < 16:
+        raise NotImplementedError(f"the HIP event network takes [{1 if max_batch == 1 else 'B'},6,H,W] with H, W >= 16 (got "
+                                  f"{tuple(x.shape)})")
+    if not 1 <= x.shape[0] <= max_batch:
+        raise NotImplementedError(f"the training-mode HIP event network runs batches of 1 to {max_batch} (got "
+                                  f"an input of shape {tuple(x.shape)})")
+
+
+def _cached(cache, key, make):
+    """cache[key], made on first use and kept (the per-shape workspaces)."""
+    ws = cache.get(key)
+    if ws is None:
+        ws = cache[key] = make()
+    return ws
+
+
 # (cin, cout) of the 26 convolutions in packing order (EN_CONV of csrc/event_net.hip; the first cin is 6 padded to 8)
 EVENTNET_CONVS = ((8, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 512), (512, 512), (512, 512),
                   (512, 512)) + ((1024, 512), (512, 256), (512, 256), (256, 128), (256, 128), (128, 64), (128, 64), (64, 64)) * 2
@@ -237,8 +271,7 @@ def check_event_net(net, frozen=True, eval_only=True):
     if (net.n_channels, net.n_classes1, net.n_classes2) != (6, 2, 2):
         raise NotImplementedError("the HIP event network implements UNet_2heads(6, 2, 2) only, got "
                                   f"({net.n_channels}, {net.n_classes1}, {net.n_classes2})")
-    convs = [m for pair in _conv_pairs(net) for m in (pair.double_conv[0], pair.double_conv[3])]
-    got = tuple((c.in_channels, c.out_channels) for c in convs)
+    got = tuple((c.in_channels, c.out_channels) for c, _ in _conv_bn_pairs(net))
     if got != ((6, 64),) + EVENTNET_CONVS[1:]:
         raise NotImplementedError(f"the HIP event network implements the widths {UNet_2heads.WIDTHS} only")
     if eval_only and net.training:
@@ -255,14 +288,13 @@ def fold_event_net(net):
     """[(w' float64 [cout,cin,3,3], b' float64 [cout])] of the 26 conv + BN pairs in packing order, folded in float64:
     w' = w * gamma / sqrt(var + eps), b' = beta + (conv bias - mean) * gamma / sqrt(var + eps)."""
     out = []
-    for pair in _conv_pairs(net):
-        for conv, bn in ((pair.double_conv[0], pair.double_conv[1]), (pair.double_conv[3], pair.double_conv[4])):
-            w = conv.weight.detach().cpu().double()
-            s = bn.weight.detach().cpu().double() / torch.sqrt(bn.running_var.detach().cpu().double() + bn.eps)
-            shift = -bn.running_mean.detach().cpu().double()
-            if conv.bias is not None:
-                shift = shift + conv.bias.detach().cpu().double()
-            out.append((w * s[:, None, None, None], bn.bias.detach().cpu().double() + shift * s))
+    for conv, bn in _conv_bn_pairs(net):
+        w = conv.weight.detach().cpu().double()
+        s = bn.weight.detach().cpu().double() / torch.sqrt(bn.running_var.detach().cpu().double() + bn.eps)
+        shift = -bn.running_mean.detach().cpu().double()
+        if conv.bias is not None:
+            shift = shift + conv.bias.detach().cpu().double()
+        out.append((w * s[:, None, None, None], bn.bias.detach().cpu().double() + shift * s))
     return out
 
 
@@ -323,20 +355,12 @@ class HipUNet2Heads(nn.Module):
 
     def forward(self, x):
         from . import functional as EF
-        if not x.is_cuda:
-            raise NotImplementedError(f"the HIP event network needs its input on a HIP device (got {x.device}); use the torch "
-                                      "module on the CPU")
-        if x.dim() != 4 or x.shape[0] != 1:
-            raise NotImplementedError(f"the HIP event network runs batch 1 only (got an input of shape {tuple(x.shape)})")
-        if x.shape[1] != 6 or x.shape[2] < 16 or x.shape[3] < 16:
-            raise NotImplementedError(f"the HIP event network takes [1,6,H,W] with H, W >= 16 (got {tuple(x.shape)})")
+        _check_input(x)
         if self.net.training:
             raise NotImplementedError("the HIP event network runs eval mode only: call .eval()")
         packed = self.packed(x.device)
         key = (int(x.shape[2]), int(x.shape[3]), x.device)
-        ws = self._workspaces.get(key)
-        if ws is None:
-            ws = self._workspaces[key] = EF.EventNetWorkspace(key[0], key[1], x.device)
+        ws = _cached(self._workspaces, key, lambda: EF.EventNetWorkspace(key[0], key[1], x.device))
         return EF.eventnet_apply(x, packed, ws)
 
 
@@ -362,7 +386,7 @@ def pack_event_net_differentiable(net, device=None, constants=None):
     rounded once to float32; then pack_conv's layout.  The transposed blocks are built without a graph: the image depends
     on a weight through Wf alone, which is where enslam_eventnet_backward_weights puts its gradient."""
     device = torch.device(device) if device is not None else next(net.parameters()).device
-    pairs = [(p.double_conv[i], p.double_conv[i + 1]) for p in _conv_pairs(net) for i in (0, 3)]
+    pairs = _conv_bn_pairs(net)
     if constants is None:
         constants = [_bn_host_constants(bn) for _, bn in pairs]
     parts = []
@@ -411,8 +435,7 @@ class HipUNet2HeadsTrainable(nn.Module):
         buffers = list(self.net.buffers())
         stamp = (device,) + tuple((t.data_ptr(), t._version) for t in buffers)
         if self._stamp != stamp:
-            pairs = [p.double_conv[i + 1] for p in _conv_pairs(self.net) for i in (0, 3)]
-            self._constants = [tuple(t.to(device) for t in _bn_host_constants(bn)) for bn in pairs]
+            self._constants = [tuple(t.to(device) for t in _bn_host_constants(bn)) for _, bn in _conv_bn_pairs(self.net)]
             self._stamp = stamp
         return self._constants
 
@@ -422,10 +445,8 @@ class HipUNet2HeadsTrainable(nn.Module):
         parameter is a contiguous float32 tensor there, pack_event_net_differentiable's torch operations otherwise."""
         from . import functional as EF
         consts = self._bn_constants(device)
-        pairs = [(p.double_conv[i], p.double_conv[i + 1]) for p in _conv_pairs(self.net) for i in (0, 3)]
-        params = [t for conv, bn in pairs for t in (conv.weight, bn.weight, bn.bias)]
-        params += [self.net.outc_1.conv.weight, self.net.outc_2.conv.weight, self.net.outc_1.conv.bias, self.net.outc_2.conv.bias]
-        fused = device.type == 'cuda' and all(conv.bias is None for conv, _ in pairs) and all(
+        params = _param_list(self.net)
+        fused = device.type == 'cuda' and all(conv.bias is None for conv, _ in _conv_bn_pairs(self.net)) and all(
             t.device == device and t.dtype is torch.float32 and t.is_contiguous() for t in params)
         if not fused:
             return pack_event_net_differentiable(self.net, device, consts)
@@ -439,21 +460,13 @@ class HipUNet2HeadsTrainable(nn.Module):
             if 'net' not in self._plain:
                 self._plain['net'] = HipUNet2Heads(self.net)
             return self._plain['net'](x)
-        if not x.is_cuda:
-            raise NotImplementedError(f"the HIP event network needs its input on a HIP device (got {x.device}); use the torch "
-                                      "module on the CPU")
-        if x.dim() != 4 or x.shape[0] != 1:
-            raise NotImplementedError(f"the HIP event network runs batch 1 only (got an input of shape {tuple(x.shape)})")
-        if x.shape[1] != 6 or x.shape[2] < 16 or x.shape[3] < 16:
-            raise NotImplementedError(f"the HIP event network takes [1,6,H,W] with H, W >= 16 (got {tuple(x.shape)})")
+        _check_input(x)
         if EF._capturing():
             raise RuntimeError("the trainable HIP event network does not support graph capture of a training step; capture "
                                "the frozen route (compile_event_net) instead")
         key = (int(x.shape[2]), int(x.shape[3]), x.device)
-        ws = self._workspaces.get(key)
-        if ws is None:
-            ws = self._workspaces[key] = (EF.EventNetWorkspace(key[0], key[1], x.device),
-                                          EF.EventNetTrainScratch(key[0], key[1], x.device))
+        ws = _cached(self._workspaces, key, lambda: (EF.EventNetWorkspace(key[0], key[1], x.device),
+                                                     EF.EventNetTrainScratch(key[0], key[1], x.device)))
         convs_hot = any(not n.startswith('outc_') for n in hot)
         return EF.eventnet_train_apply(x, self.packed(x.device), ws[0], ws[1], convs_hot)
 
@@ -476,7 +489,7 @@ def check_event_net_batchnorm(net):
     """Raise NotImplementedError unless `net` is what the training-mode device route implements: UNet_2heads(6, 2, 2),
     bilinear, the reference's widths, every BatchNorm affine with tracked running statistics and one momentum and eps."""
     check_event_net(net, frozen=False, eval_only=False)
-    bns = [p.double_conv[i] for p in _conv_pairs(net) for i in (1, 4)]
+    bns = [bn for _, bn in _conv_bn_pairs(net)]
     if any(not bn.affine for bn in bns):
         raise NotImplementedError("the training-mode HIP event network implements affine=True BatchNorm only")
     if any(not bn.track_running_stats or bn.running_mean is None for bn in bns):
@@ -504,19 +517,13 @@ class HipUNet2HeadsBatchNorm(nn.Module):
         self._workspaces = {}
 
     def _params(self):
-        pairs = [(p.double_conv[i], p.double_conv[i + 1]) for p in _conv_pairs(self.net) for i in (0, 3)]
-        params = [t for conv, bn in pairs for t in (conv.weight, bn.weight, bn.bias)]
-        params += [self.net.outc_1.conv.weight, self.net.outc_2.conv.weight, self.net.outc_1.conv.bias, self.net.outc_2.conv.bias]
-        return params, [bn for _, bn in pairs]
+        return _param_list(self.net), [bn for _, bn in _conv_bn_pairs(self.net)]
 
     def workspace(self, B, H, W, device):
         """The EventNetBnWorkspace of this input size (allocated on first use and kept)."""
         from . import functional as EF
         key = (int(B), int(H), int(W), torch.device(device))
-        ws = self._workspaces.get(key)
-        if ws is None:
-            ws = self._workspaces[key] = EF.EventNetBnWorkspace(key[0], key[1], key[2], key[3])
-        return ws
+        return _cached(self._workspaces, key, lambda: EF.EventNetBnWorkspace(*key))
 
     def forward(self, x):
         from . import functional as EF
@@ -525,15 +532,8 @@ class HipUNet2HeadsBatchNorm(nn.Module):
                 self._eval['net'] = HipUNet2HeadsTrainable(self.net)
             return self._eval['net'](x)
         check_event_net_batchnorm(self.net)
-        if not x.is_cuda:
-            raise NotImplementedError(f"the HIP event network needs its input on a HIP device (got {x.device}); use the torch "
-                                      "module on the CPU")
-        if x.dim() != 4 or x.shape[1] != 6 or x.shape[2] < 16 or x.shape[3] < 16:
-            raise NotImplementedError(f"the HIP event network takes [B,6,H,W] with H, W >= 16 (got {tuple(x.shape)})")
+        _check_input(x, EVENTNET_MAX_BATCH)
         B, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
-        if B < 1 or B > EVENTNET_MAX_BATCH:
-            raise NotImplementedError(f"the training-mode HIP event network runs batches of 1 to {EVENTNET_MAX_BATCH} (got "
-                                      f"an input of shape {tuple(x.shape)})")
         if EF._capturing():
             raise NotImplementedError("the training-mode HIP event network does not support graph capture of a training step; "
                                       "capture the frozen route (compile_event_net) instead")
@@ -541,7 +541,7 @@ class HipUNet2HeadsBatchNorm(nn.Module):
             raise ValueError("Expected more than 1 value per channel when training, got input size "
                              f"torch.Size([{B}, 512, {H // 16}, {W // 16}])")
         params, bns = self._params()
-        if any(conv_bias is not None for conv_bias in (p.double_conv[i].bias for p in _conv_pairs(self.net) for i in (0, 3))):
+        if any(conv.bias is not None for conv, _ in _conv_bn_pairs(self.net)):
             raise NotImplementedError("the training-mode HIP event network implements bias-free convolutions only")
         if any(t.device != x.device or t.dtype is not torch.float32 or not t.is_contiguous() for t in params):
             raise NotImplementedError("the training-mode HIP event network needs contiguous float32 parameters on the input's "

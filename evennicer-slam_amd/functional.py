@@ -11,6 +11,7 @@ import weakref
 import torch
 
 from . import _lib as L
+from .event import EVENTNET_CONVS
 
 _KIND_OF_GRID = {'grid_coarse': 0, 'grid_middle': 1, 'grid_fine': 2, 'grid_color': 3}
 
@@ -2718,7 +2719,7 @@ def eventnet_fold_pack(params, consts):
 
 
 # training-mode BatchNorm and batches (enslam_eventnet_bn_* / enslam_eventnet_train_*; event.compile_event_net_batchnorm)
-EVENTNET_BN_COUT = (64, 64, 128, 128, 256, 256, 512, 512, 512, 512) + (512, 256, 256, 128, 128, 64, 64, 64) * 2
+EVENTNET_BN_COUT = tuple(cout for _, cout in EVENTNET_CONVS)       # one BatchNorm per convolution, in packing order
 EVENTNET_BN_CHANNELS = sum(EVENTNET_BN_COUT)         # 5888: the length of the concatenated batch statistics
 EVENTNET_BN_ROWS = 256                               # rows per chunk of the BatchNorm kernels (BN_ROWS of csrc/event_net.hip)
 

@@ -202,6 +202,9 @@ def test_library_exports_and_launch_names():
     # host arithmetic only: sizes and refusals
     assert lib.enslam_eventnet_bn_workspace_floats(1, 16, 16) == 0 and lib.enslam_eventnet_bn_workspace_floats(9, 32, 32) == 0
     assert lib.enslam_eventnet_bn_workspace_floats(2, 16, 16) > 0
+    pinned = {(1, 32, 32): 65201792, (2, 16, 70): 67024128, (3, 16, 32): 65010304, (2, 39, 51): 70895808, (8, 180, 240): 730994048}
+    assert {bhw: lib.enslam_eventnet_bn_workspace_floats(*bhw) for bhw in pinned} == pinned
+    assert lib.enslam_eventnet_bn_saved_offset(2, 39, 51, 26) == -1
     offs = [lib.enslam_eventnet_bn_saved_offset(2, 39, 51, i) for i in range(26)]
     assert len(set(offs)) == 26 and min(offs) > 0 and max(offs) < lib.enslam_eventnet_bn_workspace_floats(2, 39, 51)
     assert sum(EF.EVENTNET_BN_COUT) == EF.EVENTNET_BN_CHANNELS == 5888

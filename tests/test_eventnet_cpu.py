@@ -78,6 +78,11 @@ def test_pack_matches_the_library_size_and_order():
     lib = E._lib.lib()
     assert lib.enslam_eventnet_workspace_floats(15, 64) == 0 and lib.enslam_eventnet_workspace_floats(64, 15) == 0
     assert lib.enslam_eventnet_workspace_floats(16, 16) > 0
+    # the sizes are part of the contract with allocated workspaces: pinned, region by region rounded to 64 floats
+    assert lib.enslam_eventnet_pack_floats() == 50224136
+    pinned = {(16, 16): 912896, (17, 19): 1121664, (16, 70): 2687936, (39, 51): 3915072, (180, 240): 57179520,
+              (480, 640): 390144000}
+    assert {hw: lib.enslam_eventnet_workspace_floats(*hw) for hw in pinned} == pinned
     assert lib.enslam_abi_version() == 1
 
 

@@ -130,6 +130,8 @@ def test_abi_declares_the_training_entries():
     lib = E._lib.lib()
     assert lib.enslam_eventnet_wgrad_scratch_floats(15, 16) == 0 and lib.enslam_eventnet_wgrad_scratch_floats(16, 15) == 0
     assert lib.enslam_eventnet_wgrad_scratch_floats(102, 180) > 0
+    pinned = {(16, 16): 590336, (17, 19): 885120, (16, 70): 1770240, (39, 51): 2360320, (180, 240): 2361344, (480, 640): 2361344}
+    assert {hw: lib.enslam_eventnet_wgrad_scratch_floats(*hw) for hw in pinned} == pinned
     from evennicer_slam_amd import functional as EF
     assert {'forward', 'backward', 'wgrad'} <= set(EF.eventnet_launches)
 
