@@ -361,6 +361,9 @@ _SIGS = {
                                               c_double, c_double, c_double, c_int32, POINTER(c_double), c_double, c_int32,
                                               c_int32, POINTER(c_double), c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_int32, c_void_p]),
+    "enslam_depth_forecast": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double,
+                                             POINTER(c_double), c_int32, c_int32, c_double, c_double, c_int32, c_void_p,
+                                             c_void_p, c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -56,13 +56,18 @@ struct EmArgs {
 
 __device__ __forceinline__ float em_luma(const float* p) { return (0.299f * p[0] + 0.587f * p[1]) + 0.114f * p[2]; }
 
+// torch.clamp(y, min=0) of the model's statement (event_model.luminance): a NaN stays a NaN (fmaxf would turn it into 0 and a
+// render that is not a number into a finite loss with a zero gradient)
+__device__ __forceinline__ float em_clamp0(float y) { return y < 0.f ? 0.f : y; }
+
 __device__ __forceinline__ float em_logdiff(const EmArgs& A, int64_t o, float& ycur_raw) {
     ycur_raw = em_luma(A.cur + 3 * o);
-    const float yc = fmaxf(ycur_raw, 0.f), yp = fmaxf(em_luma(A.prev + 3 * o), 0.f);
+    const float yc = em_clamp0(ycur_raw), yp = em_clamp0(em_luma(A.prev + 3 * o));
     return logf(yc + A.eps) - logf(yp + A.eps);
 }
 
 __device__ __forceinline__ float em_pred(const EmArgs& A, float d, int c) {
+    if (d != d) return d;                               // (a NaN is no side of the hinge: it goes through, as in torch.clamp)
     return c ? (d > 0.f ? d / A.c_pos : 0.f) : (d < 0.f ? -d / A.c_neg : 0.f);
 }
 
@@ -212,9 +217,12 @@ __global__ __launch_bounds__(EM_BLOCK) void event_model_tile_kernel(EmArgs A) {
     if (inside && (c == 1) == !(d < 0.f)) {
         float s = 0.f;
         if (yraw >= 0.f) {
-            const float den = fmaxf(yraw, 0.f) + A.eps;
+            const float den = yraw + A.eps;
             if (d > 0.f) s = g / (A.c_pos * den);
             else if (d < 0.f) s = -g / (A.c_neg * den);
+            else if (d != d) s = d;                     // (NaN from the previous frame's luminance)
+        } else if (yraw != yraw) {
+            s = yraw;                                   // a NaN colour has a NaN gradient: the failure reaches the pose
         }
         A.grad[3 * o + 0] = 0.299f * s;
         A.grad[3 * o + 1] = 0.587f * s;

@@ -3545,3 +3545,109 @@ def event_cmax_eval(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=F
                                            (ctypes.c_double * k)(*tp), _ptr(ws), ws.numel() * 8, _ptr(iwe), _ptr(blurred),
                                            _ptr(stats), _ptr(dropped), 1 if want_grad else 0, _stream()), "enslam_event_cmax_eval")
     return iwe, blurred, stats, dropped
+
+
+# ------------------------------------------------------------------------------------------------
+# depth forecast (csrc/depth_forecast.hip): a measured depth image warped into another pose and size (slam.py is the caller)
+# ------------------------------------------------------------------------------------------------
+def relative_camera_matrix(src_c2w, dst_c2w):
+    """The 3 x 4 float64 numpy matrix M = (dst_c2w^-1 src_c2w)[:3] that takes source-camera coordinates to target-camera
+    coordinates, computed on the host in float64 (c2w: [3,4] or [4,4], tensor or array, any device)."""
+    import numpy as np
+
+    def full(c):
+        c = np.asarray(c.detach().cpu().double().numpy() if torch.is_tensor(c) else c, dtype=np.float64)
+        m = np.eye(4)
+        m[:3] = c[:3]
+        return m
+    return np.ascontiguousarray((np.linalg.inv(full(dst_c2w)) @ full(src_c2w))[:3])
+
+
+def _depth_forecast_numpy(depth, cam, m, Ho, Wo, radius, z_near, fill):
+    """The model of enslam_depth_forecast (enslam_hip.h) on a numpy float32 [H,W] image: the same float64 operations in the
+    same order on whole arrays, the z-buffer by numpy.minimum.at on the bit patterns.  Returns float32 [Ho,Wo]."""
+    import numpy as np
+    H, W = depth.shape
+    fx, fy, cx, cy = (np.float64(cam[k]) for k in ('fx', 'fy', 'cx', 'cy'))
+    sx = np.float64(W - 1) / np.float64(Wo - 1) if Wo > 1 else np.float64(1.0)
+    sy = np.float64(H - 1) / np.float64(Ho - 1) if Ho > 1 else np.float64(1.0)
+    votes = np.full(Ho * Wo, 0xFFFFFFFF, dtype=np.uint32)
+    with np.errstate(all='ignore'):
+        d = depth.astype(np.float64)
+        jj, ii = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing='ij')
+        ok = (d > 0.0) & np.isfinite(d)
+        d, jj, ii = d[ok], jj[ok], ii[ok]
+        px, py = (ii - cx) / fx, -(jj - cy) / fy
+        p0, p1, p2 = d * px, d * py, -d
+        q = [((m[r, 0] * p0 + m[r, 1] * p1) + m[r, 2] * p2) + m[r, 3] for r in range(3)]
+        z = -q[2]
+        zf = z.astype(np.float32)
+        ok = (z > z_near) & np.isfinite(zf)
+        q0, q1, z, zf = q[0][ok], q[1][ok], z[ok], zf[ok]
+        u, v = cx + fx * (q0 / z), cy - fy * (q1 / z)
+        fi, fj = np.floor(u / sx + 0.5), np.floor(v / sy + 0.5)
+        ok = (fi >= 0.0) & (fi <= Wo - 1) & (fj >= 0.0) & (fj <= Ho - 1)
+        ok &= (np.abs(u - fi * sx) <= radius) & (np.abs(v - fj * sy) <= radius)
+        np.minimum.at(votes, fj[ok].astype(np.int64) * Wo + fi[ok].astype(np.int64), zf[ok].view(np.uint32))
+    votes = votes.reshape(Ho, Wo)
+    none = votes == 0xFFFFFFFF
+    out = np.where(none, np.uint32(0), votes)
+    if fill:
+        pad = np.zeros((Ho + 2, Wo + 2), dtype=np.uint32)
+        pad[1:-1, 1:-1] = out                               # (no vote and outside the image: 0, below every voted value)
+        best = np.zeros((Ho, Wo), dtype=np.uint32)
+        for dj in range(3):
+            for di in range(3):
+                best = np.maximum(best, pad[dj:dj + Ho, di:di + Wo])
+        out = np.where(none, best, out)
+    return np.ascontiguousarray(out.astype(np.uint32)).view(np.float32)
+
+
+def depth_forecast(depth, cam, M, out_size, radius=1.0, z_near=0.0, fill=True):
+    """float32 [Ho,Wo]: the depth image `depth` (float32 [H,W], contiguous) of one camera warped into another camera and the
+    strided (Ho, Wo) pixel centres of `tracker.image_rays_from_camera_tensor` -- enslam_depth_forecast (enslam_hip.h states the
+    model in full).  cam: dict with fx, fy, cx, cy of the full-resolution image; M: the 3 x 4 (or 4 x 4) float64 matrix from
+    source-camera to target-camera coordinates (`relative_camera_matrix`), on the host; radius: how far, in full-resolution
+    pixels, a point may land from a target pixel's centre and still vote for it; z_near: points at or nearer are dropped;
+    fill: an empty pixel takes the largest value among its 8 neighbours (one round).  0 where nothing is known.  A tensor on a
+    HIP device runs csrc/depth_forecast.hip (no synchronisation), a CPU tensor the numpy route of the same model: the two
+    return the same bits."""
+    import math
+    import numpy as np
+    what = "depth_forecast"
+    if not torch.is_tensor(depth) or depth.dtype is not torch.float32 or depth.dim() != 2:
+        raise L.EnslamError(f"{what}: depth must be a float32 [H,W] tensor (got "
+                            f"{getattr(depth, 'dtype', type(depth))} {tuple(getattr(depth, 'shape', ()))})")
+    if not depth.is_contiguous():
+        raise L.EnslamError(f"{what}: depth must be contiguous")
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    Ho, Wo = int(out_size[0]), int(out_size[1])
+    if H < 1 or W < 1 or Ho < 1 or Wo < 1:
+        raise L.EnslamError(f"{what}: image sizes must be at least 1 x 1 (got {H} x {W} -> {Ho} x {Wo})")
+    if (Wo > 1 and W == 1) or (Ho > 1 and H == 1):
+        raise L.EnslamError(f"{what}: an axis of one source pixel cannot be spread over several target pixels "
+                            f"(got {H} x {W} -> {Ho} x {Wo})")
+    if H * W > (1 << 30) or Ho * Wo > (1 << 30):
+        raise L.EnslamError(f"{what}: at most 2^30 source and target pixels")
+    m = np.asarray(M.detach().cpu().numpy() if torch.is_tensor(M) else M, dtype=np.float64)
+    if m.shape not in ((3, 4), (4, 4)):
+        raise L.EnslamError(f"{what}: M must be 3 x 4 or 4 x 4 (got shape {m.shape})")
+    m = np.ascontiguousarray(m[:3])
+    c = [float(cam[k]) for k in ('fx', 'fy', 'cx', 'cy')]
+    radius, z_near = float(radius), float(z_near)
+    if not all(math.isfinite(v) for v in c + [radius, z_near]) or not np.isfinite(m).all() or c[0] == 0.0 or c[1] == 0.0:
+        raise L.EnslamError(f"{what}: the intrinsics, M, radius and z_near must be finite, fx and fy not 0")
+    if radius < 0.0 or z_near < 0.0:
+        raise L.EnslamError(f"{what}: radius and z_near must not be negative (got {radius}, {z_near})")
+    if not depth.is_cuda:
+        out = _depth_forecast_numpy(depth.detach().numpy(), dict(fx=c[0], fy=c[1], cx=c[2], cy=c[3]), m, Ho, Wo, radius, z_near,
+                                    bool(fill))
+        return torch.from_numpy(out.copy())
+    dev = depth.device
+    with torch.cuda.device(dev):
+        out = torch.empty((Ho, Wo), dtype=torch.float32, device=dev)
+        ws = torch.empty(Ho * Wo, dtype=torch.int32, device=dev)
+        L.check(L.lib().enslam_depth_forecast(_ptr(depth), H, W, c[0], c[1], c[2], c[3], (ctypes.c_double * 12)(*m.reshape(-1)),
+                                              Ho, Wo, radius, z_near, 1 if fill else 0, _ptr(ws), _ptr(out), _stream()),
+                "enslam_depth_forecast")
+    return out

@@ -23,6 +23,17 @@ the checkpoints are not in the image): decoders and grids are fitted jointly to 
 sequence, the decoders are kept, the grids are re-initialised -- the run itself then optimises grids (and the colour decoder)
 only, as the reference does.
 
+THE SPARSE RGB-D SCHEDULE.  `event.schedule` picks what the tracker is handed per frame; `frame_plan` is the one place that
+decides it.  'dense' (the default): RGB-D term and the frame's own event image on every frame, the previous frame's colour as
+the event term's first image, the candidate with the smallest summed loss.  'reference': src/Tracker.py:350-375,439-442,461-466
+as written -- the RGB-D term only where idx % event.rgbd_every_frame == 0, the event term on every frame against the events
+summed since the last frame with idx % mapping.every_frame == 0, that frame's colour as the first image, the candidate with
+the smallest EVENT loss.  `event.depth_on_event_frames` says what guides the reduced-resolution render of a frame without
+RGB-D: 'measured' (the reference: that frame's depth image, which a sensor that delivers RGB-D every k-th frame does not have),
+'forecast' (the last measured depth image warped into the frame's initial pose, functional.depth_forecast) or 'none'.  With
+'forecast' and 'none' the colour and depth images of a frame without RGB-D are dropped as soon as the dataset has handed them
+over: tracker, mapper, keyframes and figures never see them.
+
 Mesh extraction is opt-in: `SLAM.get_mesh` (or `run(mesh_file=...)`) runs `mesher.Mesher.get_mesh` on the run's keyframes and
 poses.  The per-iteration figures of the reference's Visualizer are opt-in too: `SLAM(vis=True)` builds one
 `frame_vis.Visualizer` for the tracker (`tracking.vis_freq` / `vis_inside_freq`, folder `tracking_vis`) and one for the mapper
@@ -31,6 +42,7 @@ Mapper.py:705-713 do; `mapping.no_vis_on_first_frame` is honoured (absent: False
 import os
 import time
 import types
+import typing
 
 import numpy as np
 import torch
@@ -42,9 +54,45 @@ from .eval_ate import Logger, evaluate_checkpoint
 from .mapper import FusedAdam, MapperIteration, keyframe_selection_overlap
 from .renderer import Renderer
 from .scene import GRID_KEYS, grid_init, scene_bound
-from .tracker import TrackerIteration
+from .tracker import CameraParameter, TrackerIteration, camera_learning_rates
 
 MAP_KEYS = ('grid_middle', 'grid_fine', 'grid_color')
+SCHEDULES = ('dense', 'reference')
+DEPTH_ON_EVENT_FRAMES = ('measured', 'forecast', 'none')
+
+
+class FrameStep(typing.NamedTuple):
+    rgbd: bool              # the tracker's RGB-D term runs on this frame
+    anchor: typing.Optional[int]    # the frame whose colour is pre_gt_color (None: the frame is not tracked)
+    integrate: tuple        # the frames whose event images are summed into the event image the tracker gets
+    map: bool               # the frame is mapped (the harness drops the extra round on a last frame it may not read)
+    reset: bool             # the integration restarts after this frame
+
+
+def frame_plan(n, every_frame, rgbd_every_frame=1, schedule='dense'):
+    """What the harness does on each of n frames: a list of FrameStep.  Pure host function.
+    'dense': RGB-D on every frame, the frame's own events, the previous frame's colour; rgbd_every_frame is ignored.
+    'reference' (src/Tracker.py): rgbd = (idx % rgbd_every_frame == 0) (:357); the events of every tracked frame join the sum
+    before its iterations (:351); after a frame with idx % every_frame == 0 that frame's colour becomes pre_gt_color and the sum
+    restarts (:462-466).  Frame 0 is not tracked.  Mapped in both: frame 0, every every_frame-th frame and the last one."""
+    if schedule not in SCHEDULES:
+        raise ValueError(f"event.schedule must be one of {SCHEDULES} (got {schedule!r})")
+    n, every_frame, rgbd_every_frame = int(n), int(every_frame), int(rgbd_every_frame)
+    if every_frame < 1 or rgbd_every_frame < 1:
+        raise ValueError(f"mapping.every_frame and event.rgbd_every_frame must be at least 1 (got {every_frame}, {rgbd_every_frame})")
+    plan, anchor, since = [], None, []
+    for idx in range(n):
+        mapped = idx == 0 or idx % every_frame == 0 or idx == n - 1
+        if schedule == 'dense':
+            plan.append(FrameStep(True, idx - 1 if idx > 0 else None, (idx,) if idx > 0 else (), mapped, True))
+            continue
+        if idx > 0:
+            since.append(idx)
+        restart = idx % every_frame == 0
+        plan.append(FrameStep(idx % rgbd_every_frame == 0, anchor if idx > 0 else None, tuple(since), mapped, restart))
+        if restart:
+            anchor, since = idx, []
+    return plan
 
 
 def frustum_mask(c2w, depth, shape, bound, cam):
@@ -79,10 +127,33 @@ def frustum_mask(c2w, depth, shape, bound, cam):
     return (mask | near).reshape(W_, H_, D_).permute(2, 1, 0).contiguous()
 
 
+def schedule_settings(cfg):
+    """(event.schedule, event.rgbd_every_frame, event.depth_on_event_frames) of a configuration, defaults ('dense', 1, 'measured');
+    ValueError for an unknown value and for a sparse schedule whose mapper would need images that frames without RGB-D lack."""
+    e = cfg.get('event') or {}
+    schedule = e.get('schedule', 'dense')
+    rgbd_every = int(e.get('rgbd_every_frame', 1))
+    depth_mode = e.get('depth_on_event_frames', 'measured')
+    if schedule not in SCHEDULES:
+        raise ValueError(f"event.schedule must be one of {SCHEDULES} (got {schedule!r})")
+    if depth_mode not in DEPTH_ON_EVENT_FRAMES:
+        raise ValueError(f"event.depth_on_event_frames must be one of {DEPTH_ON_EVENT_FRAMES} (got {depth_mode!r})")
+    if schedule == 'reference':
+        every = int(cfg['mapping']['every_frame'])
+        if rgbd_every < 1:
+            raise ValueError(f"event.rgbd_every_frame must be at least 1 (got {rgbd_every})")
+        if depth_mode != 'measured' and every % rgbd_every:
+            # the mapper needs the frame's images: without the measured ones it can only map frames that have RGB-D
+            raise ValueError(f"mapping.every_frame ({every}) must be a multiple of event.rgbd_every_frame ({rgbd_every}) with "
+                             f"event.depth_on_event_frames {depth_mode!r}: frames without RGB-D are not mapped")
+    return schedule, rgbd_every, depth_mode
+
+
 class SLAM:
     def __init__(self, cfg, dataset, output, device='cuda:0', event_net=None, verbose=False, static_shapes=False, vis=False,
                  experiment=None):
         self.cfg, self.dataset, self.output, self.device, self.verbose = cfg, dataset, output, device, verbose
+        self.schedule, self.rgbd_every, self.depth_mode = schedule_settings(cfg)      # (refuses before anything is built)
         self.static_shapes = static_shapes
         self.scale = cfg['scale']
         self.H, self.W = cfg['cam']['H'] - 2 * cfg['cam']['crop_edge'], cfg['cam']['W'] - 2 * cfg['cam']['crop_edge']
@@ -116,6 +187,12 @@ class SLAM:
         self.low_gpu_mem = False
         self.logger = Logger(cfg, None, self)
         self.tracker = TrackerIteration(cfg, None, self)
+        e = cfg.get('event') or {}
+        # radius (full-resolution pixels) and hole filling of the depth forecast (functional.depth_forecast)
+        self.forecast_radius = float(e.get('forecast_radius', 1.0))
+        self.forecast_fill = bool(e.get('forecast_fill', True))
+        self._last_rgbd = None                              # (frame index, its depth image) of the last frame with RGB-D
+        self._gtracks = {}                                  # captured camera iterations (_track_graphed)
         self.keyframe_dict, self.keyframe_list = [], []
         self.timing = dict(track=0.0, map=0.0)
         self.vis_tracker = self.vis_mapper = None
@@ -138,7 +215,11 @@ class SLAM:
             p.requires_grad_(False)
         self.tracker.c = {k: v.detach().clone() for k, v in self.shared_c.items()}
 
-    def track(self, idx, gt_color, gt_depth, gt_event, gt_mask, pre_gt_color):
+    def track(self, idx, gt_color, gt_depth, gt_event, gt_mask, pre_gt_color, rgbd=True, forecast=False, by_event=False):
+        """The camera iterations of frame idx.  As the dense schedule calls it (the defaults): RGB-D term on, the candidate with the
+        smallest summed loss.  The reference schedule passes the plan's `rgbd`, the integrated events as gt_event and by_event=True
+        (the candidate with the smallest event loss, Tracker.py:439-442); forecast=True guides the reduced-resolution render by
+        the last measured depth warped into the frame's initial pose (gt_depth is then None)."""
         t = getattr(self, '_track_cfg', None) or self.cfg['tracking']
         pre = self.estimate_c2w_list[idx - 1].to(self.device)
         if t.get('const_speed_assumption', True) and idx - 2 >= 0:         # Tracker.py:295-301
@@ -150,22 +231,38 @@ class SLAM:
         # (predictor 'model': the contrast-threshold model predicts the events, no network is needed)
         has_predictor = self.event_net is not None or self.cfg['event'].get('predictor', 'net') == 'model'
         use_event = has_predictor and self.cfg['event'].get('activate_events', False)
+        if not rgbd and not use_event:
+            # no RGB-D image and no event term: the frame has no loss, its pose stays the initialisation and nothing is launched
+            c2w = torch.eye(4, device=self.device)
+            c2w[:3] = est[:3].float()
+            return c2w
+        by_event = by_event and use_event
+        guide = self._forecast_depth(est) if (forecast and use_event) else None
+        extra = {} if guide is None else dict(guide_depth=guide)
+        rates = camera_learning_rates(t)
         if t.get('graphed', False) and int(t['iters']) > 0:
-            return self._track_graphed(idx, est, gt_color, gt_depth, gt_event, gt_mask, pre_gt_color, t, use_event)
-        camera_tensor = get_tensor_from_camera(est.detach()).to(self.device).requires_grad_(True)
-        opt = FusedAdam([camera_tensor], lr=t['lr'])
-        best, best_loss, first_loss = camera_tensor.detach().clone(), None, None
+            return self._track_graphed(idx, est, gt_color, gt_depth, gt_event, gt_mask, pre_gt_color, t, use_event, rgbd, guide,
+                                       by_event)
+        cam = CameraParameter(get_tensor_from_camera(est.detach()).to(self.device), rates)
+        opt = cam.opt
+        best, best_loss, first_loss = cam.value().clone(), None, None
         for it in range(t['iters']):
+            camera_tensor = cam.tensor()
             out = self.tracker.optimize_cam_in_batch(camera_tensor, est, gt_color, gt_depth, gt_event, gt_mask, t['pixels'], opt,
-                                                     idx, it, pre_gt_color, rgbd=True, event=use_event,
-                                                     scale_factor=self.cfg['event'].get('scale_factor', 0.1))
-            loss = out[0] + (out[1] if (use_event and out[1] is not None) else 0.0)
+                                                     idx, it, pre_gt_color, rgbd=rgbd, event=use_event,
+                                                     scale_factor=self.cfg['event'].get('scale_factor', 0.1), **extra)
+            if by_event:
+                loss = out[1]                                               # Tracker.py:439-442: "it is always available"
+            else:
+                loss = out[0] + (out[1] if (use_event and out[1] is not None) else 0.0)
             if it == 0:
                 first_loss = loss
-            if best_loss is None or loss < best_loss:                       # Tracker.py:321-330 (candidate with the least loss)
-                best_loss, best = loss, camera_tensor.detach().clone()
-            if self.vis_tracker is not None:
-                self._vis_camera_iteration(idx, it, gt_depth, gt_color, camera_tensor, out if use_event else None)
+            # (by_event: a loss that is not a number is taken, as the graphed route's device argmin takes it -- a poisoned input
+            # shows in the pose instead of leaving the initialisation in place)
+            if best_loss is None or loss < best_loss or (by_event and loss != loss):   # Tracker.py:321-330 (candidate with the least loss)
+                best_loss, best = loss, cam.value().clone()
+            if self.vis_tracker is not None and gt_color is not None and gt_depth is not None:
+                self._vis_camera_iteration(idx, it, gt_depth, gt_color, cam.value(), out if use_event else None)
         c2w = torch.eye(4, device=self.device)
         c2w[:3] = get_camera_from_tensor(best)
         if self.verbose:
@@ -173,6 +270,18 @@ class SLAM:
             print(f'frame {idx}: tracking loss {first_loss} -> {best_loss}; translation error init '
                   f'{float((est[:3, 3] - gt).norm()):.4f} -> {float((c2w[:3, 3] - gt).norm()):.4f} m', flush=True)
         return c2w
+
+    def _forecast_depth(self, est):
+        """Guidance depth of a frame without RGB-D at the event resolution: the depth image of the last frame that had one, at that
+        frame's final estimated pose (after its mapping round and BA), warped into the initial pose `est` of this frame
+        (functional.depth_forecast).  Once per frame, constant over its camera iterations."""
+        if self._last_rgbd is None:
+            raise RuntimeError("depth forecast: no frame with RGB-D yet")
+        src, depth = self._last_rgbd
+        M = EF.relative_camera_matrix(self.estimate_c2w_list[src], est)
+        size = self.tracker.event_size(self.cfg['event'].get('scale_factor', 0.1))
+        return EF.depth_forecast(depth.float().contiguous(), self.cam, M, size, radius=self.forecast_radius, z_near=0.0,
+                                 fill=self.forecast_fill)
 
     def _vis_camera_iteration(self, idx, it, gt_depth, gt_color, camera_tensor, out):
         """The tracker's figure of camera iteration `it` (Tracker.py:444-447): with the event term `out` is the tuple of
@@ -188,40 +297,42 @@ class SLAM:
         else:
             v.vis(idx, it, gt_depth, gt_color, camera_tensor.detach(), trk.c, trk.decoders)
 
-    def _track_graphed(self, idx, est, gt_color, gt_depth, gt_event, gt_mask, pre_gt_color, t, use_event):
-        """`track` with the camera iterations as replays of ONE hipGraph (tracker.GraphedCameraIteration, captured at the first tracked
-        frame and kept): per frame the initial pose goes into the captured camera tensor, the optimiser is reset, the images are
-        copied in (set_frame draws the frame's pixels ahead) and the map the mapper has just published is copied into the captured
-        tensors (refresh_map); the losses stay on the device and the least-loss candidate (Tracker.py:321-330) is picked by one
-        argmin behind the last iteration -- no host round trip per iteration."""
+    def _track_graphed(self, idx, est, gt_color, gt_depth, gt_event, gt_mask, pre_gt_color, t, use_event, rgbd=True, guide=None,
+                       by_event=False):
+        """`track` with the camera iterations as replays of a hipGraph (tracker.GraphedCameraIteration, captured at the first tracked
+        frame of its shape and kept): per frame the initial pose goes into the captured camera tensor, the optimiser is reset, the
+        images are copied in (set_frame draws the frame's pixels ahead) and the map the mapper has just published is copied into the
+        captured tensors (refresh_map); the losses stay on the device and the least-loss candidate (Tracker.py:321-330; by_event:
+        the least EVENT loss, :439-442) is picked by one argmin behind the last iteration -- no host round trip per iteration.
+        The sparse schedule alternates between two shapes, RGB-D + event and event only: one captured graph each, in
+        `self._gtracks` keyed by (iterations, pixels, event term, RGB-D term); nothing is captured again per frame."""
         from .tracker import GraphedCameraIteration
         iters, n = int(t['iters']), int(t['pixels'])
         sf = self.cfg['event'].get('scale_factor', 0.1)
-        g = getattr(self, '_gtrack', None)
+        rates = camera_learning_rates(t)
         init = get_tensor_from_camera(est.detach()).to(self.device).float()
-        if g is None or g['key'] != (iters, n, use_event):
-            ct = init.clone().requires_grad_(True)
-            opt = FusedAdam([ct], lr=t['lr'])
-            git = GraphedCameraIteration(self.tracker, ct, opt, gt_color, gt_depth, gt_event if use_event else None,
-                                         gt_mask if use_event else None, pre_gt_color if use_event else None, batch_size=n, rgbd=True,
-                                         event=use_event, scale_factor=sf, n_draws=iters)
-            g = self._gtrack = dict(key=(iters, n, use_event), ct=ct, opt=opt, git=git,
-                                    cams=torch.empty((iters, 7), dtype=torch.float32, device=self.device),
-                                    losses=torch.empty(iters, dtype=torch.float64, device=self.device))
-        ct, opt, git = g['ct'], g['opt'], g['git']
-        with torch.no_grad():
-            ct.copy_(init.reshape(ct.shape))
-        opt.reset()
-        opt.set_lr(t['lr'])
+        images = (gt_color if rgbd else None, gt_depth)                  # (the event-only shape never looks at the colour image)
+        events = (gt_event, gt_mask, pre_gt_color) if use_event else (None, None, None)
+        key = (iters, n, use_event, bool(rgbd))
+        g = self._gtracks.get(key)
+        if g is None or g['rates'] != rates:
+            cam = CameraParameter(init, rates)
+            git = GraphedCameraIteration(self.tracker, cam.tensor, cam.opt, images[0], images[1], *events, batch_size=n, rgbd=rgbd,
+                                         event=use_event, scale_factor=sf, n_draws=iters, guide=guide)
+            g = self._gtracks[key] = dict(key=key, cam=cam, rates=rates, git=git,
+                                          cams=torch.empty((iters, 7), dtype=torch.float32, device=self.device),
+                                          losses=torch.empty(iters, dtype=torch.float64, device=self.device))
+        cam, git = g['cam'], g['git']
+        cam.restart(init, rates)
         git.refresh_map()                                   # (update_para_from_mapping replaced the tracker's map objects)
-        git.set_frame(gt_color, gt_depth, gt_event if use_event else None, gt_mask if use_event else None,
-                      pre_gt_color if use_event else None)
+        git.set_frame(images[0], images[1], *events, guide=guide)
         for it in range(iters):
             l_rgbd, l_event, _l_mask = git.step()
-            g['losses'][it].copy_(l_rgbd + l_event if use_event else l_rgbd)
-            g['cams'][it].copy_(ct.detach().reshape(-1))         # the candidate of this loss: the pose AFTER the step (Tracker.py:321-330)
-            if self.vis_tracker is not None:                     # between two replays, never inside a capture: the captured camera tensor
-                self._vis_camera_iteration(idx, it, gt_depth, gt_color, ct.detach().reshape(-1), None)
+            g['losses'][it].copy_(l_event if by_event else (l_rgbd + l_event if use_event else l_rgbd))
+            g['cams'][it].copy_(cam.value().reshape(-1))         # the candidate of this loss: the pose AFTER the step (Tracker.py:321-330)
+            if self.vis_tracker is not None and gt_color is not None and gt_depth is not None:
+                # between two replays, never inside a capture: the captured camera tensor
+                self._vis_camera_iteration(idx, it, gt_depth, gt_color, cam.value().reshape(-1), None)
         k = torch.argmin(g['losses'])
         best = g['cams'][k]
         c2w = torch.eye(4, device=self.device)
@@ -342,27 +453,41 @@ class SLAM:
             t['iters'] = int(tracking_iters)
         self._track_cfg = t
         n = self.n_img if max_frames is None else min(max_frames, self.n_img)
-        pre_color = None
+        plan = frame_plan(n, m['every_frame'], self.rgbd_every, self.schedule)
+        dense = self.schedule == 'dense'
+        # with 'forecast' / 'none' a frame without RGB-D has no colour and no depth image: they are dropped right here
+        strict = not dense and self.depth_mode != 'measured'
+        pre_color, integrated = None, None
+        self._last_rgbd = None
         for idx in range(n):
+            step = plan[idx]
             item = self.dataset[idx]
             if len(item) == 6:
                 _, gt_color, gt_depth, gt_event, gt_mask, gt_c2w = item
             else:
                 (_, gt_color, gt_depth, gt_c2w), gt_event, gt_mask = item, None, None
+            if strict and not step.rgbd:
+                gt_color = gt_depth = None
             self.gt_c2w_list[idx] = gt_c2w.clone().cpu()
             t0 = time.perf_counter()
             if idx == 0 or t.get('gt_camera', False):
                 c2w = gt_c2w.clone()
-                if self.vis_tracker is not None and not m.get('no_vis_on_first_frame', False):           # Tracker.py:306-308
+                integrated = None                                                                        # Tracker.py:304-311
+                if self.vis_tracker is not None and not m.get('no_vis_on_first_frame', False) and gt_color is not None:   # Tracker.py:306-308
                     # (before the first mapping round the tracker holds no copy of the map yet: the shared one)
                     self.vis_tracker.vis(idx, 0, gt_depth, gt_color.float(), c2w.to(self.device), self.tracker.c or self.shared_c,
                                          self.tracker.decoders or self.shared_decoders)
-            else:
+            elif dense:
                 c2w = self.track(idx, gt_color.float(), gt_depth, gt_event, gt_mask, pre_color)
+            else:
+                if gt_event is not None:                                                                 # Tracker.py:350-351
+                    integrated = gt_event if integrated is None else integrated + gt_event
+                c2w = self.track(idx, None if gt_color is None else gt_color.float(), gt_depth, integrated, gt_mask, pre_color,
+                                 rgbd=step.rgbd, forecast=(self.depth_mode == 'forecast' and not step.rgbd), by_event=True)
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             self.timing['track'] += t1 - t0
-            if idx == 0 or idx % m['every_frame'] == 0 or idx == n - 1:
+            if step.map and gt_color is not None:             # (the extra round on the last frame needs that frame's images)
                 iters = m['iters_first'] if idx == 0 else m['iters']
                 c2w, loss = self.map(idx, gt_color, gt_depth, c2w, iters)
                 self.update_para_from_mapping()
@@ -375,7 +500,12 @@ class SLAM:
             torch.cuda.synchronize()
             self.timing['map'] += time.perf_counter() - t1
             self.estimate_c2w_list[idx] = c2w.detach().cpu()
-            pre_color = gt_color.float()
+            if dense:
+                pre_color = gt_color.float()
+            elif step.reset:                                                 # Tracker.py:461-466
+                pre_color, integrated = gt_color.float(), None
+            if not dense and step.rgbd and self.depth_mode == 'forecast':
+                self._last_rgbd = (idx, gt_depth)
         self.last_idx = n - 1
         ckpt = self.logger.log(n - 1, self.keyframe_dict, self.keyframe_list, selected_keyframes=None)
         out = dict(ckpt=ckpt, frames=n, fps=n / max(self.timing['track'] + self.timing['map'], 1e-9), timing=dict(self.timing))

@@ -126,6 +126,73 @@ def image_rays_from_camera_tensor(camera_tensor, H, W, new_H, new_W, fx, fy, cx,
     return rays_from_camera_tensor(camera_tensor, cols.repeat(new_H), rows.repeat_interleave(new_W), fx, fy, cx, cy)
 
 
+def camera_learning_rates(tracking_cfg, lr=None):
+    """(quaternion rate, translation rate) of the camera optimiser: with `tracking.seperate_LR` (the reference's spelling,
+    Tracker.py:325-342) the quaternion runs at 0.2 * lr and the translation at lr; absent or False both run at lr."""
+    lr = float(tracking_cfg['lr'] if lr is None else lr)
+    return (0.2 * lr, lr) if tracking_cfg.get('seperate_LR', False) else (lr, lr)
+
+
+class SeparateRateAdam(object):
+    """The reference's `Adam([{T, lr}, {quad, 0.2 lr}])` (Tracker.py:335-336) as two `mapper.FusedAdam`s behind the one interface
+    the camera iteration uses (zero_grad, step, reset, set_lr)."""
+
+    def __init__(self, quad, trans, rates):
+        from .mapper import FusedAdam
+        self.opts = (FusedAdam([quad], lr=rates[0]), FusedAdam([trans], lr=rates[1]))
+
+    def zero_grad(self):
+        for o in self.opts:
+            o.zero_grad()
+
+    def step(self):
+        for o in self.opts:
+            o.step()
+
+    def reset(self):
+        for o in self.opts:
+            o.reset()
+
+    def set_lr(self, rates):
+        for o, r in zip(self.opts, rates):
+            o.set_lr(r)
+
+
+class CameraParameter(object):
+    """The 7 numbers a frame's camera iterations optimise, with their optimiser.  One rate: one leaf tensor [7] and one FusedAdam
+    (what the harness always built).  `tracking.seperate_LR`: the quaternion and the translation are two leaves, `tensor()`
+    concatenates them anew for every iteration as Tracker.py:354-355 does, and each has its own rate."""
+
+    def __init__(self, init, rates):
+        from .mapper import FusedAdam
+        init = init.detach().float().reshape(-1)
+        self.separate = rates[0] != rates[1]
+        if self.separate:
+            self.parts = (init[:4].clone().requires_grad_(True), init[4:].clone().requires_grad_(True))
+            self.opt = SeparateRateAdam(self.parts[0], self.parts[1], rates)
+        else:
+            self.parts = (init.clone().requires_grad_(True),)
+            self.opt = FusedAdam([self.parts[0]], lr=rates[1])
+
+    def tensor(self):
+        return torch.cat(self.parts, 0) if self.separate else self.parts[0]
+
+    def value(self):
+        return torch.cat([p.detach() for p in self.parts], 0) if self.separate else self.parts[0].detach()
+
+    def restart(self, init, rates):
+        """A new frame: the initial pose into the same tensors, the optimiser back to its first step."""
+        init = init.detach().float().reshape(-1)
+        with torch.no_grad():
+            if self.separate:
+                self.parts[0].copy_(init[:4])
+                self.parts[1].copy_(init[4:])
+            else:
+                self.parts[0].copy_(init)
+        self.opt.reset()
+        self.opt.set_lr(rates if self.separate else rates[1])
+
+
 class TrackerIteration(object):
     """The camera-iteration half of the reference's `Tracker` (src/Tracker.py:23-245): same configuration keys, same
     `optimize_cam_in_batch` signature and return values; the frame loop, visualiser, logging and the mapper hand-shake
@@ -179,14 +246,26 @@ class TrackerIteration(object):
         out[1].zero_()
         return out
 
-    def _render_rescaled(self, camera_tensor, gt_depth, scale_factor):
-        """`renderer.render_img_rescale(c, decoders, get_camera_from_tensor(camera_tensor), ...)`'s colour image."""
+    def event_size(self, scale_factor):
+        """(rows, columns) of the reduced-resolution render of the event term."""
+        return int(self.H * scale_factor), int(self.W * scale_factor)
+
+    def _render_rescaled(self, camera_tensor, gt_depth, scale_factor, guide=None):
+        """`renderer.render_img_rescale(c, decoders, get_camera_from_tensor(camera_tensor), ...)`'s colour image.  guide: a
+        guidance depth that is already at the event resolution (float32 [new_H, new_W], 0 = no guidance for the ray; the depth
+        forecast of a frame without RGB-D): used as it is -- a bilinear resize would blend its holes into the depths beside
+        them -- and gt_depth is not looked at."""
         from .event import resize_bilinear
         H, W = self.H, self.W
-        new_H, new_W = int(H * scale_factor), int(W * scale_factor)
+        new_H, new_W = self.event_size(scale_factor)
         rays_o, rays_d = image_rays_from_camera_tensor(camera_tensor, H, W, new_H, new_W, self.fx, self.fy, self.cx, self.cy,
                                                        self.device)
-        gd = resize_bilinear(gt_depth[None].float(), (new_H, new_W)).reshape(-1) if gt_depth is not None else None
+        if guide is not None:
+            if tuple(guide.shape) != (new_H, new_W) or guide.dtype != torch.float32:
+                raise L.EnslamError(f"guide must be float32 [{new_H}, {new_W}] (got {guide.dtype} {tuple(guide.shape)})")
+            gd = guide.reshape(-1)
+        else:
+            gd = resize_bilinear(gt_depth[None].float(), (new_H, new_W)).reshape(-1) if gt_depth is not None else None
         _, _, color = self.renderer._render_chunks(self.c, self.decoders, rays_o, rays_d, self.device, 'color', gd)
         return color.reshape(new_H, new_W, 3)
 
@@ -292,11 +371,14 @@ class TrackerIteration(object):
         return loss
 
     def iteration_losses(self, camera_tensor, gt_color, gt_depth, frame, batch_size, rgbd=True, event=True,
-                         scale_factor=0.1, static_shapes=False):
+                         scale_factor=0.1, static_shapes=False, guide_depth=None):
         """Loss tensors of one camera iteration, nothing synchronised: dict with `total` (what is back-propagated;
         None when nothing is), `rgbd`, `event` (balanced), `mask`, `full_event`, `event_mask`, `gts_blurred`,
         `preds_blurred`, `terms`.  `frame` = prepare_event_frame(...) (needed when event).  With `predictor: 'model'` the
-        event image comes from the contrast-threshold model: `mask` and `event_mask` stay None and no event_net is needed."""
+        event image comes from the contrast-threshold model: `mask` and `event_mask` stay None and no event_net is needed.
+        rgbd=False is the event-only iteration of a frame without an RGB-D image: no pixel is drawn, nothing of the RGB-D term is
+        launched and gt_color is not looked at (it may be None); gt_depth then only guides the reduced-resolution render and may
+        be None as well (no guidance), or be replaced by `guide_depth` (see _render_rescaled)."""
         from . import event as EV
         out = dict(total=None, rgbd=None, event=None, mask=None, full_event=None, event_mask=None, gts_blurred=[],
                    preds_blurred=[], terms=[])
@@ -307,7 +389,10 @@ class TrackerIteration(object):
             gt_event, gt_mask, full_color_previous = frame
             if self.low_gpu_mem and not static_shapes:
                 torch.cuda.empty_cache()
-            full_color_current = self._render_rescaled(camera_tensor, gt_depth, scale_factor)      # :150
+            if guide_depth is None:                     # (the call as it always was)
+                full_color_current = self._render_rescaled(camera_tensor, gt_depth, scale_factor)  # :150
+            else:
+                full_color_current = self._render_rescaled(camera_tensor, gt_depth, scale_factor, guide=guide_depth)
             if not by_model:
                 out['full_event'], out['event_mask'] = EV.inference_event(
                     net=self.event_net, img1=full_color_previous, img2=full_color_current, device=self.device, scale_factor=1.0,
@@ -332,20 +417,23 @@ class TrackerIteration(object):
         return out
 
     def optimize_cam_in_batch(self, camera_tensor, pre_c2w, gt_color, gt_depth, gt_event, gt_mask, batch_size, optimizer,
-                              idx, iter, pre_gt_color, rgbd=True, event=True, scale_factor=0.1):
+                              idx, iter, pre_gt_color, rgbd=True, event=True, scale_factor=0.1, guide_depth=None):
         """One camera iteration (Tracker.py:104-245): sample pixels, render, RGB-D loss and/or event loss, backward,
         optimiser step.  Returns the reference's tuple:
         blur off: (loss_rgbd, loss_event, loss_mask, gt_event, full_event, gt_mask, P(event)[h,w]);
         blur on : (loss_rgbd, loss_event, loss_mask, gt_event, full_event, gts_blurred, preds_blurred, term_values,
                    gt_mask, P(event)[h,w]).  With `predictor: 'model'` loss_mask and P(event) are None (there is no mask
         head).  With `event=False` the event entries are None (the reference raises a
-        NameError on its undefined lists in that case when blur is on)."""
+        NameError on its undefined lists in that case when blur is on).  gt_event is the event image the term is held against:
+        the frame's own, or the sum since the last mapped frame (the nearest-neighbour resize of the sum is the reference's,
+        Tracker.py:129-137).  guide_depth: see iteration_losses."""
         optimizer.zero_grad()
         frame = None
         if event:
             frame = self.prepare_event_frame(gt_event, gt_mask, pre_gt_color, scale_factor)
             gt_event, gt_mask = frame[0], frame[1]
-        o = self.iteration_losses(camera_tensor, gt_color, gt_depth, frame, batch_size, rgbd, event, scale_factor)
+        extra = {} if guide_depth is None else dict(guide_depth=guide_depth)
+        o = self.iteration_losses(camera_tensor, gt_color, gt_depth, frame, batch_size, rgbd, event, scale_factor, **extra)
         if o['total'] is not None and o['total'].requires_grad:
             with EF.engine_on_calling_thread():
                 o['total'].backward()                                                               # :197-199,231-232
@@ -365,13 +453,21 @@ class GraphedCameraIteration(object):
     """The camera iterations of one frame as replays of ONE hipGraph (zero_grad -> losses -> backward -> optimiser
     step), using the static-shape formulation of `TrackerIteration.iteration_losses`.  `optimizer` must be capturable
     (`mapper.FusedAdam`).  Per frame: `set_frame(images...)` copies the images into the graph's input buffers and
-    prepares the event-resolution ground truth; per iteration: `step()` returns the (device) loss tensors."""
+    prepares the event-resolution ground truth; per iteration: `step()` returns the (device) loss tensors.
+    camera_tensor: the leaf tensor [7], or a callable that returns the camera tensor of one iteration (CameraParameter.tensor
+    with `tracking.seperate_LR`).  rgbd=False captures the event-only shape: gt_color may be None, gt_depth may be None (no
+    guidance) and `guide` (float32 at the event resolution, see TrackerIteration._render_rescaled) takes its place when given;
+    what is None at capture has no buffer and stays None in set_frame."""
 
     def __init__(self, trk, camera_tensor, optimizer, gt_color, gt_depth, gt_event=None, gt_mask=None, pre_gt_color=None,
-                 batch_size=200, rgbd=True, event=True, scale_factor=0.1, warmup=3, n_draws=None):
+                 batch_size=200, rgbd=True, event=True, scale_factor=0.1, warmup=3, n_draws=None, guide=None):
         from .graph import GraphedStep
-        self.trk, self.event, self.scale_factor = trk, event, scale_factor
-        self.gt_color, self.gt_depth = gt_color.clone(), gt_depth.clone()
+        self.trk, self.event, self.scale_factor, self.rgbd = trk, event, scale_factor, rgbd
+        if rgbd and (gt_color is None or gt_depth is None):
+            raise L.EnslamError("GraphedCameraIteration: the RGB-D term needs gt_color and gt_depth")
+        self.gt_color = None if gt_color is None else gt_color.clone()
+        self.gt_depth = None if gt_depth is None else gt_depth.clone()
+        self.guide = None if guide is None else guide.clone()
         self.frame = None
         if event:
             self.frame = tuple(t.clone() for t in trk.prepare_event_frame(gt_event, gt_mask, pre_gt_color, scale_factor))
@@ -383,8 +479,9 @@ class GraphedCameraIteration(object):
 
         def it():
             optimizer.zero_grad()
-            o = trk.iteration_losses(camera_tensor, self.gt_color, self.gt_depth, self.frame, batch_size, rgbd, event,
-                                     scale_factor, static_shapes=True)
+            ct = camera_tensor() if callable(camera_tensor) else camera_tensor
+            o = trk.iteration_losses(ct, self.gt_color, self.gt_depth, self.frame, batch_size, rgbd, event,
+                                     scale_factor, static_shapes=True, **({} if self.guide is None else dict(guide_depth=self.guide)))
             if 'one' not in self.__dict__:
                 self.one = torch.ones_like(o['total'])
             with EF.engine_on_calling_thread():
@@ -407,9 +504,13 @@ class GraphedCameraIteration(object):
         self._map_c = {k: trk.c[k] for k in ('grid_middle', 'grid_fine', 'grid_color')}
         self._map_decoders = trk.decoders
 
-    def set_frame(self, gt_color, gt_depth, gt_event=None, gt_mask=None, pre_gt_color=None):
-        self.gt_color.copy_(gt_color)
-        self.gt_depth.copy_(gt_depth)
+    def set_frame(self, gt_color, gt_depth, gt_event=None, gt_mask=None, pre_gt_color=None, guide=None):
+        for name, src in (('gt_color', gt_color), ('gt_depth', gt_depth), ('guide', guide)):
+            dst = getattr(self, name)
+            if (dst is None) != (src is None):
+                raise L.EnslamError(f"GraphedCameraIteration.set_frame: {name} must be given exactly when it was at capture")
+            if dst is not None:
+                dst.copy_(src)
         if self._draws is not None:
             self.trk.draw_ahead(self.n_draws, self._draws[0].shape[1], out=self._draws)      # fresh pixels for the new frame
         self._steps_since_draw = 0

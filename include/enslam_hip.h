@@ -1295,7 +1295,8 @@ int enslam_ssim(const float *x, const float *y, int32_t H, int32_t W, int32_t C,
  * k / 2 of a border also receives what was reflected onto it: in one dimension of length n, with C the zero-padded
  * correlation of the taps, (B^T v)[p] = C(p) + [1 <= p <= k/2] C(-p) + [n - 1 - k/2 <= p <= n - 2] C(2 (n - 1) - p));
  * d pred_+ / d cur_ch = [d > 0] w_ch / (c_pos (Y(cur) + eps)), d pred_- / d cur_ch = -[d < 0] w_ch / (c_neg (Y(cur) + eps)),
- * zero where the luminance of cur was clamped (below 0).
+ * zero where the luminance of cur was clamped (below 0).  The two max() are torch.clamp(min=0): a NaN goes through them, so a
+ * colour that is not a number gives a NaN prediction, a NaN loss and a NaN gradient at that pixel, never a finite loss.
  *
  * Outputs: pred float32 [h,w,2]; sums float64 [K + 2] = the raw term sum r^2, the K blurred terms sum (B_i r)^2, then the
  * loss; grad float32 [h,w,3] = dloss/dcur; and, both or neither, blur_gt and blur_pred float32 [K,h,w,2] = B_i gt, B_i pred.
@@ -1375,6 +1376,28 @@ int enslam_event_cmax_eval(const double *t, const uint16_t *x, const uint16_t *y
                            double t_ref, int32_t sign_votes, int32_t k, const double *taps_host, void *workspace,
                            int64_t workspace_bytes, int64_t *iwe, double *blurred, double *stats, uint64_t *dropped,
                            int32_t want_grad, void *stream);
+
+/* Depth forecast (csrc/depth_forecast.hip, functional.depth_forecast): a measured depth image forward-warped into another
+ * camera pose and image size by a z-buffered point splat -- the guidance depth of the tracker's reduced-resolution render on a
+ * frame without an RGB-D image (slam.py, event.depth_on_event_frames: 'forecast').
+ * depth float32 [H,W] (device); m_host 12 float64 on the HOST, row-major 3 x 4, source-camera to target-camera coordinates
+ * (cameras look down -z); depth_out float32 [Ho,Wo] (device); workspace 4 * Ho * Wo bytes (device, the vote image).
+ * Every operation is float64 in the order written, not contracted; (float)z is the only float32 rounding.
+ *   A source pixel (row j, column i) with d = depth[j,i] finite and > 0 is the point p = (d px, d py, -d), px = (i - cx) / fx,
+ *   py = -(j - cy) / fy.  q_r = ((M[4r] p_0 + M[4r+1] p_1) + M[4r+2] p_2) + M[4r+3], z = -q_2; kept iff z > z_near and (float)z
+ *   is finite.  u = cx + fx (q_0 / z), v = cy - fy (q_1 / z).  Target pixel (jo, io) stands for the full-resolution position
+ *   (jo sy, io sx), sx = (W - 1) / (Wo - 1), sy = (H - 1) / (Ho - 1) (1 for an axis of one target pixel).  io = floor(u / sx +
+ *   0.5), jo = floor(v / sy + 0.5); the point votes iff 0 <= io <= Wo - 1, 0 <= jo <= Ho - 1, |u - io sx| <= radius and
+ *   |v - jo sy| <= radius.  Votes combine by an unsigned integer minimum on the bits of (float)z: the same bits in every run.
+ *   A pixel without a vote is 0.0; with fill = 1 it takes the LARGEST voted value among its up to 8 neighbours of the voted
+ *   (unfilled) image, 0.0 when there is none.
+ * One memset and two launches on the stream, no host synchronisation; the input is only read.
+ * ENSLAM_EINVAL without a launch: a NULL or misaligned (4 bytes) pointer; H, W, Ho or Wo <= 0; Wo > 1 with W = 1 or Ho > 1
+ * with H = 1; a non-finite intrinsic, matrix entry, radius or z_near; fx or fy equal to 0; radius < 0; z_near < 0; fill not 0
+ * or 1.  ENSLAM_EUNSUPPORTED: more than 2^30 source or target pixels. */
+int enslam_depth_forecast(const float *depth, int32_t H, int32_t W, double fx, double fy, double cx, double cy,
+                          const double *m_host, int32_t Ho, int32_t Wo, double radius, double z_near, int32_t fill,
+                          void *workspace, float *depth_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,8 @@
     python tools/run_slam.py CONFIG [--default-config PATH] [--input_folder DIR] [--event_folder DIR] [--output DIR]
                                     [--max-frames N] [--prepare host|device] [--prefit ITERS] [--device cuda:0]
                                     [--event-net PATH] [--net-backend hip|torch] [--event-predictor net|model] [--vis]
+                                    [--schedule dense|reference] [--rgbd-every K]
+                                    [--depth-on-event-frames measured|forecast|none]
 
 CONFIG may name parents with `inherit_from` (config.load_config); --default-config is the root under a chain that names
 none (the reference passes configs/nice_slam.yaml).  The reference's YAML files are not part of this repository: point at
@@ -12,7 +14,10 @@ pretrained decoders); --event-net loads a state_dict (tools/train_event_net.py, 
 eval-mode UNet_2heads(6, 2, 2) and hands it to the harness as its event network, --net-backend picks `event.net_backend`
 for it (hip: event.compile_event_net); without --event-net the harness runs without one, as before; --event-predictor
 model sets `event.predictor`: the event term from the contrast-threshold model (event_model.py; thresholds `event.c_pos`,
-`event.c_neg`, `event.eps` of the configuration), which needs no network.  Prints one JSON line: checkpoint path, frames, frames per second and the ATE."""
+`event.c_neg`, `event.eps` of the configuration), which needs no network.  --schedule, --rgbd-every and
+--depth-on-event-frames override `event.schedule`, `event.rgbd_every_frame` and `event.depth_on_event_frames` (slam.py: 'dense' --
+the default, also for a configuration that sets rgbd_every_frame -- runs RGB-D on every frame; 'reference' is the reference
+tracker's sparse schedule).  Prints one JSON line: checkpoint path, frames, frames per second and the ATE."""
 import argparse
 import copy
 import json
@@ -36,6 +41,22 @@ def slam_camera(cfg):
     return out
 
 
+def add_schedule_arguments(ap):
+    ap.add_argument('--schedule', choices=('dense', 'reference'), default=None)
+    ap.add_argument('--rgbd-every', type=int, default=None)
+    ap.add_argument('--depth-on-event-frames', choices=('measured', 'forecast', 'none'), default=None)
+
+
+def apply_schedule_arguments(cfg, args):
+    """--schedule, --rgbd-every and --depth-on-event-frames over cfg['event']."""
+    ev = cfg.setdefault('event', {})
+    for key, value in (('schedule', args.schedule), ('rgbd_every_frame', args.rgbd_every),
+                       ('depth_on_event_frames', args.depth_on_event_frames)):
+        if value is not None:
+            ev[key] = value
+    return cfg
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('config')
@@ -51,6 +72,7 @@ def main(argv=None):
     ap.add_argument('--net-backend', choices=('hip', 'torch'), default=None)
     ap.add_argument('--event-predictor', choices=('net', 'model'), default=None)
     ap.add_argument('--vis', action='store_true')
+    add_schedule_arguments(ap)
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -64,6 +86,7 @@ def main(argv=None):
         cfg.setdefault('data', {})['prepare'] = args.prepare
     if args.event_predictor is not None:
         cfg.setdefault('event', {})['predictor'] = args.event_predictor
+    apply_schedule_arguments(cfg, args)
     output = args.output or cfg.get('data', {}).get('output') or 'output'
     ds = D.get_dataset(cfg, types.SimpleNamespace(input_folder=args.input_folder, event_folder=args.event_folder), cfg['scale'],
                        device=args.device)

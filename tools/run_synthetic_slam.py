@@ -15,7 +15,9 @@ sets event.predictor ('model': the event term from the contrast-threshold model 
 figures (frame_vis.Visualizer: DIR/tracking_vis, DIR/mapping_vis; VIS_FREQ and VIS_INSIDE_FREQ, default 5 and 10, set both
 stages' vis_freq / vis_inside_freq); with --events simulate, [--refractory S] [--leak-rate HZ] [--shot-rate HZ] [--noise-seed N]
 switch the simulator to the noisy sensor (event_sim.EventNoise; the frame times are i / 30 s, those of
-tools/simulate_events.py's default --fps).  SEED (environment, default 0) seeds torch and numpy for each run."""
+tools/simulate_events.py's default --fps); [--schedule dense|reference] [--rgbd-every K] [--depth-on-event-frames
+measured|forecast|none] set event.schedule, event.rgbd_every_frame and event.depth_on_event_frames (slam.py; the sparse RGB-D
+schedule) and [--no-events] keeps event.activate_events off with simulated events (the "events off" arm).  SEED (environment, default 0) seeds torch and numpy for each run."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -29,6 +31,62 @@ DEV = 'cuda:0'
 
 
 from evennicer_slam_amd.synthetic import demo_config, write_demo_sequence
+
+
+def schedule_overrides(event_cfg, schedule=None, rgbd_every=None, depth_on_event_frames=None):
+    """event_cfg with --schedule, --rgbd-every and --depth-on-event-frames applied (None: left as it is)."""
+    out = dict(event_cfg)
+    if schedule is not None:
+        out['schedule'] = schedule
+    if rgbd_every is not None:
+        out['rgbd_every_frame'] = int(rgbd_every)
+    if depth_on_event_frames is not None:
+        out['depth_on_event_frames'] = depth_on_event_frames
+    return out
+
+
+def parse_args(args):
+    """(n_frames, keyword arguments of run) from the command line."""
+    args = list(args)
+    mesh_dir = None
+    if '--mesh' in args:
+        k = args.index('--mesh')
+        mesh_dir = args[k + 1]
+        del args[k:k + 2]
+    flags = {}
+    for flag, key in (('--overlap', 'overlap'), ('--tsdf', 'tsdf'), ('--no-events', 'no_events')):
+        flags[key] = flag in args
+        if flags[key]:
+            args.remove(flag)
+    opts = {}
+    for flag, key in (('--events', 'events'), ('--event-net', 'event_net'), ('--net-backend', 'net_backend'), ('--vis', 'vis'),
+                      ('--event-predictor', 'event_predictor'), ('--c-pos', 'c_pos'), ('--c-neg', 'c_neg'),
+                      ('--schedule', 'schedule'), ('--rgbd-every', 'rgbd_every'), ('--depth-on-event-frames', 'depth_on_event_frames')):
+        if flag in args:
+            k = args.index(flag)
+            opts[key] = args[k + 1]
+            del args[k:k + 2]
+    if opts.get('events') not in (None, 'simulate'):
+        raise SystemExit("--events takes 'simulate'")
+    if opts.get('event_predictor') not in (None, 'net', 'model'):
+        raise SystemExit("--event-predictor takes 'net' or 'model'")
+    if opts.get('schedule') not in (None, 'dense', 'reference'):
+        raise SystemExit("--schedule takes 'dense' or 'reference'")
+    if opts.get('depth_on_event_frames') not in (None, 'measured', 'forecast', 'none'):
+        raise SystemExit("--depth-on-event-frames takes 'measured', 'forecast' or 'none'")
+    if 'rgbd_every' in opts:
+        opts['rgbd_every'] = int(opts['rgbd_every'])
+    noise = {}
+    for flag, key, kind in (('--refractory', 'refractory', float), ('--leak-rate', 'leak_rate', float), ('--shot-rate', 'shot_rate', float),
+                            ('--noise-seed', 'seed', int)):
+        if flag in args:
+            k = args.index(flag)
+            noise[key] = kind(args[k + 1])
+            del args[k:k + 2]
+    if any(noise.get(k, 0) > 0 for k in ('refractory', 'leak_rate', 'shot_rate')):
+        from evennicer_slam_amd.event_sim import EventNoise
+        opts['noise'] = EventNoise(**noise)
+    return (int(args[0]) if args else 30), dict(mesh_dir=mesh_dir, **flags, **opts)
 
 
 def tsdf_metrics(slam, path, gt):
@@ -75,7 +133,8 @@ def mesh_metrics(slam, path, n_gt=200000, tsdf=False):
 
 
 def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=None, event_net=None, net_backend=None, vis=None,
-        noise=None, event_predictor=None, c_pos=None, c_neg=None):
+        noise=None, event_predictor=None, c_pos=None, c_neg=None, schedule=None, rgbd_every=None, depth_on_event_frames=None,
+        no_events=False):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -97,6 +156,9 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=Non
             c_sim = float(os.environ.get('EVENT_C', 0.2))
             cfg['event'] = dict(cfg['event'], predictor=event_predictor, c_pos=c_sim if c_pos is None else float(c_pos),
                                 c_neg=c_sim if c_neg is None else float(c_neg))
+        if no_events:
+            cfg['event'] = dict(cfg['event'], activate_events=False)
+        cfg['event'] = schedule_overrides(cfg['event'], schedule, rgbd_every, depth_on_event_frames)
         if event_net is not None:
             from evennicer_slam_amd.event import UNet_2heads
             net = UNet_2heads(6, 2, 2)
@@ -132,37 +194,5 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=Non
 
 
 if __name__ == '__main__':
-    args = sys.argv[1:]
-    mesh_dir = None
-    if '--mesh' in args:
-        k = args.index('--mesh')
-        mesh_dir = args[k + 1]
-        del args[k:k + 2]
-    overlap = '--overlap' in args
-    if overlap:
-        args.remove('--overlap')
-    tsdf = '--tsdf' in args
-    if tsdf:
-        args.remove('--tsdf')
-    opts = {}
-    for flag, key in (('--events', 'events'), ('--event-net', 'event_net'), ('--net-backend', 'net_backend'), ('--vis', 'vis'),
-                      ('--event-predictor', 'event_predictor'), ('--c-pos', 'c_pos'), ('--c-neg', 'c_neg')):
-        if flag in args:
-            k = args.index(flag)
-            opts[key] = args[k + 1]
-            del args[k:k + 2]
-    if opts.get('events') not in (None, 'simulate'):
-        raise SystemExit("--events takes 'simulate'")
-    if opts.get('event_predictor') not in (None, 'net', 'model'):
-        raise SystemExit("--event-predictor takes 'net' or 'model'")
-    noise = {}
-    for flag, key, kind in (('--refractory', 'refractory', float), ('--leak-rate', 'leak_rate', float), ('--shot-rate', 'shot_rate', float),
-                            ('--noise-seed', 'seed', int)):
-        if flag in args:
-            k = args.index(flag)
-            noise[key] = kind(args[k + 1])
-            del args[k:k + 2]
-    if any(noise.get(k, 0) > 0 for k in ('refractory', 'leak_rate', 'shot_rate')):
-        from evennicer_slam_amd.event_sim import EventNoise
-        opts['noise'] = EventNoise(**noise)
-    run(int(args[0]) if args else 30, mesh_dir=mesh_dir, overlap=overlap, tsdf=tsdf, **opts)
+    n_frames, kw = parse_args(sys.argv[1:])
+    run(n_frames, **kw)
