@@ -81,6 +81,51 @@ bool build_job(int kind, const enslam_mlp_params& P, bool with_transposed, PackJ
     return false;
 }
 
+bool is_decoder(int kind) { return is_xyz(kind) || kind == ENSLAM_MLP_COARSE; }
+
+// Append decoders 0..n-1 (host arrays) to a multi-decoder job, pack direction.  False: an array or a buffer is missing, or a
+// decoder lacks a parameter tensor.
+bool pack_decoders(PackJob& j, int n, const int32_t* kinds, const enslam_mlp_params* params, float* const* packed) {
+    if (n > 0 && (!kinds || !params || !packed)) return false;
+    for (int i = 0; i < n; ++i) {
+        if (!packed[i]) return false;
+        g_seg_dec = i;
+        j.packed[i] = packed[i];
+        const bool ok = build_job(kinds[i], params[i], true, j, true);
+        g_seg_dec = 0;
+        if (!ok) return false;
+    }
+    return true;
+}
+// The same in the unpack direction: NULL gradient tensors are skipped; partials[i] (optional) makes decoder i's gradient the sum
+// of its per-workgroup partial images.  False: an array or a buffer is missing, or a kind is unknown.
+bool unpack_decoders(PackJob& j, int n, const int32_t* kinds, const float* const* packed_grads, const float* const* partials,
+                     const enslam_mlp_params* grads) {
+    if (n > 0 && (!kinds || !packed_grads || !grads)) return false;
+    for (int i = 0; i < n; ++i) {
+        if (!packed_grads[i] || !is_decoder(kinds[i])) return false;
+        g_seg_dec = i;
+        j.packed[i] = const_cast<float*>(packed_grads[i]);
+        if (partials != nullptr && partials[i] != nullptr) {
+            j.part[i] = partials[i];
+            j.part_stride[i] = (int)enslam_packed_grad_floats(kinds[i]);
+        }
+        build_job(kinds[i], grads[i], false, j, true);
+        g_seg_dec = 0;
+    }
+    return true;
+}
+
+// Launchers return 0, -1 for a job they do not take (what that is to the caller differs by family: `refused`), or -2 for a
+// launch the runtime reported as failed.
+int launch_rc(int rc, int refused = ENSLAM_ELAUNCH) { return rc == 0 ? ENSLAM_OK : (rc == -1 ? refused : ENSLAM_ELAUNCH); }
+
+// optional work list arguments: both given or both NULL
+bool work_list_of(const int32_t* tiles, const int32_t* count, WorkList& w) {
+    w.tiles = const_cast<int32_t*>(tiles); w.count = const_cast<int32_t*>(count);
+    return (tiles == nullptr) == (count == nullptr);
+}
+
 bool to_dev_scene(const enslam_scene* s, DevScene& d) {
     if (s == nullptr) return false;
     for (int a = 0; a < 3; ++a) {
@@ -147,23 +192,15 @@ int enslam_pack_mlp_multi(int32_t n, const int32_t* kinds, const enslam_mlp_para
                           void* stream) {
     if (n < 0 || n > 3) return ENSLAM_EINVAL;
     if (n == 0) return ENSLAM_OK;
-    if (!kinds || !params || !packed) return ENSLAM_EINVAL;
     PackJob job;
     clear_job(job);
-    for (int i = 0; i < n; ++i) {
-        if (!packed[i]) return ENSLAM_EINVAL;
-        g_seg_dec = i;
-        job.packed[i] = packed[i];
-        const bool ok = build_job(kinds[i], params[i], true, job, true);
-        g_seg_dec = 0;
-        if (!ok) return ENSLAM_EINVAL;
-    }
+    if (!pack_decoders(job, n, kinds, params, packed)) return ENSLAM_EINVAL;
     return ens_launch_pack(job, nullptr, false, (hipStream_t)stream);
 }
 
 int enslam_unpack_mlp_grads(int kind, const float* packed_grad, const enslam_mlp_params* grads, void* stream) {
     if (grads == nullptr || packed_grad == nullptr) return ENSLAM_EINVAL;
-    if (!is_xyz(kind) && kind != ENSLAM_MLP_COARSE) return ENSLAM_EINVAL;
+    if (!is_decoder(kind)) return ENSLAM_EINVAL;
     PackJob job;
     build_job(kind, *grads, false, job);        // NULL outputs are simply skipped
     return ens_launch_pack(job, const_cast<float*>(packed_grad), true, (hipStream_t)stream);
@@ -173,16 +210,9 @@ int enslam_unpack_mlp_grads_multi(int32_t n, const int32_t* kinds, const float* 
                                   const enslam_mlp_params* grads, void* stream) {
     if (n < 0 || n > 4) return ENSLAM_EINVAL;
     if (n == 0) return ENSLAM_OK;
-    if (!kinds || !packed_grads || !grads) return ENSLAM_EINVAL;
     PackJob job;
     clear_job(job);
-    for (int i = 0; i < n; ++i) {
-        if (!packed_grads[i] || (!is_xyz(kinds[i]) && kinds[i] != ENSLAM_MLP_COARSE)) return ENSLAM_EINVAL;
-        g_seg_dec = i;
-        job.packed[i] = const_cast<float*>(packed_grads[i]);
-        build_job(kinds[i], grads[i], false, job, true);
-    }
-    g_seg_dec = 0;
+    if (!unpack_decoders(job, n, kinds, packed_grads, nullptr, grads)) return ENSLAM_EINVAL;
     return ens_launch_pack(job, nullptr, true, (hipStream_t)stream);
 }
 
@@ -207,9 +237,6 @@ bool make_conv_job(int32_t n, const float* const* src, float* const* dst, const 
     for (int i = n; i < 4; ++i) job.block_begin[i] = begin;
     return true;
 }
-}  // namespace
-
-namespace {
 void empty_conv_job(ConvJob& job) {
     job.n = 0;
     for (int i = 0; i < 4; ++i) { job.src[i] = nullptr; job.dst[i] = nullptr; job.V[i] = 0; job.need[i] = nullptr; job.valid[i] = nullptr; }
@@ -226,15 +253,7 @@ int enslam_step_prepare(int32_t n_dec, const int32_t* kinds, const enslam_mlp_pa
         return ENSLAM_EINVAL;
     PackJob pj;
     clear_job(pj);
-    if (n_dec > 0 && (!kinds || !params || !packed)) return ENSLAM_EINVAL;
-    for (int i = 0; i < n_dec; ++i) {
-        if (!packed[i]) return ENSLAM_EINVAL;
-        g_seg_dec = i;
-        pj.packed[i] = packed[i];
-        const bool ok = build_job(kinds[i], params[i], true, pj, true);
-        g_seg_dec = 0;
-        if (!ok) return ENSLAM_EINVAL;
-    }
+    if (!pack_decoders(pj, n_dec, kinds, params, packed)) return ENSLAM_EINVAL;
     ConvJob cj, zj;
     empty_conv_job(cj);
     empty_conv_job(zj);
@@ -245,34 +264,43 @@ int enslam_step_prepare(int32_t n_dec, const int32_t* kinds, const enslam_mlp_pa
         if (!make_conv_job(n_conv, src, dst, n_voxels, need, valid, true, cj)) return ENSLAM_EINVAL;
     }
     if (n_zero > 0 && !make_conv_job(n_zero, nullptr, zero_dst, zero_voxels, zero_need, nullptr, false, zj)) return ENSLAM_EINVAL;
-    return ens_launch_step(pj, false, cj, true, zj, flat, n_flat, nullptr, (hipStream_t)stream) == 0 ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    return launch_rc(ens_launch_step(pj, false, cj, true, zj, flat, n_flat, nullptr, (hipStream_t)stream));
 }
 
-// optional work list arguments: both given or both NULL
-static bool work_list_of(int32_t* tiles, int32_t* count, WorkList& w) {
-    w.tiles = tiles; w.count = count;
-    return (tiles == nullptr) == (count == nullptr);
-}
-static int step_finish_impl(int32_t n_conv, const float* const* src, float* const* dst, const int64_t* n_voxels,
-                            const uint8_t* const* need, int32_t n_dec, const int32_t* kinds, const float* const* packed_grads,
-                            const enslam_mlp_params* grads, const RayGradArgs* rg, void* stream, uint8_t* const* prev = nullptr,
-                            const float* const* partials = nullptr, uint8_t* mv_need = nullptr, uint8_t* mv_prev = nullptr,
-                            int64_t n_move = 0) {
+// The finish launch: the one body behind the five enslam_step_finish* entries, which fix the arguments they do not have (prev /
+// grad_partials / move_* NULL or 0; enslam_step_finish: no rays).  They differ in one rule only -- handoff_required: a NULL
+// dgrid_ws with rays is an error (the two narrow members) instead of "no ray role" (the two wide ones).
+// The order of the checks decides which code a call with several faults returns.
+static int step_finish_body(bool handoff_required, int32_t n_conv, const float* const* src, float* const* dst, const int64_t* n_voxels,
+                            const uint8_t* const* need, uint8_t* const* prev, int32_t n_dec, const int32_t* kinds,
+                            const float* const* packed_grads, const float* const* grad_partials, const enslam_mlp_params* grads,
+                            int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
+                            const double* z_vals, const enslam_scene* scene, float* dgrid_ws, float* g_rays_o, float* g_rays_d,
+                            const int32_t* work_list, const int32_t* work_count, uint8_t* move_need, uint8_t* move_prev,
+                            int64_t n_move, void* stream) {
+    if (n_rays < 0 || n_move < 0 || (n_move > 0 && (!move_need || !move_prev))) return ENSLAM_EINVAL;
+    if (prev != nullptr) {
+        if (!need || n_conv < 0 || n_conv > 4) return ENSLAM_EINVAL;
+        for (int i = 0; i < n_conv; ++i)
+            if (!need[i] || !prev[i]) return ENSLAM_EINVAL;
+    }
+    RayGradArgs rg;
+    const bool ray_role = n_rays > 0 && stage != ENSLAM_STAGE_COARSE && (handoff_required || dgrid_ws != nullptr);
+    if (ray_role) {
+        if (!samples_ok(n_samples)) return ENSLAM_EUNSUPPORTED;
+        DevScene d;
+        if (!to_dev_scene(scene, d) || !stage_ok(stage, d)) return ENSLAM_EINVAL;
+        if (!rays_o || !rays_d || !z_vals || !dgrid_ws || !g_rays_o || !g_rays_d) return ENSLAM_EINVAL;
+        WorkList wl;
+        if (!work_list_of(work_list, work_count, wl)) return ENSLAM_EINVAL;
+        if (!ens_ray_grad_args(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, d, dgrid_ws, g_rays_o, g_rays_d, rg,
+                               work_list ? &wl : nullptr))
+            return ENSLAM_EINVAL;
+    }
     if (n_dec < 0 || n_dec > 4 || n_conv < 0 || n_conv > 4) return ENSLAM_EINVAL;
     PackJob pj;
     clear_job(pj);
-    if (n_dec > 0 && (!kinds || !packed_grads || !grads)) return ENSLAM_EINVAL;
-    for (int i = 0; i < n_dec; ++i) {
-        if (!packed_grads[i] || (!is_xyz(kinds[i]) && kinds[i] != ENSLAM_MLP_COARSE)) return ENSLAM_EINVAL;
-        g_seg_dec = i;
-        pj.packed[i] = const_cast<float*>(packed_grads[i]);
-        if (partials != nullptr && partials[i] != nullptr) {
-            pj.part[i] = partials[i];
-            pj.part_stride[i] = (int)enslam_packed_grad_floats(kinds[i]);
-        }
-        build_job(kinds[i], grads[i], false, pj, true);
-    }
-    g_seg_dec = 0;
+    if (!unpack_decoders(pj, n_dec, kinds, packed_grads, grad_partials, grads)) return ENSLAM_EINVAL;
     ConvJob cj, zj;
     empty_conv_job(cj);
     empty_conv_job(zj);
@@ -280,15 +308,17 @@ static int step_finish_impl(int32_t n_conv, const float* const* src, float* cons
         if (!need) return ENSLAM_EINVAL;
         for (int i = 0; i < n_conv; ++i)
             if (!need[i]) return ENSLAM_EINVAL;
-        if (!make_conv_job(n_conv, src, dst, n_voxels, need, need ? prev : nullptr, true, cj)) return ENSLAM_EINVAL;
+        if (!make_conv_job(n_conv, src, dst, n_voxels, need, prev, true, cj)) return ENSLAM_EINVAL;
     }
-    if (n_move < 0 || (n_move > 0 && (!mv_need || !mv_prev))) return ENSLAM_EINVAL;
-    return ens_launch_step(pj, true, cj, false, zj, nullptr, 0, rg, (hipStream_t)stream, mv_need, mv_prev, n_move) == 0 ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    return launch_rc(ens_launch_step(pj, true, cj, false, zj, nullptr, 0, ray_role ? &rg : nullptr, (hipStream_t)stream, move_need,
+                                     move_prev, n_move));
 }
 int enslam_step_finish(int32_t n_conv, const float* const* src, float* const* dst, const int64_t* n_voxels,
                        const uint8_t* const* need, int32_t n_dec, const int32_t* kinds, const float* const* packed_grads,
                        const enslam_mlp_params* grads, void* stream) {
-    return step_finish_impl(n_conv, src, dst, n_voxels, need, n_dec, kinds, packed_grads, grads, nullptr, stream);
+    return step_finish_body(true, n_conv, src, dst, n_voxels, need, nullptr, n_dec, kinds, packed_grads, nullptr, grads,
+                            ENSLAM_STAGE_COARSE, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, 0, stream);
 }
 int enslam_step_finish_rays(int32_t n_conv, const float* const* src, float* const* dst, const int64_t* n_voxels,
                             const uint8_t* const* need, int32_t n_dec, const int32_t* kinds, const float* const* packed_grads,
@@ -296,20 +326,9 @@ int enslam_step_finish_rays(int32_t n_conv, const float* const* src, float* cons
                             const float* rays_o, const float* rays_d, const double* z_vals, const enslam_scene* scene,
                             float* dgrid_ws, float* g_rays_o, float* g_rays_d, const int32_t* work_list,
                             const int32_t* work_count, void* stream) {
-    if (n_rays < 0) return ENSLAM_EINVAL;
-    if (n_rays == 0 || stage == ENSLAM_STAGE_COARSE)
-        return step_finish_impl(n_conv, src, dst, n_voxels, need, n_dec, kinds, packed_grads, grads, nullptr, stream);
-    if (!samples_ok(n_samples)) return ENSLAM_EUNSUPPORTED;
-    DevScene d;
-    if (!to_dev_scene(scene, d) || !stage_ok(stage, d)) return ENSLAM_EINVAL;
-    if (!rays_o || !rays_d || !z_vals || !dgrid_ws || !g_rays_o || !g_rays_d) return ENSLAM_EINVAL;
-    RayGradArgs rg;
-    WorkList wl;
-    if (!work_list_of(const_cast<int32_t*>(work_list), const_cast<int32_t*>(work_count), wl)) return ENSLAM_EINVAL;
-    if (!ens_ray_grad_args(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, d, dgrid_ws, g_rays_o, g_rays_d, rg,
-                           work_list ? &wl : nullptr))
-        return ENSLAM_EINVAL;
-    return step_finish_impl(n_conv, src, dst, n_voxels, need, n_dec, kinds, packed_grads, grads, &rg, stream);
+    return step_finish_body(true, n_conv, src, dst, n_voxels, need, nullptr, n_dec, kinds, packed_grads, nullptr, grads, stage, n_rays,
+                            n_samples, rays_o, rays_d, z_vals, scene, dgrid_ws, g_rays_o, g_rays_d, work_list, work_count, nullptr,
+                            nullptr, 0, stream);
 }
 int enslam_step_finish_rays_prev(int32_t n_conv, const float* const* src, float* const* dst, const int64_t* n_voxels,
                                  const uint8_t* const* need, uint8_t* const* prev, int32_t n_dec, const int32_t* kinds,
@@ -317,54 +336,20 @@ int enslam_step_finish_rays_prev(int32_t n_conv, const float* const* src, float*
                                  int32_t n_samples, const float* rays_o, const float* rays_d, const double* z_vals,
                                  const enslam_scene* scene, float* dgrid_ws, float* g_rays_o, float* g_rays_d,
                                  const int32_t* work_list, const int32_t* work_count, void* stream) {
-    if (n_rays < 0) return ENSLAM_EINVAL;
-    if (prev != nullptr) {
-        if (!need || n_conv < 0 || n_conv > 4) return ENSLAM_EINVAL;
-        for (int i = 0; i < n_conv; ++i)
-            if (!need[i] || !prev[i]) return ENSLAM_EINVAL;
-    }
-    if (n_rays == 0 || stage == ENSLAM_STAGE_COARSE)
-        return step_finish_impl(n_conv, src, dst, n_voxels, need, n_dec, kinds, packed_grads, grads, nullptr, stream, prev);
-    if (!samples_ok(n_samples)) return ENSLAM_EUNSUPPORTED;
-    DevScene d;
-    if (!to_dev_scene(scene, d) || !stage_ok(stage, d)) return ENSLAM_EINVAL;
-    if (!rays_o || !rays_d || !z_vals || !dgrid_ws || !g_rays_o || !g_rays_d) return ENSLAM_EINVAL;
-    RayGradArgs rg;
-    WorkList wl;
-    if (!work_list_of(const_cast<int32_t*>(work_list), const_cast<int32_t*>(work_count), wl)) return ENSLAM_EINVAL;
-    if (!ens_ray_grad_args(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, d, dgrid_ws, g_rays_o, g_rays_d, rg,
-                           work_list ? &wl : nullptr))
-        return ENSLAM_EINVAL;
-    return step_finish_impl(n_conv, src, dst, n_voxels, need, n_dec, kinds, packed_grads, grads, &rg, stream, prev);
+    return step_finish_body(true, n_conv, src, dst, n_voxels, need, prev, n_dec, kinds, packed_grads, nullptr, grads, stage, n_rays,
+                            n_samples, rays_o, rays_d, z_vals, scene, dgrid_ws, g_rays_o, g_rays_d, work_list, work_count, nullptr,
+                            nullptr, 0, stream);
 }
-
 int enslam_step_finish_partials(int32_t n_conv, const float* const* src, float* const* dst, const int64_t* n_voxels,
                                 const uint8_t* const* need, uint8_t* const* prev, int32_t n_dec, const int32_t* kinds,
                                 const float* const* packed_grads, const float* const* grad_partials, const enslam_mlp_params* grads,
                                 int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
                                 const double* z_vals, const enslam_scene* scene, float* dgrid_ws, float* g_rays_o, float* g_rays_d,
                                 const int32_t* work_list, const int32_t* work_count, void* stream) {
-    if (n_rays < 0) return ENSLAM_EINVAL;
-    if (prev != nullptr) {
-        if (!need || n_conv < 0 || n_conv > 4) return ENSLAM_EINVAL;
-        for (int i = 0; i < n_conv; ++i)
-            if (!need[i] || !prev[i]) return ENSLAM_EINVAL;
-    }
-    if (n_rays == 0 || stage == ENSLAM_STAGE_COARSE || dgrid_ws == nullptr)
-        return step_finish_impl(n_conv, src, dst, n_voxels, need, n_dec, kinds, packed_grads, grads, nullptr, stream, prev, grad_partials);
-    if (!samples_ok(n_samples)) return ENSLAM_EUNSUPPORTED;
-    DevScene d;
-    if (!to_dev_scene(scene, d) || !stage_ok(stage, d)) return ENSLAM_EINVAL;
-    if (!rays_o || !rays_d || !z_vals || !g_rays_o || !g_rays_d) return ENSLAM_EINVAL;
-    RayGradArgs rg;
-    WorkList wl;
-    if (!work_list_of(const_cast<int32_t*>(work_list), const_cast<int32_t*>(work_count), wl)) return ENSLAM_EINVAL;
-    if (!ens_ray_grad_args(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, d, dgrid_ws, g_rays_o, g_rays_d, rg,
-                           work_list ? &wl : nullptr))
-        return ENSLAM_EINVAL;
-    return step_finish_impl(n_conv, src, dst, n_voxels, need, n_dec, kinds, packed_grads, grads, &rg, stream, prev, grad_partials);
+    return step_finish_body(false, n_conv, src, dst, n_voxels, need, prev, n_dec, kinds, packed_grads, grad_partials, grads, stage,
+                            n_rays, n_samples, rays_o, rays_d, z_vals, scene, dgrid_ws, g_rays_o, g_rays_d, work_list, work_count,
+                            nullptr, nullptr, 0, stream);
 }
-
 int enslam_step_finish_native(int32_t n_conv, const float* const* src, float* const* dst, const int64_t* n_voxels,
                               const uint8_t* const* need, uint8_t* const* prev, int32_t n_dec, const int32_t* kinds,
                               const float* const* packed_grads, const float* const* grad_partials, const enslam_mlp_params* grads,
@@ -372,27 +357,9 @@ int enslam_step_finish_native(int32_t n_conv, const float* const* src, float* co
                               const double* z_vals, const enslam_scene* scene, float* dgrid_ws, float* g_rays_o, float* g_rays_d,
                               const int32_t* work_list, const int32_t* work_count, uint8_t* move_need, uint8_t* move_prev,
                               int64_t n_move, void* stream) {
-    if (n_rays < 0 || n_move < 0 || (n_move > 0 && (!move_need || !move_prev))) return ENSLAM_EINVAL;
-    if (prev != nullptr) {
-        if (!need || n_conv < 0 || n_conv > 4) return ENSLAM_EINVAL;
-        for (int i = 0; i < n_conv; ++i)
-            if (!need[i] || !prev[i]) return ENSLAM_EINVAL;
-    }
-    if (n_rays == 0 || stage == ENSLAM_STAGE_COARSE || dgrid_ws == nullptr)
-        return step_finish_impl(n_conv, src, dst, n_voxels, need, n_dec, kinds, packed_grads, grads, nullptr, stream, prev, grad_partials,
-                                move_need, move_prev, n_move);
-    if (!samples_ok(n_samples)) return ENSLAM_EUNSUPPORTED;
-    DevScene d;
-    if (!to_dev_scene(scene, d) || !stage_ok(stage, d)) return ENSLAM_EINVAL;
-    if (!rays_o || !rays_d || !z_vals || !g_rays_o || !g_rays_d) return ENSLAM_EINVAL;
-    RayGradArgs rg;
-    WorkList wl;
-    if (!work_list_of(const_cast<int32_t*>(work_list), const_cast<int32_t*>(work_count), wl)) return ENSLAM_EINVAL;
-    if (!ens_ray_grad_args(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, d, dgrid_ws, g_rays_o, g_rays_d, rg,
-                           work_list ? &wl : nullptr))
-        return ENSLAM_EINVAL;
-    return step_finish_impl(n_conv, src, dst, n_voxels, need, n_dec, kinds, packed_grads, grads, &rg, stream, prev, grad_partials,
-                            move_need, move_prev, n_move);
+    return step_finish_body(false, n_conv, src, dst, n_voxels, need, prev, n_dec, kinds, packed_grads, grad_partials, grads, stage,
+                            n_rays, n_samples, rays_o, rays_d, z_vals, scene, dgrid_ws, g_rays_o, g_rays_d, work_list, work_count,
+                            move_need, move_prev, n_move, stream);
 }
 
 int enslam_grids_convert(int32_t n, const float* const* src, float* const* dst, const int64_t* n_voxels,
@@ -595,8 +562,8 @@ int enslam_mark_blocks_g(int32_t stage, int32_t n_rays, int32_t n_samples, const
     if (n_rays == 0) return ENSLAM_OK;
     DevScene d;
     if (!to_dev_scene(scene, d) || !rays_o || !rays_d || !z_vals || !flags) return ENSLAM_EINVAL;
-    const int rc = ens_launch_mark_blocks(stage, n_rays, n_samples, rays_o, rays_d, z_vals, d, flags, (hipStream_t)stream, block_voxels);
-    return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EINVAL : ENSLAM_ELAUNCH);
+    return launch_rc(ens_launch_mark_blocks(stage, n_rays, n_samples, rays_o, rays_d, z_vals, d, flags, (hipStream_t)stream, block_voxels),
+                     ENSLAM_EINVAL);
 }
 int enslam_bucket_pack_g(int32_t n_grids, const float* const* grid_grad, int32_t channels, const int64_t* n_voxels,
                          const int32_t* layout, const uint8_t* flags, const int32_t* pos, int32_t n_small,
@@ -635,27 +602,45 @@ int enslam_sample_rays(int32_t n_rays, int32_t n_lin, int32_t n_surf, const floa
     return enslam_sample_rays_g(n_rays, n_lin, n_surf, rays_o, rays_d, gt_depth, bound_host, t_lin, t_surf, lindisp, t_rand, scratch,
                                 depth_max_given, z_vals, mark_stage, mark_scene, mark_flags, 64, nullptr, stream);
 }
+// log2 of the voxels per flag the sampler's marking takes (64, 32, 16 or 8); -1 for any other size
+static int mark_shift(int32_t block_voxels) {
+    switch (block_voxels) { case 64: return 6; case 32: return 5; case 16: return 4; case 8: return 3; default: return -1; }
+}
+// The sampler's optional block marking: `mark` = &mk when mark_scene and mark_flags are both given, else NULL.
+// False: a block size, stage or scene the marking does not take.
+static bool mark_args(int32_t block_voxels, int32_t stage, const enslam_scene* scene, uint8_t* const* flags, uint8_t* const* flags64,
+                      MarkArgs& mk, const MarkArgs*& mark) {
+    const int shift = mark_shift(block_voxels);
+    if (shift < 0) return false;
+    mark = nullptr;
+    if (scene == nullptr || flags == nullptr) return true;
+    if (stage < 0 || stage > 3 || !to_dev_scene(scene, mk.sc)) return false;
+    mk.kmask = stage == 0 ? 1 : (stage == 1 ? 2 : (stage == 2 ? 6 : 14));
+    for (int k = 0; k < 4; ++k) { mk.flags[k] = flags[k]; mk.flags64[k] = (flags64 != nullptr && shift < 6) ? flags64[k] : nullptr; }
+    mk.shift = shift;
+    mark = &mk;
+    return true;
+}
+// the pointers a sampler call with rays needs
+static bool sample_ptrs_ok(const float* rays_o, const float* rays_d, const float* gt_depth, const double* bound_host, const float* t_lin,
+                           const double* t_surf, int32_t n_surf, const float* scratch, const double* z_vals) {
+    if (!rays_o || !rays_d || !bound_host || !t_lin || !z_vals) return false;
+    return gt_depth == nullptr || (scratch != nullptr && (n_surf == 0 || t_surf != nullptr));
+}
+
 int enslam_sample_rays_g(int32_t n_rays, int32_t n_lin, int32_t n_surf, const float* rays_o, const float* rays_d,
                          const float* gt_depth, const double* bound_host, const float* t_lin, const double* t_surf,
                          int32_t lindisp, const float* t_rand, float* scratch, int32_t depth_max_given, double* z_vals,
                          int32_t mark_stage, const enslam_scene* mark_scene, uint8_t* const* mark_flags,
                          int32_t mark_block_voxels, uint8_t* const* mark_flags64, void* stream) {
     if (n_rays < 0 || n_lin < 1 || n_surf < 0) return ENSLAM_EINVAL;
-    int shift = 6;
-    switch (mark_block_voxels) { case 64: shift = 6; break; case 32: shift = 5; break; case 16: shift = 4; break; case 8: shift = 3; break; default: return ENSLAM_EINVAL; }
-    if (n_rays == 0) return ENSLAM_OK;
-    if (!rays_o || !rays_d || !bound_host || !t_lin || !z_vals) return ENSLAM_EINVAL;
-    if (gt_depth != nullptr && (scratch == nullptr || (n_surf > 0 && t_surf == nullptr))) return ENSLAM_EINVAL;
+    if (n_rays == 0) return mark_shift(mark_block_voxels) < 0 ? ENSLAM_EINVAL : ENSLAM_OK;    // no pointer, no marking looked at
+    if (!sample_ptrs_ok(rays_o, rays_d, gt_depth, bound_host, t_lin, t_surf, n_surf, scratch, z_vals)) return ENSLAM_EINVAL;
     MarkArgs mk;
-    const bool marking = mark_scene != nullptr && mark_flags != nullptr;
-    if (marking) {
-        if (mark_stage < 0 || mark_stage > 3 || !to_dev_scene(mark_scene, mk.sc)) return ENSLAM_EINVAL;
-        mk.kmask = mark_stage == 0 ? 1 : (mark_stage == 1 ? 2 : (mark_stage == 2 ? 6 : 14));
-        for (int k = 0; k < 4; ++k) { mk.flags[k] = mark_flags[k]; mk.flags64[k] = (mark_flags64 != nullptr && shift < 6) ? mark_flags64[k] : nullptr; }
-        mk.shift = shift;
-    }
+    const MarkArgs* mark;
+    if (!mark_args(mark_block_voxels, mark_stage, mark_scene, mark_flags, mark_flags64, mk, mark)) return ENSLAM_EINVAL;
     return ens_launch_sample(n_rays, n_lin, n_surf, rays_o, rays_d, gt_depth, bound_host, t_lin, t_surf, lindisp,
-                             t_rand, scratch, depth_max_given, z_vals, marking ? &mk : nullptr, (hipStream_t)stream);
+                             t_rand, scratch, depth_max_given, z_vals, mark, (hipStream_t)stream);
 }
 
 int enslam_sample_prepare(int32_t n_rays, int32_t n_lin, int32_t n_surf, const float* rays_o, const float* rays_d,
@@ -668,102 +653,73 @@ int enslam_sample_prepare(int32_t n_rays, int32_t n_lin, int32_t n_surf, const f
                           float* flat, int64_t n_flat, void* stream) {
     if (n_rays < 0 || n_lin < 1 || n_surf < 0) return ENSLAM_EINVAL;
     if (n_dec < 0 || n_dec > 3 || n_zero < 0 || n_zero > 4 || n_flat < 0 || (n_flat > 0 && !flat)) return ENSLAM_EINVAL;
-    int shift = 6;
-    switch (mark_block_voxels) { case 64: shift = 6; break; case 32: shift = 5; break; case 16: shift = 4; break; case 8: shift = 3; break; default: return ENSLAM_EINVAL; }
-    if (n_rays > 0) {
-        if (!rays_o || !rays_d || !bound_host || !t_lin || !z_vals) return ENSLAM_EINVAL;
-        if (gt_depth != nullptr && (scratch == nullptr || (n_surf > 0 && t_surf == nullptr))) return ENSLAM_EINVAL;
-    } else if (!bound_host) {
+    // zero rays: the prepare roles run alone, and the launcher still reads the bound
+    if (n_rays > 0 ? !sample_ptrs_ok(rays_o, rays_d, gt_depth, bound_host, t_lin, t_surf, n_surf, scratch, z_vals) : !bound_host)
         return ENSLAM_EINVAL;
-    }
     MarkArgs mk;
-    const bool marking = mark_scene != nullptr && mark_flags != nullptr;
-    if (marking) {
-        if (mark_stage < 0 || mark_stage > 3 || !to_dev_scene(mark_scene, mk.sc)) return ENSLAM_EINVAL;
-        mk.kmask = mark_stage == 0 ? 1 : (mark_stage == 1 ? 2 : (mark_stage == 2 ? 6 : 14));
-        for (int k = 0; k < 4; ++k) { mk.flags[k] = mark_flags[k]; mk.flags64[k] = (mark_flags64 != nullptr && shift < 6) ? mark_flags64[k] : nullptr; }
-        mk.shift = shift;
-    }
+    const MarkArgs* mark;
+    if (!mark_args(mark_block_voxels, mark_stage, mark_scene, mark_flags, mark_flags64, mk, mark)) return ENSLAM_EINVAL;
     PackJob pj;
     clear_job(pj);
-    if (n_dec > 0 && (!kinds || !params || !packed)) return ENSLAM_EINVAL;
-    for (int i = 0; i < n_dec; ++i) {
-        if (!packed[i]) return ENSLAM_EINVAL;
-        g_seg_dec = i;
-        pj.packed[i] = packed[i];
-        const bool ok = build_job(kinds[i], params[i], true, pj, true);
-        g_seg_dec = 0;
-        if (!ok) return ENSLAM_EINVAL;
-    }
+    if (!pack_decoders(pj, n_dec, kinds, params, packed)) return ENSLAM_EINVAL;
     ConvJob zj;
     empty_conv_job(zj);
     if (n_zero > 0 && !make_conv_job(n_zero, nullptr, zero_dst, zero_voxels, zero_need, nullptr, false, zj)) return ENSLAM_EINVAL;
-    const int rc = ens_launch_sample_prepare(n_rays, n_lin, n_surf, rays_o, rays_d, gt_depth, bound_host, t_lin, t_surf, lindisp, t_rand,
-                                             scratch, depth_max_given, z_vals, marking ? &mk : nullptr, pj, zj, flat, n_flat,
-                                             (hipStream_t)stream);
-    return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EINVAL : ENSLAM_ELAUNCH);
+    return launch_rc(ens_launch_sample_prepare(n_rays, n_lin, n_surf, rays_o, rays_d, gt_depth, bound_host, t_lin, t_surf, lindisp, t_rand,
+                                               scratch, depth_max_given, z_vals, mark, pj, zj, flat, n_flat, (hipStream_t)stream),
+                     ENSLAM_EINVAL);
 }
 
-int enslam_render_fwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
-                      const double* z_vals, const enslam_scene* scene, double* depth, double* var, float* rgb,
-                      float* raw_out, float* act_ws, int32_t act_light, void* stream) {
+// The rendering forward: the one body behind enslam_render_fwd (ls, ts and the list NULL), enslam_render_loss_fwd (ls) and
+// enslam_render_tracker_loss_fwd (ls and ts).  raw_out is optional only without a loss; -1 from the launcher: a ray count
+// beyond the tile-mode limit, or 64 samples without raw_out.
+static int render_fwd_body(int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
+                           const double* z_vals, const enslam_scene* scene, double* depth, double* var, float* rgb, float* raw_out,
+                           float* act_ws, int32_t act_light, const LossSpec* ls, const TrackerSpec* ts, int32_t* work_list,
+                           int32_t* work_count, void* stream) {
     if (n_rays < 0) return ENSLAM_EINVAL;
     if (n_rays == 0) return ENSLAM_OK;
     if (!samples_ok(n_samples)) return ENSLAM_EUNSUPPORTED;
+    if (ts != nullptr && (n_rays > ENS_TRACKER_TAIL_MAX_RAYS || stage == ENSLAM_STAGE_COARSE)) return ENSLAM_EUNSUPPORTED;
     DevScene d;
     if (!to_dev_scene(scene, d) || !stage_ok(stage, d)) return ENSLAM_EINVAL;
     if (!rays_o || !rays_d || !z_vals || !depth || !var || !rgb) return ENSLAM_EINVAL;
+    if (ls != nullptr && (!raw_out || !ls->gd || !ls->loss)) return ENSLAM_EINVAL;
+    if (ts != nullptr && !ts->tmp) return ENSLAM_EINVAL;
     if (act_ws != nullptr)                               // the saved cell records hold the voxel index in 29 bits
         for (int k = 1; k < 4; ++k)
             if (d.grid[k].data && (int64_t)d.grid[k].D * d.grid[k].H * d.grid[k].W >= ACT_MAX_VOXELS) return ENSLAM_EUNSUPPORTED;
-    const int rc = ens_launch_render_fwd(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, nullptr, 0, 1, d, depth, var,
-                                         rgb, raw_out, stage == ENSLAM_STAGE_COARSE ? nullptr : act_ws, act_light != 0, (hipStream_t)stream);
-    return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EUNSUPPORTED : ENSLAM_ELAUNCH);     // (64 samples without raw_out)
+    WorkList wl;
+    if (!work_list_of(work_list, work_count, wl) || (work_list && !(ls && ls->d_raw_unit))) return ENSLAM_EINVAL;
+    return launch_rc(ens_launch_render_fwd(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, nullptr, 0, 1, d, depth, var, rgb,
+                                           raw_out, stage == ENSLAM_STAGE_COARSE ? nullptr : act_ws, act_light != 0,
+                                           (hipStream_t)stream, ls, work_list ? &wl : nullptr, ts),
+                     ENSLAM_EUNSUPPORTED);
 }
-
+int enslam_render_fwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
+                      const double* z_vals, const enslam_scene* scene, double* depth, double* var, float* rgb,
+                      float* raw_out, float* act_ws, int32_t act_light, void* stream) {
+    return render_fwd_body(stage, n_rays, n_samples, rays_o, rays_d, z_vals, scene, depth, var, rgb, raw_out, act_ws, act_light,
+                           nullptr, nullptr, nullptr, nullptr, stream);
+}
 int enslam_render_loss_fwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
                            const double* z_vals, const enslam_scene* scene, double* depth, double* var, float* rgb,
                            float* raw_out, float* act_ws, int32_t act_light, const float* gt_depth, const float* gt_color,
                            float w_color, double* loss, float* d_raw_unit, int32_t* work_list, int32_t* work_count,
                            void* stream) {
-    if (n_rays < 0) return ENSLAM_EINVAL;
-    if (n_rays == 0) return ENSLAM_OK;
-    if (!samples_ok(n_samples)) return ENSLAM_EUNSUPPORTED;
-    DevScene d;
-    if (!to_dev_scene(scene, d) || !stage_ok(stage, d)) return ENSLAM_EINVAL;
-    if (!rays_o || !rays_d || !z_vals || !depth || !var || !rgb || !raw_out || !gt_depth || !loss) return ENSLAM_EINVAL;
-    if (act_ws != nullptr)
-        for (int k = 1; k < 4; ++k)
-            if (d.grid[k].data && (int64_t)d.grid[k].D * d.grid[k].H * d.grid[k].W >= ACT_MAX_VOXELS) return ENSLAM_EUNSUPPORTED;
     const LossSpec ls{gt_depth, gt_color, w_color, loss, nullptr, d_raw_unit};
-    WorkList wl;
-    if (!work_list_of(work_list, work_count, wl) || (work_list && !d_raw_unit)) return ENSLAM_EINVAL;
-    const int rc = ens_launch_render_fwd(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, nullptr, 0, 1, d, depth, var, rgb,
-                                         raw_out, stage == ENSLAM_STAGE_COARSE ? nullptr : act_ws, act_light != 0,
-                                         (hipStream_t)stream, &ls, work_list ? &wl : nullptr);
-    return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EUNSUPPORTED : ENSLAM_ELAUNCH);
+    return render_fwd_body(stage, n_rays, n_samples, rays_o, rays_d, z_vals, scene, depth, var, rgb, raw_out, act_ws, act_light, &ls,
+                           nullptr, work_list, work_count, stream);
 }
 int enslam_render_tracker_loss_fwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
                                    const double* z_vals, const enslam_scene* scene, double* depth, double* var, float* rgb,
                                    float* raw_out, float* act_ws, int32_t act_light, const float* gt_depth, const float* gt_color,
                                    float w_color, const uint8_t* inside, int32_t handle_dynamic, double* tmp_scratch, double* loss,
                                    float* d_raw_unit, int32_t* work_list, int32_t* work_count, void* stream) {
-    if (n_rays < 0) return ENSLAM_EINVAL;
-    if (n_rays == 0) return ENSLAM_OK;
-    if (!samples_ok(n_samples) || n_rays > ENS_TRACKER_TAIL_MAX_RAYS || stage == ENSLAM_STAGE_COARSE) return ENSLAM_EUNSUPPORTED;
-    DevScene d;
-    if (!to_dev_scene(scene, d) || !stage_ok(stage, d)) return ENSLAM_EINVAL;
-    if (!rays_o || !rays_d || !z_vals || !depth || !var || !rgb || !raw_out || !gt_depth || !loss || !tmp_scratch) return ENSLAM_EINVAL;
-    if (act_ws != nullptr)
-        for (int k = 1; k < 4; ++k)
-            if (d.grid[k].data && (int64_t)d.grid[k].D * d.grid[k].H * d.grid[k].W >= ACT_MAX_VOXELS) return ENSLAM_EUNSUPPORTED;
     const LossSpec ls{gt_depth, gt_color, w_color, loss, nullptr, d_raw_unit};
     const TrackerSpec ts{inside, handle_dynamic != 0 ? 1 : 0, tmp_scratch};
-    WorkList wl;
-    if (!work_list_of(work_list, work_count, wl) || (work_list && !d_raw_unit)) return ENSLAM_EINVAL;
-    const int rc = ens_launch_render_fwd(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, nullptr, 0, 1, d, depth, var, rgb,
-                                         raw_out, act_ws, act_light != 0, (hipStream_t)stream, &ls, work_list ? &wl : nullptr, &ts);
-    return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EUNSUPPORTED : ENSLAM_ELAUNCH);
+    return render_fwd_body(stage, n_rays, n_samples, rays_o, rays_d, z_vals, scene, depth, var, rgb, raw_out, act_ws, act_light, &ls,
+                           &ts, work_list, work_count, stream);
 }
 int enslam_tracker_tail(int32_t n_rays, int32_t n_samples, const float* raw, const double* z_vals, double* depth, double* var,
                         float* rgb, const float* gt_depth, const float* gt_color, float w_color, const uint8_t* inside,
@@ -779,9 +735,9 @@ int enslam_tracker_tail(int32_t n_rays, int32_t n_samples, const float* raw, con
     WorkList wl;
     if (!work_list_of(work_list, work_count, wl) || (work_list && !d_raw_unit)) return ENSLAM_EINVAL;
     if (work_list && n_samples % 16 != 0) return ENSLAM_EINVAL;      // the list holds whole 16-sample tiles only
-    const int rc = ens_launch_tracker_tail(n_rays, n_samples, raw, z_vals, depth, var, rgb, ls, ts, work_list ? &wl : nullptr,
-                                           (hipStream_t)stream, loss_only != 0);
-    return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EINVAL : ENSLAM_ELAUNCH);
+    return launch_rc(ens_launch_tracker_tail(n_rays, n_samples, raw, z_vals, depth, var, rgb, ls, ts, work_list ? &wl : nullptr,
+                                             (hipStream_t)stream, loss_only != 0),
+                     ENSLAM_EINVAL);
 }
 int enslam_tracker_tail_max_rays(void) { return ENS_TRACKER_TAIL_MAX_RAYS; }
 int64_t enslam_fwd_res_min_tiles(void) { return FWD_RES_MIN_TILES; }
@@ -804,19 +760,28 @@ int enslam_tracker_rays(int32_t n, const float* camera_tensor, const int64_t* pi
                                    depth_max, (hipStream_t)stream, draw_counter, n_draws) == 0 ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
 
+// The compositing backward: the one body behind enslam_composite_bwd (no list, no loss), enslam_composite_bwd_list (no loss)
+// and enslam_composite_loss_bwd (ls with its rgb; the output gradients NULL).
+static int composite_bwd_body(int32_t n_rays, int32_t n_samples, const float* raw, const double* z_vals, const double* depth,
+                              const double* g_depth, const double* g_var, const float* g_rgb, float* d_raw, const LossSpec* ls,
+                              const float* rgb, int32_t* work_list, int32_t* work_count, void* stream) {
+    if (n_rays < 0 || n_samples < 1 || n_samples > 64) return ENSLAM_EINVAL;
+    if (n_rays == 0) return ENSLAM_OK;
+    if (!raw || !z_vals || !depth || !d_raw) return ENSLAM_EINVAL;
+    if (ls != nullptr && (!ls->gd || !ls->g_loss || (ls->gc && !rgb))) return ENSLAM_EINVAL;
+    WorkList wl;
+    if (!work_list_of(work_list, work_count, wl)) return ENSLAM_EINVAL;
+    if (work_list && n_samples % 16 != 0) return ENSLAM_EINVAL;      // the list holds whole 16-sample tiles only
+    return launch_rc(ens_launch_composite_bwd(n_rays, n_samples, raw, z_vals, depth, g_depth, g_var, g_rgb, d_raw, (hipStream_t)stream,
+                                              ls, rgb, work_list ? &wl : nullptr));
+}
 int enslam_composite_loss_bwd(int32_t n_rays, int32_t n_samples, const float* raw, const double* z_vals,
                               const double* depth, const float* rgb, const float* gt_depth, const float* gt_color,
                               float w_color, const double* g_loss, float* d_raw, int32_t* work_list, int32_t* work_count,
                               void* stream) {
-    if (n_rays < 0 || n_samples < 1 || n_samples > 64) return ENSLAM_EINVAL;
-    if (n_rays == 0) return ENSLAM_OK;
-    if (!raw || !z_vals || !depth || !gt_depth || !g_loss || !d_raw || (gt_color && !rgb)) return ENSLAM_EINVAL;
     const LossSpec ls{gt_depth, gt_color, w_color, nullptr, g_loss, nullptr};
-    WorkList wl;
-    if (!work_list_of(work_list, work_count, wl)) return ENSLAM_EINVAL;
-    if (work_list && n_samples % 16 != 0) return ENSLAM_EINVAL;      // the list holds whole 16-sample tiles only
-    return ens_launch_composite_bwd(n_rays, n_samples, raw, z_vals, depth, nullptr, nullptr, nullptr, d_raw,
-                                    (hipStream_t)stream, &ls, rgb, work_list ? &wl : nullptr) == 0 ? ENSLAM_OK : ENSLAM_ELAUNCH;
+    return composite_bwd_body(n_rays, n_samples, raw, z_vals, depth, nullptr, nullptr, nullptr, d_raw, &ls, rgb, work_list, work_count,
+                              stream);
 }
 
 size_t enslam_grid_handoff_floats(int32_t stage, int32_t n_rays, int32_t n_samples) {
@@ -852,23 +817,14 @@ int enslam_composite_fwd(int32_t n_rays, int32_t n_samples, const float* raw, co
 int enslam_composite_bwd(int32_t n_rays, int32_t n_samples, const float* raw, const double* z_vals,
                          const double* depth, const double* g_depth, const double* g_var, const float* g_rgb,
                          float* d_raw, void* stream) {
-    if (n_rays < 0 || n_samples < 1 || n_samples > 64) return ENSLAM_EINVAL;
-    if (n_rays == 0) return ENSLAM_OK;
-    if (!raw || !z_vals || !depth || !d_raw) return ENSLAM_EINVAL;
-    return ens_launch_composite_bwd(n_rays, n_samples, raw, z_vals, depth, g_depth, g_var, g_rgb, d_raw,
-                                    (hipStream_t)stream);
+    return enslam_composite_bwd_list(n_rays, n_samples, raw, z_vals, depth, g_depth, g_var, g_rgb, d_raw, nullptr, nullptr, stream);
 }
 
 int enslam_composite_bwd_list(int32_t n_rays, int32_t n_samples, const float* raw, const double* z_vals,
                               const double* depth, const double* g_depth, const double* g_var, const float* g_rgb,
                               float* d_raw, int32_t* work_list, int32_t* work_count, void* stream) {
-    if (n_rays < 0 || n_samples < 1 || n_samples > 64) return ENSLAM_EINVAL;
-    if (n_rays == 0) return ENSLAM_OK;
-    WorkList wl;
-    if (!raw || !z_vals || !depth || !d_raw || !work_list_of(work_list, work_count, wl)) return ENSLAM_EINVAL;
-    if (work_list && n_samples % 16 != 0) return ENSLAM_EINVAL;      // the list holds whole 16-sample tiles only
-    return ens_launch_composite_bwd(n_rays, n_samples, raw, z_vals, depth, g_depth, g_var, g_rgb, d_raw, (hipStream_t)stream,
-                                    nullptr, nullptr, work_list ? &wl : nullptr);
+    return composite_bwd_body(n_rays, n_samples, raw, z_vals, depth, g_depth, g_var, g_rgb, d_raw, nullptr, nullptr, work_list, work_count,
+                              stream);
 }
 
 int enslam_decoder_bwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
@@ -923,9 +879,9 @@ int enslam_ray_grad_bwd(int32_t stage, int32_t n_rays, int32_t n_samples, const 
     DevScene d;
     if (!to_dev_scene(scene, d) || !stage_ok(stage, d)) return ENSLAM_EINVAL;
     if (!rays_o || !rays_d || !z_vals || !dgrid_ws || !g_rays_o || !g_rays_d) return ENSLAM_EINVAL;
-    const int rc = ens_launch_ray_grad_bwd(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, d, dgrid_ws, g_rays_o,
-                                           g_rays_d, (hipStream_t)stream);
-    return rc == 0 ? ENSLAM_OK : (rc == -1 ? ENSLAM_EINVAL : ENSLAM_ELAUNCH);
+    return launch_rc(ens_launch_ray_grad_bwd(stage, n_samples / 16, n_rays, rays_o, rays_d, z_vals, d, dgrid_ws, g_rays_o, g_rays_d,
+                                             (hipStream_t)stream),
+                     ENSLAM_EINVAL);
 }
 
 int enslam_render_bwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float* rays_o, const float* rays_d,
@@ -1094,13 +1050,16 @@ int enslam_plan_layout(const enslam_step_plan* plan, enslam_step_layout* L) {
 }
 
 namespace {
-// scene of a plan call: grid values (converted copy for mode 3), packed decoders
-void plan_scene(const enslam_step_plan* plan, const enslam_step_layout* L, void* scratch, const float* const* grid_values, enslam_scene& sc) {
+// scene of a plan call: grid values (converted copy for mode 3), packed decoders.  marking_only: the scene the sampler's block
+// marking reads -- the dims of the grids with gradient (mode >= 2), no data (grid_values is not looked at)
+void plan_scene(const enslam_step_plan* plan, const enslam_step_layout* L, void* scratch, const float* const* grid_values, enslam_scene& sc,
+                bool marking_only = false) {
     for (int i = 0; i < 6; ++i) { sc.bound[i] = plan->bound[i]; sc.coarse_bound[i] = plan->coarse_bound[i]; }
     for (int k = 0; k < 4; ++k) {
         sc.grids[k].data = nullptr; sc.grids[k].D = sc.grids[k].H = sc.grids[k].W = 0; sc.packed[k] = nullptr;
-        if (plan->grid_mode[k] == 0) continue;
+        if (plan->grid_mode[k] < (marking_only ? 2 : 1)) continue;
         sc.grids[k].D = plan->grid_D[k]; sc.grids[k].H = plan->grid_H[k]; sc.grids[k].W = plan->grid_W[k];
+        if (marking_only) continue;
         sc.grids[k].data = plan->grid_mode[k] == 3 ? at<float>(scratch, L->s_vm[k]) : const_cast<float*>(grid_values[k]);
         sc.packed[k] = at<float>(scratch, L->s_packed[k]);
     }
@@ -1118,17 +1077,11 @@ int enslam_plan_forward(const enslam_step_plan* plan, const enslam_step_layout* 
     if (L->s_zero_bytes > 0 && hipMemsetAsync(scratch, 0, (size_t)L->s_zero_bytes, (hipStream_t)stream) != hipSuccess) return ENSLAM_ELAUNCH;
     // block marking of the grids with gradient
     enslam_scene msc;
-    for (int i = 0; i < 6; ++i) { msc.bound[i] = plan->bound[i]; msc.coarse_bound[i] = plan->coarse_bound[i]; }
+    plan_scene(plan, L, scratch, nullptr, msc, true);
     uint8_t* fptr[4] = {nullptr, nullptr, nullptr, nullptr};
     bool marking = false;
-    for (int k = 0; k < 4; ++k) {
-        msc.grids[k].data = nullptr; msc.grids[k].D = msc.grids[k].H = msc.grids[k].W = 0; msc.packed[k] = nullptr;
-        if (plan->grid_mode[k] >= 2) {
-            msc.grids[k].D = plan->grid_D[k]; msc.grids[k].H = plan->grid_H[k]; msc.grids[k].W = plan->grid_W[k];
-            fptr[k] = at<uint8_t>(scratch, L->s_flags[k]);
-            marking = true;
-        }
-    }
+    for (int k = 0; k < 4; ++k)
+        if (plan->grid_mode[k] >= 2) { fptr[k] = at<uint8_t>(scratch, L->s_flags[k]); marking = true; }
     // prepare roles: pack every decoder of the stage, clear the accumulators
     int32_t kinds[3]; enslam_mlp_params structs[3]; float* packed[3]; int nd = 0;
     for (int k = 1; k < 4; ++k)

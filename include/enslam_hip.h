@@ -214,7 +214,20 @@ int enslam_bucket_unpack(int32_t n_grids, float *const *grid_grad, int32_t chann
 /* The small independent jobs around a render call in ONE launch each (they are 4-6 us kernels when issued separately):
  * enslam_step_prepare = enslam_pack_mlp_multi (n_dec decoders) + enslam_grids_convert_sparse to voxel-major (n_conv
  *   grids) + enslam_zero_blocks (n_zero accumulators and the flat range); any of the three parts may be empty.
- * enslam_step_finish  = enslam_grids_convert_sparse back to [32,V] (gradients) + enslam_unpack_mlp_grads_multi. */
+ * enslam_step_finish  = enslam_grids_convert_sparse back to [32,V] (gradients) + enslam_unpack_mlp_grads_multi.
+ * The finish launch is one family, each member the next wider one with its extra arguments fixed:
+ *   enslam_step_finish           = enslam_step_finish_rays with n_rays = 0 (no ray arguments)
+ *   enslam_step_finish_rays      = enslam_step_finish_rays_prev with prev = NULL
+ *   enslam_step_finish_rays_prev = enslam_step_finish_partials with grad_partials = NULL, except for the NULL hand-off below
+ *   enslam_step_finish_partials  = enslam_step_finish_native with n_move = 0 (move_need, move_prev unused)
+ * One rule differs.  With a ray role asked for (n_rays > 0, stage above COARSE) the two narrow members that take rays,
+ * enslam_step_finish_rays and enslam_step_finish_rays_prev, REQUIRE the hand-off: dgrid_ws NULL is ENSLAM_EINVAL (after the
+ * sample count has been checked).  The two wide members, enslam_step_finish_partials and enslam_step_finish_native, read a
+ * NULL dgrid_ws as "no ray role": the ray arguments, scene and sample count are then not looked at, as with n_rays = 0.
+ * Common to all: n_rays < 0 (and n_move < 0, or n_move > 0 without both move pointers) is ENSLAM_EINVAL; then prev, when given,
+ * needs need and every need[i] / prev[i] (ENSLAM_EINVAL); then, with a ray role, n_samples not in {16, 32, 48, 64} is
+ * ENSLAM_EUNSUPPORTED, and a scene that lacks the stage's grids, a NULL ray pointer or half a work list ENSLAM_EINVAL; the
+ * conversion and unpack arguments are checked last. */
 int enslam_step_prepare(int32_t n_dec, const int32_t *kinds, const enslam_mlp_params *params, float *const *packed,
                         int32_t n_conv, const float *const *src, float *const *dst, const int64_t *n_voxels,
                         const uint8_t *const *need, uint8_t *const *valid, int32_t n_zero, float *const *zero_dst,
@@ -224,7 +237,8 @@ int enslam_step_finish(int32_t n_conv, const float *const *src, float *const *ds
                        const uint8_t *const *need, int32_t n_dec, const int32_t *kinds,
                        const float *const *packed_grads, const enslam_mlp_params *grads, void *stream);
 /* enslam_step_finish with enslam_ray_grad_bwd riding in the same launch (both depend only on enslam_decoder_bwd):
- * one dependent launch fewer per step.  stage COARSE or n_rays == 0: plain enslam_step_finish. */
+ * one dependent launch fewer per step.  stage COARSE or n_rays == 0: plain enslam_step_finish.  Otherwise dgrid_ws (the
+ * hand-off enslam_decoder_bwd left) is required, see above. */
 int enslam_step_finish_rays(int32_t n_conv, const float *const *src, float *const *dst, const int64_t *n_voxels,
                             const uint8_t *const *need, int32_t n_dec, const int32_t *kinds,
                             const float *const *packed_grads, const enslam_mlp_params *grads, int32_t stage,
@@ -246,9 +260,9 @@ int enslam_step_finish_rays_prev(int32_t n_conv, const float *const *src, float 
                                  const double *z_vals, const enslam_scene *scene, float *dgrid_ws, float *g_rays_o,
                                  float *g_rays_d, const int32_t *work_list, const int32_t *work_count, void *stream);
 
-/* The general finish launch: enslam_step_finish_rays_prev (prev NULL: no persistent destinations; dgrid_ws NULL or
- * n_rays == 0: no ray-gradient role) which, for every decoder i with grad_partials[i] != NULL, forms the gradient as the SUM
- * of the per-workgroup partial images enslam_decoder_bwd_partials left there instead of reading packed_grads[i]. */
+/* enslam_step_finish_rays_prev (prev NULL: no persistent destinations) which, for every decoder i with grad_partials[i] != NULL,
+ * forms the gradient as the SUM of the per-workgroup partial images enslam_decoder_bwd_partials left there instead of reading
+ * packed_grads[i] (grad_partials NULL: none).  Unlike there, dgrid_ws NULL means "no ray-gradient role", as n_rays == 0 does. */
 int enslam_step_finish_partials(int32_t n_conv, const float *const *src, float *const *dst, const int64_t *n_voxels,
                                 const uint8_t *const *need, uint8_t *const *prev, int32_t n_dec, const int32_t *kinds,
                                 const float *const *packed_grads, const float *const *grad_partials,
@@ -275,7 +289,9 @@ int enslam_step_finish_native(int32_t n_conv, const float *const *src, float *co
  * feature grids all arrive in the kernels' own layout: with nothing to convert, no prepare role waits for the sampler's
  * block marks, and the decoder packing / accumulator clearing run under the sampler's latency (a ray's wave is one dependent
  * chain of float64 divisions and a 21-step shuffle sort).  Arguments: enslam_sample_rays_g's, then enslam_step_prepare's
- * (n_dec .. packed, n_zero .. n_flat).  n_rays = 0 runs the prepare roles alone.
+ * (n_dec .. packed, n_zero .. n_flat); the sampler arguments are checked as there (mark_block_voxels in every call).
+ * n_rays = 0 runs the prepare roles alone: unlike enslam_sample_rays_g, which returns ENSLAM_OK for n_rays = 0 before it looks
+ * at a pointer or at the marking, this call goes on, still needs bound_host and still checks the marking arguments.
  *   Replaces Renderer.render_batch_ray lines 83-171 (sampling) of the reference; the prepare roles replace nothing. */
 int enslam_sample_prepare(int32_t n_rays, int32_t n_lin, int32_t n_surf, const float *rays_o, const float *rays_d,
                           const float *gt_depth, const double *bound_host, const float *t_lin, const double *t_surf,
@@ -307,8 +323,9 @@ int enslam_tracker_rays(int32_t n, const float *camera_tensor, const int64_t *pi
                         void *stream);
 
 /* enslam_render_loss_fwd with the TRACKER's loss in place of the mapper's (batches of up to enslam_tracker_tail_max_rays()
- * rays; more: ENSLAM_EUNSUPPORTED): behind the decoder kernel two launches of 16 rays per workgroup (one without
- * handle_dynamic) -- compositing with
+ * rays; more, or the coarse stage: ENSLAM_EUNSUPPORTED, reported where the sample count is, before the scene and the pointers
+ * are looked at; tmp_scratch is required as gt_depth, loss and raw_out are): behind the decoder kernel two launches of 16
+ * rays per workgroup (one without handle_dynamic) -- compositing with
  *   tmp = |gt_depth - depth| / sqrt(var + 1e-10),
  * then, every workgroup taking the median of tmp over the inside rays for itself (the lower median of torch.median; by counting
  * ranks in LDS up to 1024 rays, a bitonic network above),
@@ -367,7 +384,9 @@ int enslam_sample_rays(int32_t n_rays, int32_t n_lin, int32_t n_surf, const floa
                        int32_t mark_stage, const enslam_scene *mark_scene, uint8_t *const *mark_flags, void *stream);
 /* enslam_sample_rays whose block marking works at mark_block_voxels in {64, 32, 16, 8} voxels per flag (mark_flags sized
  * accordingly) and, for the finer ones, optionally leaves the 64-voxel form in mark_flags64 as well (NULL: not wanted): the flags
- * of a ray-sharded step's gradient bucket (enslam_bucket_pack_g) and what the finish launch keeps, from ONE launch. */
+ * of a ray-sharded step's gradient bucket (enslam_bucket_pack_g) and what the finish launch keeps, from ONE launch.
+ * enslam_sample_rays is this call with mark_block_voxels = 64 and mark_flags64 = NULL.  A mark_block_voxels outside {64, 32, 16, 8} is
+ * ENSLAM_EINVAL, with or without marking and for n_rays = 0 too; no pointer and no marking argument is looked at when n_rays = 0 (ENSLAM_OK). */
 int enslam_sample_rays_g(int32_t n_rays, int32_t n_lin, int32_t n_surf, const float *rays_o, const float *rays_d,
                          const float *gt_depth, const double *bound, const float *t_lin, const double *t_surf,
                          int32_t lindisp, const float *t_rand, float *scratch, int32_t depth_max_given, double *z_vals,
@@ -665,7 +684,9 @@ int enslam_render_bwd(int32_t stage, int32_t n_rays, int32_t n_samples, const fl
  *   float32 [N*S,4]): d(loss)/d(raw) for g_loss = 1, so that the backward can start at enslam_decoder_bwd_scaled
  *   (d_raw = d_raw_unit, d_raw_scale = g_loss) without a compositing launch.
  * enslam_composite_loss_bwd: enslam_composite_bwd with d(depth), d(rgb) derived from that loss and the device scalar
- *   g_loss = d(total)/d(loss) instead of read from memory; follow with enslam_decoder_bwd. */
+ *   g_loss = d(total)/d(loss) instead of read from memory; follow with enslam_decoder_bwd.  gt_depth and g_loss are required,
+ *   rgb (the forward's) when gt_color is given; the work list arguments are enslam_composite_bwd_list's.
+ * enslam_render_fwd is enslam_render_loss_fwd without the loss arguments and the list; only there may raw_out be NULL. */
 int enslam_render_loss_fwd(int32_t stage, int32_t n_rays, int32_t n_samples, const float *rays_o, const float *rays_d,
                            const double *z_vals, const enslam_scene *scene, double *depth, double *var, float *rgb,
                            float *raw_out, float *act_ws, int32_t act_light, const float *gt_depth,
@@ -721,7 +742,8 @@ int enslam_decoder_bwd_partials(int32_t stage, int32_t n_rays, int32_t n_samples
  * enslam_composite_bwd_list.  enslam_decoder_bwd_scaled (saved-activation roles only) and enslam_step_finish_rays then
  * walk the list instead of all tiles; both must be given the same list.  The list holds whole tiles only: with a work list
  * n_samples must be a multiple of 16 (ENSLAM_EINVAL otherwise; the samples past the last whole tile would never be listed).
- * Without a list the two compositing entries take every n_samples from 1 to 64. */
+ * Without a list the two compositing entries take every n_samples from 1 to 64.
+ * enslam_composite_bwd is enslam_composite_bwd_list with work_list = work_count = NULL. */
 int enslam_composite_bwd_list(int32_t n_rays, int32_t n_samples, const float *raw, const double *z_vals,
                               const double *depth, const double *g_depth, const double *g_var, const float *g_rgb,
                               float *d_raw, int32_t *work_list, int32_t *work_count, void *stream);

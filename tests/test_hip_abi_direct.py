@@ -158,3 +158,96 @@ def test_step_finish_rays_prev_persistent_destination():
     # prev without flags is refused
     assert lib.enslam_step_finish_rays_prev(1, arr(vm.data_ptr()), arr(dense.data_ptr()), nvox, None, arr(prev.data_ptr()), 0, None,
                                             None, None, 3, 0, 48, None, None, None, None, None, None, None, None, None, st) == -1
+
+
+def test_the_five_finish_members_agree_with_their_extras_absent():
+    """All five enslam_step_finish* members with zero rays, NULL prev, no partials and n_move = 0 are the same launch: one dense
+    grid of 5 x 6 x 7 voxels (four 64-voxel blocks, the last with 18 voxels), blocks 0 and 3 flagged, five destinations that must
+    agree bit for bit.  What they hold is pinned too: the flagged blocks are the transposed source; the unflagged ones are zeros
+    (without prev the destination is fresh memory: include/enslam_hip.h, enslam_grids_convert_sparse); the row behind the
+    buffer, the source and the flags are untouched.  With prev (all zero: nothing written before) the three members that take
+    it write the same flagged blocks, leave the unflagged blocks alone and move the flags."""
+    import evennicer_slam_amd as E
+    import evennicer_slam_amd.functional as EF
+    from tests.hip_util import DEV
+    L = E._lib
+    lib = L.lib()
+    st = EF._stream()
+    D, H, W = 5, 6, 7
+    V = D * H * W
+    assert (V + 63) // 64 == 4 and V % 64 == 18
+    vm = torch.randn((V, 32), generator=torch.Generator().manual_seed(11)).to(DEV)
+    vm_before = vm.clone()
+    flags = torch.tensor([1, 0, 0, 1], dtype=torch.uint8, device=DEV)
+    flagged = torch.zeros(V, dtype=torch.bool, device=DEV)
+    flagged[:64] = True
+    flagged[192:] = True
+    want = torch.zeros((32, V), dtype=torch.float32, device=DEV)
+    want[:, flagged] = vm.t()[:, flagged]
+    arr = lambda *ptrs: (ctypes.c_void_p * len(ptrs))(*ptrs)
+    nvox = (ctypes.c_int64 * 1)(V)
+    SENTINEL = 123.0
+    no_rays = (3, 0, 48, None, None, None, None, None, None, None, None, None)   # stage .. work_count
+
+    def run(name, prev=None):
+        dst = torch.full((33, V), SENTINEL, dtype=torch.float32, device=DEV)        # row 32 lies behind the [32][V] buffer
+        need = flags.clone()
+        conv = (1, arr(vm.data_ptr()), arr(dst.data_ptr()), nvox, arr(need.data_ptr()))
+        pv = (arr(prev.data_ptr()) if prev is not None else None,)
+        args = {"enslam_step_finish": conv + (0, None, None, None),
+                "enslam_step_finish_rays": conv + (0, None, None, None) + no_rays,
+                "enslam_step_finish_rays_prev": conv + pv + (0, None, None, None) + no_rays,
+                "enslam_step_finish_partials": conv + pv + (0, None, None, None, None) + no_rays,
+                "enslam_step_finish_native": conv + pv + (0, None, None, None, None) + no_rays + (None, None, 0)}[name]
+        L.check(getattr(lib, name)(*args, st), name)
+        torch.cuda.synchronize()
+        assert bool((dst[32] == SENTINEL).all()), name
+        assert torch.equal(vm, vm_before), name
+        return dst[:32], need
+
+    names = ("enslam_step_finish", "enslam_step_finish_rays", "enslam_step_finish_rays_prev", "enslam_step_finish_partials",
+             "enslam_step_finish_native")
+    first = None
+    for name in names:
+        got, need = run(name)
+        assert torch.equal(need, flags), name                        # without prev the flags stay
+        assert torch.equal(got, want), name
+        first = got if first is None else first
+        assert torch.equal(got.view(torch.int32), first.view(torch.int32)), name
+    for name in names[2:]:
+        prev = torch.zeros(4, dtype=torch.uint8, device=DEV)
+        got, need = run(name, prev)
+        assert torch.equal(prev, flags) and int(need.sum()) == 0, name
+        assert torch.equal(got[:, flagged].view(torch.int32), first[:, flagged].view(torch.int32)), name
+        assert bool((got[:, ~flagged] == SENTINEL).all()), name      # untouched now and before: not written at all
+
+
+@pytest.mark.parametrize("S", [16, 40])
+def test_composite_bwd_is_composite_bwd_list_without_a_list(S):
+    """enslam_composite_bwd and enslam_composite_bwd_list with a NULL list write the same d_raw bit for bit (5 rays; 16 samples:
+    one whole tile, 40: a count only the list-free launch takes)."""
+    import evennicer_slam_amd as E
+    import evennicer_slam_amd.functional as EF
+    from tests.hip_util import DEV
+    L = E._lib
+    lib = L.lib()
+    P, st = EF._ptr, EF._stream()
+    N = 5
+    g = torch.Generator().manual_seed(100 + S)
+    raw = torch.randn((N * S, 4), generator=g).to(DEV)
+    z = (0.1 + torch.rand((N, S), generator=g, dtype=torch.float64)).cumsum(1).to(DEV)
+    depth = torch.empty(N, dtype=torch.float64, device=DEV)
+    var = torch.empty(N, dtype=torch.float64, device=DEV)
+    rgb = torch.empty((N, 3), dtype=torch.float32, device=DEV)
+    L.check(lib.enslam_composite_fwd(N, S, P(raw), P(z), P(depth), P(var), P(rgb), None, st), "enslam_composite_fwd")
+    gD = torch.randn(N, generator=g, dtype=torch.float64).to(DEV)
+    gV = torch.randn(N, generator=g, dtype=torch.float64).to(DEV)
+    gC = torch.randn((N, 3), generator=g).to(DEV)
+    a = torch.full((N * S, 4), 1.0, dtype=torch.float32, device=DEV)        # different fills: an element neither call writes shows
+    b = torch.full((N * S, 4), 2.0, dtype=torch.float32, device=DEV)
+    L.check(lib.enslam_composite_bwd(N, S, P(raw), P(z), P(depth), P(gD), P(gV), P(gC), P(a), st), "enslam_composite_bwd")
+    L.check(lib.enslam_composite_bwd_list(N, S, P(raw), P(z), P(depth), P(gD), P(gV), P(gC), P(b), None, None, st),
+            "enslam_composite_bwd_list")
+    torch.cuda.synchronize()
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0.0
