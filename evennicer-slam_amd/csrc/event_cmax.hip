@@ -1,10 +1,13 @@
-// Event motion compensation by contrast maximisation (enslam_event_cmax_eval; enslam_hip.h holds the model and fixes the order
-// of every float64 operation): the image of warped events of a stream under a candidate motion, the variance of its blur and
+// Event motion compensation by contrast maximisation (enslam_event_cmax_eval and enslam_event_cmax_rigid_eval; enslam_hip.h
+// holds the models and fixes the order of every float64 operation): the image of warped events of a stream under a candidate motion, the variance of its blur and
 // the gradient of that variance in the motion.  One evaluation is a fixed chain of launches on one stream:
 //
-//   vote     one thread per event: sensor check, time check, warp, the float64 range check, then up to four 64-bit integer
-//            atomic adds of llrint(w 2^32) into the int64 IWE (corners of weight 0 are not sent).  The three drop counters are
-//            summed per workgroup in LDS, then one global integer add per workgroup and counter.
+//   zero     one thread per pixel: the IWE, the drop counters and stats start from zero.  A kernel, not memsets: captured as
+//            memset nodes, the three did not zero their buffers again from the second replay of the graph on
+//            (tests/test_hip_event_cmax_rigid.py replays one captured evaluation over refilled outputs)
+//   vote     one thread per event: sensor check, time check, (rigid: depth check,) warp, the float64 range check, then up to
+//            four 64-bit integer atomic adds of llrint(w 2^32) into the int64 IWE (corners of weight 0 are not sent).  The drop
+//            counters are summed per workgroup in LDS, then one global integer add per workgroup and counter.
 //   rows     one thread per pixel: r = the row pass of the zero-padded blur (of the IWE times 2^-32, or of J - mu)
 //   columns  one thread per pixel: the column pass; for J also the first level of SUM(J) (256 consecutive pixels per
 //            workgroup, halving tree in LDS, one partial per workgroup)
@@ -14,8 +17,10 @@
 //   gather   one thread per event: the same warp, the four D values of its corners, its P products into the block tree in LDS
 // Integer atomics for the image, fixed trees for every float64 sum, no float atomics, no fences: two runs give the same
 // bits, and the numpy route of event_cmax.py, which performs the same operations in the same order, gives them too.
-// Every address comes from a checked value: the event's own x, y against the sensor before anything else, the warped
-// position against (-1, W) x (-1, H) in float64 before floor() and the conversion, every corner against the image.
+// The three models share one warp (cm_warp<MODEL>), one vote and one gather; the kernels are templates of the model only so
+// that the factors Bu, Bv and the gather's LDS tree have the model's own size (rigid: 6 x 256 doubles = 12 KB).
+// Every address comes from a checked value: the event's own x, y against the sensor before anything else (the rigid model
+// reads its depth at that checked pixel and nowhere else), the warped position against (-1, W) x (-1, H) in float64 before floor() and the conversion, every corner against the image.
 #include "../../include/enslam_hip.h"
 #include "common.hpp"
 
@@ -25,7 +30,8 @@ namespace {
 
 constexpr int CM_BLOCK = 256;
 constexpr int CM_KMAX = ENSLAM_CMAX_MAX_KSIZE;
-constexpr int CM_PMAX = 3;
+constexpr int CM_PMAX = 6;
+constexpr int CM_RIGID = 2;                                 // the third model, behind its own entry point only
 constexpr int64_t CM_MAX_EVENTS = 2147483647;
 constexpr int64_t CM_MAX_PIXELS = (int64_t)1 << 28;
 constexpr double CM_TWO32 = 4294967296.0;
@@ -36,6 +42,7 @@ struct CmStream {
     const uint16_t* x;
     const uint16_t* y;
     const uint8_t* p;
+    const float* depth;                                     // [H,W], the rigid model's; nullptr otherwise
     int64_t N;
     int32_t H, W, model, sign_votes;
     double fx, fy, cx, cy, t_ref;
@@ -48,16 +55,20 @@ struct CmBlur {
 };
 
 // what the header calls a vote: the cell (x0, y0), the fractions and the factors of the gradient
+template <int P>
 struct CmWarp {
     int x0, y0;
     double a, b, oa, ob, mx, my, s;
-    double Bu[CM_PMAX], Bv[CM_PMAX];
+    double Bu[P], Bv[P];
 };
+
+constexpr int cm_params(int model) { return model == ENSLAM_CMAX_FLOW ? 2 : model == ENSLAM_CMAX_ROTATION ? 3 : 6; }
 
 enum { CM_OK = -1 };
 
 // CM_OK, or the drop counter of event i.  The operations and their order are the header's.
-__device__ __forceinline__ int cm_warp(const CmStream& S, int64_t i, CmWarp& Q) {
+template <int MODEL>
+__device__ __forceinline__ int cm_warp(const CmStream& S, int64_t i, CmWarp<cm_params(MODEL)>& Q) {
     const unsigned ex = S.x[i], ey = S.y[i];
     if (ex >= (unsigned)S.W || ey >= (unsigned)S.H) return ENSLAM_CMAX_DROP_SENSOR;
     const double tv = S.t[i];
@@ -65,9 +76,9 @@ __device__ __forceinline__ int cm_warp(const CmStream& S, int64_t i, CmWarp& Q) 
     const double xd = (double)ex, yd = (double)ey;
     const double dt = tv - S.t_ref;
     double du, dv;
-    if (S.model == ENSLAM_CMAX_FLOW) {
-        Q.Bu[0] = 1.0 / S.fx; Q.Bu[1] = 0.0; Q.Bu[2] = 0.0;
-        Q.Bv[0] = 0.0; Q.Bv[1] = 1.0 / S.fy; Q.Bv[2] = 0.0;
+    if constexpr (MODEL == ENSLAM_CMAX_FLOW) {
+        Q.Bu[0] = 1.0 / S.fx; Q.Bu[1] = 0.0;
+        Q.Bv[0] = 0.0; Q.Bv[1] = 1.0 / S.fy;
         du = S.theta[0] / S.fx;
         dv = S.theta[1] / S.fy;
     } else {
@@ -77,6 +88,15 @@ __device__ __forceinline__ int cm_warp(const CmStream& S, int64_t i, CmWarp& Q) 
         Q.Bv[0] = pv; Q.Bv[1] = -uv; Q.Bv[2] = -u;
         du = (uv * S.theta[0] - pu * S.theta[1]) + v * S.theta[2];
         dv = (pv * S.theta[0] - uv * S.theta[1]) - u * S.theta[2];
+        if constexpr (MODEL == CM_RIGID) {
+            const float z = S.depth[(int64_t)ey * S.W + ex];            // ex < W, ey < H: checked above
+            if (!(std::isfinite(z) && z > 0.0f)) return ENSLAM_CMAX_DROP_DEPTH;
+            const double rho = 1.0 / (double)z;
+            Q.Bu[3] = -rho; Q.Bu[4] = 0.0; Q.Bu[5] = u * rho;
+            Q.Bv[3] = 0.0; Q.Bv[4] = -rho; Q.Bv[5] = v * rho;
+            du = du + rho * (u * S.theta[5] - S.theta[3]);
+            dv = dv + rho * (v * S.theta[5] - S.theta[4]);
+        }
     }
     Q.mx = -(dt * S.fx);
     Q.my = -(dt * S.fy);
@@ -93,21 +113,34 @@ __device__ __forceinline__ int cm_warp(const CmStream& S, int64_t i, CmWarp& Q) 
     return CM_OK;
 }
 
-__device__ __forceinline__ bool cm_corner(const CmStream& S, const CmWarp& Q, int c, int64_t& cell) {
+template <int P>
+__device__ __forceinline__ bool cm_corner(const CmStream& S, const CmWarp<P>& Q, int c, int64_t& cell) {
     const int px = Q.x0 + (c & 1), py = Q.y0 + (c >> 1);
     if (px < 0 || px >= S.W || py < 0 || py >= S.H) return false;
     cell = (int64_t)py * S.W + px;
     return true;
 }
 
+__global__ __launch_bounds__(CM_BLOCK) void cmax_zero_kernel(long long* __restrict__ iwe, int64_t npix, unsigned long long* __restrict__ dropped,
+                                                             int n_dropped, double* __restrict__ stats, int n_stats) {
+    const int64_t o = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
+    if (o < npix) iwe[o] = 0;
+    if (blockIdx.x == 0) {
+        if ((int)threadIdx.x < n_dropped) dropped[threadIdx.x] = 0ull;
+        if ((int)threadIdx.x < n_stats) stats[threadIdx.x] = 0.0;
+    }
+}
+
+// dropped has three counters, four for the rigid model: only that model returns the fourth, and a counter of 0 is not sent
+template <int MODEL>
 __global__ __launch_bounds__(CM_BLOCK) void cmax_vote_kernel(CmStream S, unsigned long long* iwe, unsigned long long* dropped) {
-    __shared__ unsigned s_drop[3];
-    if (threadIdx.x < 3) s_drop[threadIdx.x] = 0u;
+    __shared__ unsigned s_drop[4];
+    if (threadIdx.x < 4) s_drop[threadIdx.x] = 0u;
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
     if (i < S.N) {
-        CmWarp Q;
-        const int why = cm_warp(S, i, Q);
+        CmWarp<cm_params(MODEL)> Q;
+        const int why = cm_warp<MODEL>(S, i, Q);
         if (why != CM_OK) {
             atomicAdd(&s_drop[why], 1u);
         } else {
@@ -123,7 +156,7 @@ __global__ __launch_bounds__(CM_BLOCK) void cmax_vote_kernel(CmStream S, unsigne
         }
     }
     __syncthreads();
-    if (threadIdx.x < 3 && s_drop[threadIdx.x]) atomicAdd(&dropped[threadIdx.x], (unsigned long long)s_drop[threadIdx.x]);
+    if (threadIdx.x < 4 && s_drop[threadIdx.x]) atomicAdd(&dropped[threadIdx.x], (unsigned long long)s_drop[threadIdx.x]);
 }
 
 // the halving tree of the header over the workgroup's 256 values; every thread gets the result
@@ -208,13 +241,15 @@ __global__ __launch_bounds__(CM_BLOCK) void cmax_upper_kernel(const double* __re
     }
 }
 
-__global__ __launch_bounds__(CM_BLOCK) void cmax_gather_kernel(CmStream S, int P, const double* __restrict__ D, double* __restrict__ partials) {
-    __shared__ double s_red[CM_PMAX * CM_BLOCK];
+template <int MODEL>
+__global__ __launch_bounds__(CM_BLOCK) void cmax_gather_kernel(CmStream S, const double* __restrict__ D, double* __restrict__ partials) {
+    constexpr int P = cm_params(MODEL);
+    __shared__ double s_red[P * CM_BLOCK];
     const int64_t i = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
-    double g[CM_PMAX] = {0.0, 0.0, 0.0};
+    double g[P] = {};
     if (i < S.N) {
-        CmWarp Q;
-        if (cm_warp(S, i, Q) == CM_OK) {
+        CmWarp<P> Q;
+        if (cm_warp<MODEL>(S, i, Q) == CM_OK) {
             const double dwx[4] = {-Q.ob, Q.ob, -Q.b, Q.b}, dwy[4] = {-Q.oa, -Q.a, Q.oa, Q.a};
             double Gx = 0.0, Gy = 0.0;
             for (int c = 0; c < 4; ++c) {
@@ -253,29 +288,35 @@ int64_t cm_workspace_bytes(int32_t H, int32_t W, int64_t N, int32_t P) {
 
 bool cm_finite(double v) { return std::isfinite(v); }
 
-}  // namespace
-
-extern "C" {
-
-int enslam_event_cmax_workspace(int32_t H, int32_t W, int64_t N, int32_t P, int64_t* bytes_host) {
-    if (!bytes_host || P < 2 || P > CM_PMAX) return ENSLAM_EINVAL;
-    const int rc = cm_sizes(H, W, N);
-    if (rc != ENSLAM_OK) return rc;
-    *bytes_host = cm_workspace_bytes(H, W, N, P);
-    return ENSLAM_OK;
+// the launches that depend on the model
+void cm_vote(int model, const CmStream& S, unsigned blocks, int64_t* iwe, uint64_t* dropped, hipStream_t st) {
+    unsigned long long* I = reinterpret_cast<unsigned long long*>(iwe);
+    unsigned long long* X = reinterpret_cast<unsigned long long*>(dropped);
+    if (model == ENSLAM_CMAX_FLOW) cmax_vote_kernel<ENSLAM_CMAX_FLOW><<<blocks, CM_BLOCK, 0, st>>>(S, I, X);
+    else if (model == ENSLAM_CMAX_ROTATION) cmax_vote_kernel<ENSLAM_CMAX_ROTATION><<<blocks, CM_BLOCK, 0, st>>>(S, I, X);
+    else cmax_vote_kernel<CM_RIGID><<<blocks, CM_BLOCK, 0, st>>>(S, I, X);
 }
 
-int enslam_event_cmax_eval(const double* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t N, int32_t H, int32_t W,
-                           double fx, double fy, double cx, double cy, int32_t model, const double* theta_host, double t_ref,
-                           int32_t sign_votes, int32_t k, const double* taps_host, void* workspace, int64_t workspace_bytes,
-                           int64_t* iwe, double* blurred, double* stats, uint64_t* dropped, int32_t want_grad, void* stream) {
+void cm_gather(int model, const CmStream& S, unsigned blocks, const double* D, double* partials, hipStream_t st) {
+    if (model == ENSLAM_CMAX_FLOW) cmax_gather_kernel<ENSLAM_CMAX_FLOW><<<blocks, CM_BLOCK, 0, st>>>(S, D, partials);
+    else if (model == ENSLAM_CMAX_ROTATION) cmax_gather_kernel<ENSLAM_CMAX_ROTATION><<<blocks, CM_BLOCK, 0, st>>>(S, D, partials);
+    else cmax_gather_kernel<CM_RIGID><<<blocks, CM_BLOCK, 0, st>>>(S, D, partials);
+}
+
+// The one validating body of both *_eval entries.  rigid: the model is CM_RIGID whatever `model` says, depth is its image and
+// dropped has four counters; otherwise model is the caller's ENSLAM_CMAX_FLOW or ENSLAM_CMAX_ROTATION and depth is not looked at.
+int cm_eval(bool rigid, const double* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t N, int32_t H, int32_t W,
+            double fx, double fy, double cx, double cy, int32_t model, const float* depth, const double* theta_host, double t_ref,
+            int32_t sign_votes, int32_t k, const double* taps_host, void* workspace, int64_t workspace_bytes, int64_t* iwe,
+            double* blurred, double* stats, uint64_t* dropped, int32_t want_grad, void* stream) {
     if (!theta_host || !taps_host || !workspace || !iwe || !stats || !dropped) return ENSLAM_EINVAL;
-    if (N > 0 && (!t || !x || !y || !p)) return ENSLAM_EINVAL;
-    if (model != ENSLAM_CMAX_FLOW && model != ENSLAM_CMAX_ROTATION) return ENSLAM_EINVAL;
+    if (N > 0 && (!t || !x || !y || !p || (rigid && !depth))) return ENSLAM_EINVAL;
+    if (rigid) model = CM_RIGID;
+    else if (model != ENSLAM_CMAX_FLOW && model != ENSLAM_CMAX_ROTATION) return ENSLAM_EINVAL;
     if (k <= 0 || k % 2 == 0) return ENSLAM_EINVAL;
     int rc = cm_sizes(H, W, N);
     if (rc == ENSLAM_EINVAL) return rc;
-    const int P = model == ENSLAM_CMAX_FLOW ? 2 : 3;
+    const int P = cm_params(model);
     if (!cm_finite(fx) || !cm_finite(fy) || !cm_finite(cx) || !cm_finite(cy) || !cm_finite(t_ref) || fx == 0.0 || fy == 0.0)
         return ENSLAM_EINVAL;
     for (int i = 0; i < P; ++i)
@@ -296,19 +337,16 @@ int enslam_event_cmax_eval(const double* t, const uint16_t* x, const uint16_t* y
     hipStream_t st = (hipStream_t)stream;
 
     CmStream S;
-    S.t = t; S.x = x; S.y = y; S.p = p; S.N = N; S.H = H; S.W = W; S.model = model; S.sign_votes = sign_votes;
+    S.t = t; S.x = x; S.y = y; S.p = p; S.depth = rigid ? depth : nullptr; S.N = N; S.H = H; S.W = W; S.model = model; S.sign_votes = sign_votes;
     S.fx = fx; S.fy = fy; S.cx = cx; S.cy = cy; S.t_ref = t_ref;
     for (int i = 0; i < CM_PMAX; ++i) S.theta[i] = i < P ? theta_host[i] : 0.0;
     CmBlur B;
     B.H = H; B.W = W; B.k = k;
     for (int i = 0; i < CM_KMAX; ++i) B.taps[i] = i < k ? taps_host[i] : 0.0;
 
-    if (hipMemsetAsync(iwe, 0, (size_t)npix * sizeof(int64_t), st) != hipSuccess) return ENSLAM_ELAUNCH;
-    if (hipMemsetAsync(dropped, 0, 3 * sizeof(uint64_t), st) != hipSuccess) return ENSLAM_ELAUNCH;
-    if (hipMemsetAsync(stats, 0, (size_t)(2 + P) * sizeof(double), st) != hipSuccess) return ENSLAM_ELAUNCH;
-    if (N > 0)
-        cmax_vote_kernel<<<(unsigned)ev_blocks, CM_BLOCK, 0, st>>>(S, reinterpret_cast<unsigned long long*>(iwe),
-                                                                  reinterpret_cast<unsigned long long*>(dropped));
+    cmax_zero_kernel<<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(reinterpret_cast<long long*>(iwe), npix,
+                                                                 reinterpret_cast<unsigned long long*>(dropped), rigid ? 4 : 3, stats, 2 + P);
+    if (N > 0) cm_vote(model, S, (unsigned)ev_blocks, iwe, dropped, st);
     cmax_rows_kernel<long long><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, reinterpret_cast<const long long*>(iwe), bufR);
     cmax_cols_kernel<true><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, bufR, J, partials);
     cmax_upper_kernel<<<1, CM_BLOCK, 0, st>>>(partials, pix_blocks, 1, (double)npix, 0, stats);
@@ -317,10 +355,47 @@ int enslam_event_cmax_eval(const double* t, const uint16_t* x, const uint16_t* y
     if (want_grad) {
         cmax_rows_kernel<double><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, bufC, bufR);
         cmax_cols_kernel<false><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, bufR, bufA, nullptr);
-        if (N > 0) cmax_gather_kernel<<<(unsigned)ev_blocks, CM_BLOCK, 0, st>>>(S, P, bufA, partials);
+        if (N > 0) cm_gather(model, S, (unsigned)ev_blocks, bufA, partials, st);
         cmax_upper_kernel<<<1, CM_BLOCK, 0, st>>>(partials, ev_blocks, P, 2.0 / (double)npix, 1, stats + 2);
     }
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
+}
+
+}  // namespace
+
+extern "C" {
+
+int enslam_event_cmax_workspace(int32_t H, int32_t W, int64_t N, int32_t P, int64_t* bytes_host) {
+    if (!bytes_host || P < 2 || P > 3) return ENSLAM_EINVAL;
+    const int rc = cm_sizes(H, W, N);
+    if (rc != ENSLAM_OK) return rc;
+    *bytes_host = cm_workspace_bytes(H, W, N, P);
+    return ENSLAM_OK;
+}
+
+int enslam_event_cmax_rigid_workspace(int32_t H, int32_t W, int64_t N, int64_t* bytes_host) {
+    if (!bytes_host) return ENSLAM_EINVAL;
+    const int rc = cm_sizes(H, W, N);
+    if (rc != ENSLAM_OK) return rc;
+    *bytes_host = cm_workspace_bytes(H, W, N, cm_params(CM_RIGID));
+    return ENSLAM_OK;
+}
+
+int enslam_event_cmax_eval(const double* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t N, int32_t H, int32_t W,
+                           double fx, double fy, double cx, double cy, int32_t model, const double* theta_host, double t_ref,
+                           int32_t sign_votes, int32_t k, const double* taps_host, void* workspace, int64_t workspace_bytes,
+                           int64_t* iwe, double* blurred, double* stats, uint64_t* dropped, int32_t want_grad, void* stream) {
+    return cm_eval(false, t, x, y, p, N, H, W, fx, fy, cx, cy, model, nullptr, theta_host, t_ref, sign_votes, k, taps_host, workspace,
+                   workspace_bytes, iwe, blurred, stats, dropped, want_grad, stream);
+}
+
+int enslam_event_cmax_rigid_eval(const double* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t N, int32_t H,
+                                 int32_t W, double fx, double fy, double cx, double cy, const float* depth, const double* theta_host,
+                                 double t_ref, int32_t sign_votes, int32_t k, const double* taps_host, void* workspace,
+                                 int64_t workspace_bytes, int64_t* iwe, double* blurred, double* stats, uint64_t* dropped,
+                                 int32_t want_grad, void* stream) {
+    return cm_eval(true, t, x, y, p, N, H, W, fx, fy, cx, cy, 0, depth, theta_host, t_ref, sign_votes, k, taps_host, workspace,
+                   workspace_bytes, iwe, blurred, stats, dropped, want_grad, stream);
 }
 
 }  // extern "C"

@@ -139,6 +139,19 @@ class BaseDataset(torch.utils.data.Dataset):
         self.n_event = len(self._edges) - 1
         return True
 
+    def event_slice(self, index):
+        """(stream, t0, t1): the events of item `index` >= 1 as an event_stream.EventStream on the stream's device (the
+        dataset's, when that is a HIP device), and the two frame times that bound them: t0 < t <= t1, the bin rule of
+        `_init_event_stream`.  Needs data.event_stream and data.frame_stamps."""
+        if getattr(self, '_stream', None) is None:
+            raise ValueError("event_slice needs the time-stamped events of data.event_stream and data.frame_stamps")
+        if not 1 <= index < len(self._cuts):
+            raise IndexError(f"event_slice: item {index} has no event interval (1..{len(self._cuts) - 1})")
+        from . import event_stream as ES
+        i0, i1 = self._cuts[index - 1], self._cuts[index]
+        part = ES.EventStream(*(a[i0:i1] for a in self._stream.arrays()))
+        return part, float(self._edges[index - 1]), float(self._edges[index])
+
     def _event_image(self, index, order):
         """uint8 [H,W,3]: the decoded event png of item `index` >= 1, or the same array accumulated from the stream;
         order 'replica' = channels (0, -, +), 'rpg' = (+, -, 0)."""

@@ -1,18 +1,21 @@
 """Event motion compensation by contrast maximisation (Gallego, Rebecq, Scaramuzza, CVPR 2018): what the time stamps of a
 stream are for.  Every event is warped along a candidate motion to a reference time and voted into an image of warped events
 (IWE); the motion that makes the blurred IWE sharpest (largest variance) compensates the stream's motion blur and is an
-estimate of the image flow or of the camera's angular velocity from events alone.
+estimate of the image flow or of the camera's angular velocity from events alone -- or, with a depth image, of all six
+velocity components of the camera at metric scale ('rigid').
 
     warp_image       the IWE (float64) of a stream under a motion, and its blur
     contrast         (f, grad): the variance of the blurred IWE and its gradient in the motion
-    estimate_motion  maximises f from theta0: BFGS on the 2 or 3 parameters on the host, float64, deterministic
+    estimate_motion  maximises f from theta0: BFGS on the 2, 3 or 6 parameters on the host, float64, deterministic
     relative_rotation  the 4 x 4 camera-to-camera delta of an angular velocity over dt, in the project's camera convention
+    relative_motion  the same for a six-vector (w, v) of 'rigid': the exact SE(3) exponential; camera_velocity is its inverse
     cmax_numpy       the CPU route: the operations and the sum order of include/enslam_hip.h in numpy
 
-include/enslam_hip.h (enslam_event_cmax_eval) fixes the model and the order of every float64 operation; a stream on a HIP
+include/enslam_hip.h (enslam_event_cmax_eval, enslam_event_cmax_rigid_eval) fixes the model and the order of every float64 operation; a stream on a HIP
 device runs csrc/event_cmax.hip, one on the CPU runs cmax_numpy, and the two return the same bits.
 
-Motion models ('flow': theta = image flow in pixels / s; 'rotation': theta = angular velocity in rad / s) live in the PINHOLE
+Motion models ('flow': theta = image flow in pixels / s; 'rotation': theta = angular velocity in rad / s; 'rigid': theta =
+(angular velocity, linear velocity in depth units / s), with `depth` a float32 [H, W] image at the sensor's resolution) live in the PINHOLE
 frame of the calibration (x right, y down, z forward), which is what the kernel sees.  The project's cameras look down -z with
 y up (common.get_rays, synthetic.py): `to_pinhole` / `from_pinhole` flip y and z, and relative_rotation returns its delta in the
 project's convention.  The warp is first order in |omega| dt (a few hundredths of a radian)."""
@@ -23,9 +26,10 @@ import torch
 
 from ._lib import EnslamError
 
-MODELS = {'flow': 2, 'rotation': 3}
+MODELS = {'flow': 2, 'rotation': 3, 'rigid': 6}
 MAX_KSIZE = 31
 DROPPED = ('time', 'sensor', 'warp')
+DROPPED_RIGID = DROPPED + ('depth',)            # 'rigid' alone has the fourth counter
 _TWO32 = 4294967296.0
 
 
@@ -104,9 +108,24 @@ def _blur(img, taps):
     return out
 
 
-def cmax_numpy(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False, want_grad=True):
-    """The CPU route of enslam_event_cmax_eval on numpy arrays: (iwe int64 [H,W], blurred float64 [H,W], stats float64 [2 + P],
-    dropped int64 [3]) with every operation and every sum in the header's order."""
+def _host_depth(depth, model, H, W):
+    """the float32 [H, W] numpy image of a 'rigid' call on the CPU route (a CPU tensor or an array); None for the other models"""
+    if model != 'rigid':
+        if depth is not None:
+            raise EnslamError(f"event_cmax: model {model!r} takes no depth")
+        return None
+    if torch.is_tensor(depth) and depth.device.type == 'cpu':
+        depth = depth.detach().numpy()
+    if not isinstance(depth, np.ndarray) or depth.dtype != np.float32 or depth.shape != (H, W):
+        raise EnslamError(f"event_cmax: model 'rigid' takes depth, a float32 [{H},{W}] image on the stream's device (got "
+                          f"{(depth.dtype, tuple(depth.shape)) if hasattr(depth, 'shape') else type(depth).__name__})")
+    return depth
+
+
+def cmax_numpy(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False, want_grad=True, depth=None):
+    """The CPU route of enslam_event_cmax_eval and enslam_event_cmax_rigid_eval on numpy arrays: (iwe int64 [H,W], blurred
+    float64 [H,W], stats float64 [2 + P], dropped int64 [3], or [4] = (time, sensor, warp, depth) for 'rigid') with every
+    operation and every sum in the header's order."""
     if model not in MODELS:
         raise EnslamError(f"event_cmax: model must be one of {sorted(MODELS)} (got {model!r})")
     P = MODELS[model]
@@ -122,6 +141,7 @@ def cmax_numpy(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False,
         raise EnslamError(f"event_cmax: the blur takes an odd number of taps up to {MAX_KSIZE} (got {len(taps)})")
     if not all(math.isfinite(float(v)) for v in list(th) + [fx, fy, cx, cy, t_ref] + taps) or fx == 0 or fy == 0:
         raise EnslamError("event_cmax: theta, t_ref, the intrinsics and the taps must be finite, fx and fy not 0")
+    depth = _host_depth(depth, model, H, W)
     t = np.asarray(t, dtype=np.float64)
     N = t.size
     t_ref = np.float64(t_ref)
@@ -130,6 +150,7 @@ def cmax_numpy(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False,
     with np.errstate(all='ignore'):
         sensor = (xi >= W) | (yi >= H)
         timed = ~sensor & ~np.isfinite(t)
+        deep = np.zeros(N, dtype=bool)
         xd, yd = xi.astype(np.float64), yi.astype(np.float64)
         dt = t - t_ref
         zero = np.zeros(N, dtype=np.float64)
@@ -144,10 +165,17 @@ def cmax_numpy(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False,
             Bu, Bv = [uv, -pu, v], [pv, -uv, -u]
             du = (uv * th[0] - pu * th[1]) + v * th[2]
             dv = (pv * th[0] - uv * th[1]) - u * th[2]
+            if model == 'rigid':
+                z = depth.reshape(-1)[np.where(sensor, 0, yi * W + xi)]            # the event's own pixel, once it is checked
+                deep = ~sensor & ~timed & ~(np.isfinite(z) & (z > 0))
+                rho = np.float64(1.0) / z.astype(np.float64)
+                Bu, Bv = Bu + [-rho, zero, u * rho], Bv + [zero, -rho, v * rho]
+                du = du + rho * (u * th[5] - th[3])
+                dv = dv + rho * (v * th[5] - th[4])
         mx, my = -(dt * fx), -(dt * fy)
         xw, yw = xd + mx * du, yd + my * dv
-        ok = ~sensor & ~timed & (xw > -1.0) & (xw < np.float64(W)) & (yw > -1.0) & (yw < np.float64(H))
-        warp = ~sensor & ~timed & ~ok
+        ok = ~sensor & ~timed & ~deep & (xw > -1.0) & (xw < np.float64(W)) & (yw > -1.0) & (yw < np.float64(H))
+        warp = ~sensor & ~timed & ~deep & ~ok
         xw, yw = np.where(ok, xw, 0.0), np.where(ok, yw, 0.0)          # checked before any conversion
         fx0, fy0 = np.floor(xw), np.floor(yw)
         x0, y0 = fx0.astype(np.int64), fy0.astype(np.int64)
@@ -186,19 +214,21 @@ def cmax_numpy(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False,
             for k in range(P):
                 g = np.where(ok, s * (Gx * (mx * Bu[k]) + Gy * (my * Bv[k])), 0.0)
                 stats[2 + k] = scale * np.float64(tree_sum(g))
-    dropped = np.array([int(timed.sum()), int(sensor.sum()), int(warp.sum())], dtype=np.int64)
+    dropped = np.array([int(timed.sum()), int(sensor.sum()), int(warp.sum())] + ([int(deep.sum())] if model == 'rigid' else []),
+                       dtype=np.int64)
     return iwe, J, stats, dropped
 
 
-def _evaluate(stream, H, W, calib, model, theta, t_ref, taps, signed, want_grad, want_blurred=False):
+def _evaluate(stream, H, W, calib, model, theta, t_ref, taps, signed, want_grad, want_blurred=False, depth=None):
     """(iwe, blurred or None, stats, dropped) as CPU tensors / numpy, from the route of the stream's device"""
     cal = calib_tuple(calib)
     if stream.device.type == 'cuda':
         from . import functional as EF
         iwe, J, stats, dropped = EF.event_cmax_eval(*stream.arrays(), H, W, cal, model, theta, t_ref, taps, signed=signed,
-                                                    want_grad=want_grad, want_blurred=want_blurred)
+                                                    want_grad=want_grad, want_blurred=want_blurred, depth=depth)
         return iwe, J, stats.cpu().numpy(), dropped.cpu().numpy()
-    iwe, J, stats, dropped = cmax_numpy(*stream.numpy(), H, W, cal, model, theta, t_ref, taps, signed=signed, want_grad=want_grad)
+    iwe, J, stats, dropped = cmax_numpy(*stream.numpy(), H, W, cal, model, theta, t_ref, taps, signed=signed, want_grad=want_grad,
+                                        depth=depth)
     return torch.from_numpy(iwe), torch.from_numpy(J), stats, dropped
 
 
@@ -210,29 +240,41 @@ def default_t_ref(stream):
     return 0.5 * (float(t.min()) + float(t.max()))
 
 
-def warp_image(stream, calib, model, theta, H, W, t_ref=None, sigma=1.5, ksize=None, signed=False, with_dropped=False):
+def warp_image(stream, calib, model, theta, H, W, t_ref=None, sigma=1.5, ksize=None, signed=False, with_dropped=False,
+               depth=None):
     """(IWE float64 [H,W], blurred IWE float64 [H,W]) of the stream under the motion, on the stream's device; with_dropped also
-    the dict of drop counters.  theta = zeros gives the uncompensated event image."""
+    the dict of drop counters.  theta = zeros gives the uncompensated event image.  depth: the image of 'rigid'."""
     t_ref = default_t_ref(stream) if t_ref is None else float(t_ref)
-    iwe, J, _, dropped = _evaluate(stream, int(H), int(W), calib, model, theta, t_ref, blur_taps(sigma, ksize), signed, False, True)
+    iwe, J, _, dropped = _evaluate(stream, int(H), int(W), calib, model, theta, t_ref, blur_taps(sigma, ksize), signed, False, True,
+                                   depth=depth)
     img = iwe.to(torch.float64) * (1.0 / _TWO32)
-    return (img, J, dict(zip(DROPPED, (int(v) for v in dropped)))) if with_dropped else (img, J)
+    names = DROPPED_RIGID if model == 'rigid' else DROPPED
+    return (img, J, dict(zip(names, (int(v) for v in dropped)))) if with_dropped else (img, J)
 
 
-def contrast(stream, calib, model, theta, H, W, t_ref=None, sigma=1.5, ksize=None, signed=False):
+def contrast(stream, calib, model, theta, H, W, t_ref=None, sigma=1.5, ksize=None, signed=False, depth=None):
     """(f, grad): the variance of the blurred IWE and its gradient in theta (numpy float64 [P])"""
     t_ref = default_t_ref(stream) if t_ref is None else float(t_ref)
-    stats = _evaluate(stream, int(H), int(W), calib, model, theta, t_ref, blur_taps(sigma, ksize), signed, True)[2]
+    stats = _evaluate(stream, int(H), int(W), calib, model, theta, t_ref, blur_taps(sigma, ksize), signed, True, depth=depth)[2]
     return float(stats[1]), stats[2:].copy()
 
 
+def _largest_rho(depth):
+    """the largest finite inverse depth among the valid pixels (finite, > 0) of a depth image; 1.0 when there is none"""
+    d = torch.as_tensor(depth).detach().reshape(-1)
+    rho = 1.0 / d[torch.isfinite(d) & (d > 0)].double()
+    rho = rho[torch.isfinite(rho)]
+    return float(rho.max()) if rho.numel() else 1.0
+
+
 def estimate_motion(stream, calib, model, H, W, theta0=None, t_ref=None, sigma=1.5, ksize=None, signed=False, iters=40,
-                    tol_px=1e-3, max_halvings=20):
+                    tol_px=1e-3, max_halvings=20, depth=None):
     """Maximises the contrast over theta from theta0 (zeros): BFGS on the host in float64 with a backtracking line search
     whose every accepted step raises f (sufficient increase 1e-4 of the predicted one).  The first step, and every step after
     a reset of the curvature estimate, moves the fastest event of the window by one pixel.  Stops after `iters` accepted steps,
     when a step moves no event by more than tol_px pixels, or when the line search finds no increase along the gradient.
     Deterministic: the same (f, grad) give the same steps, so the device and the CPU route follow the same trace to the bit.
+    depth: the image of 'rigid' (float32 [H, W] on the stream's device).
     Returns dict(theta=[P], trace=[f after every accepted step, trace[0] = f(theta0)], thetas=[theta after every accepted step],
     evals=the number of evaluations, t_ref=...)."""
     if model not in MODELS:
@@ -245,6 +287,8 @@ def estimate_motion(stream, calib, model, H, W, theta0=None, t_ref=None, sigma=1
     theta = np.zeros(P) if theta0 is None else np.array([float(v) for v in theta0], dtype=np.float64)
     if theta.shape != (P,):
         raise EnslamError(f"event_cmax: model {model!r} takes {P} parameters (got {theta.shape})")
+    if (depth is None) != (model != 'rigid'):
+        raise EnslamError(f"event_cmax: depth is required for 'rigid' and refused for the other models (model {model!r})")
     tf = stream.t[torch.isfinite(stream.t)]
     half = max(float((tf - t_ref).abs().max()), 1e-12) if tf.numel() else 1.0
     # pixels an event at the window's end moves per unit of each parameter (rotation: at the image corner, first order)
@@ -254,11 +298,14 @@ def estimate_motion(stream, calib, model, H, W, theta0=None, t_ref=None, sigma=1
         um, vm = max(abs(cx), abs(W - 1 - cx)) / abs(fx), max(abs(cy), abs(H - 1 - cy)) / abs(fy)
         px_per = half * np.array([abs(fy) * (1 + vm * vm) + abs(fx) * um * vm, abs(fx) * (1 + um * um) + abs(fy) * um * vm,
                                   abs(fx) * vm + abs(fy) * um])
+        if model == 'rigid':                                # translation: the nearest valid pixel, as if it sat at the corner
+            rho = _largest_rho(depth)
+            px_per = np.concatenate([px_per, half * rho * np.array([abs(fx), abs(fy), abs(fx) * um + abs(fy) * vm])])
     evals = [0]
 
     def fg(th):
         evals[0] += 1
-        st = _evaluate(stream, H, W, (fx, fy, cx, cy), model, th.tolist(), t_ref, taps, signed, True)[2]
+        st = _evaluate(stream, H, W, (fx, fy, cx, cy), model, th.tolist(), t_ref, taps, signed, True, depth=depth)[2]
         return float(st[1]), st[2:].astype(np.float64)
 
     f, g = fg(theta)
@@ -336,3 +383,49 @@ def angular_velocity(c2w_a, c2w_b, dt):
     axis = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
     w = 0.5 * axis if ang < 1e-9 else axis * (ang / (2.0 * math.sin(ang)))
     return to_pinhole(w / float(dt))
+
+
+def _skew(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def relative_motion(theta, dt):
+    """The 4 x 4 delta D with c2w(t + dt) = c2w(t) @ D for a camera that moves with the constant body velocity theta = (w, v)
+    (rad / s and depth units / s in the PINHOLE frame, what estimate_motion('rigid') returns) for dt seconds, in the project's
+    camera convention: the flip of to_pinhole applies to w and to v alike.  The exact SE(3) exponential in float64; its
+    rotation block is relative_rotation(w, dt)'s."""
+    th = [float(x) for x in theta]
+    if len(th) != 6:
+        raise EnslamError(f"event_cmax: relative_motion takes (w_x, w_y, w_z, v_x, v_y, v_z) (got {len(th)} numbers)")
+    w = np.array(from_pinhole(th[:3]), dtype=np.float64) * float(dt)
+    v = np.array(from_pinhole(th[3:]), dtype=np.float64) * float(dt)
+    ang = float(np.linalg.norm(w))
+    Kx = _skew(w)
+    if ang < 1e-12:
+        V = np.eye(3) + 0.5 * Kx
+    else:
+        V = np.eye(3) + ((1.0 - math.cos(ang)) / (ang * ang)) * Kx + ((ang - math.sin(ang)) / (ang * ang * ang)) * (Kx @ Kx)
+    out = relative_rotation(th[:3], dt).numpy().copy()
+    out[:3, 3] = V @ v
+    return torch.from_numpy(out)
+
+
+def camera_velocity(c2w_a, c2w_b, dt):
+    """The inverse of relative_motion: the constant body velocity (w, v) in the pinhole frame that carries pose a into pose b
+    in dt seconds (the SE(3) logarithm of a^-1 b over dt) -- what a pair of ground-truth or tracked poses implies."""
+    def full(c):
+        m = np.eye(4)
+        m[:3] = np.asarray(torch.as_tensor(c).detach().double().cpu())[:3]
+        return m
+    A, B = full(c2w_a), full(c2w_b)
+    D = np.linalg.inv(A) @ B
+    w = np.array(from_pinhole(angular_velocity(A, B, 1.0)), dtype=np.float64)       # the rotation vector, project frame
+    ang = float(np.linalg.norm(w))
+    Kx = _skew(w)
+    if ang < 1e-6:
+        Vinv = np.eye(3) - 0.5 * Kx + (1.0 / 12.0) * (Kx @ Kx)
+    else:
+        half = 0.5 * ang
+        Vinv = np.eye(3) - 0.5 * Kx + ((1.0 - half * math.cos(half) / math.sin(half)) / (ang * ang)) * (Kx @ Kx)
+    v = Vinv @ D[:3, 3]
+    return [c / float(dt) for c in to_pinhole(w)] + [c / float(dt) for c in to_pinhole(v)]

@@ -3505,20 +3505,29 @@ def event_model_loss(cur, prev, gt, c_neg=0.2, c_pos=0.2, eps=1e-3, kernel_sizes
 # event motion compensation by contrast maximisation (csrc/event_cmax.hip; event_cmax.py is the caller)
 # ------------------------------------------------------------------------------------------------
 EVENT_CMAX_MODELS = {'flow': (0, 2), 'rotation': (1, 3)}            # name -> (ENSLAM_CMAX_*, P)
+EVENT_CMAX_RIGID = 6                                                # 'rigid': its own entry point, P = 6, four drop counters
 EVENT_CMAX_MAX_KSIZE = 31
 
 
-def event_cmax_eval(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False, want_grad=True, want_blurred=False):
+def event_cmax_eval(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False, want_grad=True, want_blurred=False,
+                    depth=None):
     """enslam_event_cmax_eval (enslam_hip.h) on a stream on one HIP device: t float64 [N], x, y uint16 [N], p uint8 [N].  calib =
     (fx, fy, cx, cy) pinhole, model 'flow' or 'rotation', theta its P host numbers, taps the k float64 taps of the blur (a
     host sequence).  Returns (iwe int64 [H,W], blurred float64 [H,W] or None, stats float64 [2 + P] = (mu, f, df/dtheta...),
-    dropped int64 [3] = (time, sensor, warp)) as device tensors; no synchronisation."""
+    dropped int64 [3] = (time, sensor, warp)) as device tensors; no synchronisation.
+    model 'rigid' is enslam_event_cmax_rigid_eval: theta = (w, v), P = 6, depth a contiguous float32 [H,W] tensor on the
+    stream's device (required; refused for the other models), dropped int64 [4] = (time, sensor, warp, depth)."""
     what = "event_cmax_eval"
     _event_arrays(what, t, x, y, p)
     H, W = _event_sensor(what, H, W)
-    if model not in EVENT_CMAX_MODELS:
-        raise L.EnslamError(f"{what}: model must be one of {sorted(EVENT_CMAX_MODELS)} (got {model!r})")
-    code, P = EVENT_CMAX_MODELS[model]
+    rigid = model == 'rigid'
+    if not rigid and model not in EVENT_CMAX_MODELS:
+        raise L.EnslamError(f"{what}: model must be one of {sorted(EVENT_CMAX_MODELS) + ['rigid']} (got {model!r})")
+    if rigid:
+        _event_plane(what, 'depth', depth, torch.float32, H, W, t.device)
+    elif depth is not None:
+        raise L.EnslamError(f"{what}: model {model!r} takes no depth")
+    code, P = (None, EVENT_CMAX_RIGID) if rigid else EVENT_CMAX_MODELS[model]
     import math
     th = [float(v) for v in theta]
     cal = [float(v) for v in calib]
@@ -3533,13 +3542,23 @@ def event_cmax_eval(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=F
     N, dev = int(t.shape[0]), t.device
     lib = L.lib()
     nbytes = ctypes.c_int64(0)
-    L.check(lib.enslam_event_cmax_workspace(H, W, N, P, ctypes.byref(nbytes)), "enslam_event_cmax_workspace")
+    if rigid:
+        L.check(lib.enslam_event_cmax_rigid_workspace(H, W, N, ctypes.byref(nbytes)), "enslam_event_cmax_rigid_workspace")
+    else:
+        L.check(lib.enslam_event_cmax_workspace(H, W, N, P, ctypes.byref(nbytes)), "enslam_event_cmax_workspace")
     with torch.cuda.device(dev):
         ws = torch.empty(max(nbytes.value // 8, 1), dtype=torch.float64, device=dev)
         iwe = torch.empty((H, W), dtype=torch.int64, device=dev)
         blurred = torch.empty((H, W), dtype=torch.float64, device=dev) if want_blurred else None
         stats = torch.empty(2 + P, dtype=torch.float64, device=dev)
-        dropped = torch.empty(3, dtype=torch.int64, device=dev)
+        dropped = torch.empty(4 if rigid else 3, dtype=torch.int64, device=dev)
+        if rigid:
+            L.check(lib.enslam_event_cmax_rigid_eval(_ptr(t), _ptr(x), _ptr(y), _ptr(p), N, H, W, cal[0], cal[1], cal[2], cal[3],
+                                                     _ptr(depth), (ctypes.c_double * P)(*th), float(t_ref), 1 if signed else 0, k,
+                                                     (ctypes.c_double * k)(*tp), _ptr(ws), ws.numel() * 8, _ptr(iwe), _ptr(blurred),
+                                                     _ptr(stats), _ptr(dropped), 1 if want_grad else 0, _stream()),
+                    "enslam_event_cmax_rigid_eval")
+            return iwe, blurred, stats, dropped
         L.check(lib.enslam_event_cmax_eval(_ptr(t), _ptr(x), _ptr(y), _ptr(p), N, H, W, cal[0], cal[1], cal[2], cal[3], code,
                                            (ctypes.c_double * P)(*th), float(t_ref), 1 if signed else 0, k,
                                            (ctypes.c_double * k)(*tp), _ptr(ws), ws.numel() * 8, _ptr(iwe), _ptr(blurred),

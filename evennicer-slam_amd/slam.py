@@ -34,6 +34,15 @@ RGB-D: 'measured' (the reference: that frame's depth image, which a sensor that 
 'forecast' and 'none' the colour and depth images of a frame without RGB-D are dropped as soon as the dataset has handed them
 over: tracker, mapper, keyframes and figures never see them.
 
+THE POSE PRIOR.  `tracking.motion_prior` says where the camera iterations of a frame start: 'const_speed' (the default, the
+reference's constant-speed pose) or 'cmax' (opt-in): the six-component camera velocity that maximises the contrast of the
+frame interval's events (event_cmax.estimate_motion('rigid')) under the last measured depth image warped into the previous
+pose, composed onto that pose (`SLAM._cmax_prior`).  It needs `data.event_stream` and `data.frame_stamps` on an uncropped
+sensor; `tracking.cmax_min_events` (500) and `tracking.cmax_iters` (10 accepted steps at most) bound it.  A frame falls back to
+the constant-speed pose, counted in `motion_prior_stats`, with too few events, without a depth image yet, with a result that
+is not finite and with a contrast that did not rise above f(theta0).  Measured on the analytic room the prior does not
+help -- the six-parameter contrast rises without bound along v_z and the estimate follows it -- so the default stays 'const_speed'.
+
 Mesh extraction is opt-in: `SLAM.get_mesh` (or `run(mesh_file=...)`) runs `mesher.Mesher.get_mesh` on the run's keyframes and
 poses.  The per-iteration figures of the reference's Visualizer are opt-in too: `SLAM(vis=True)` builds one
 `frame_vis.Visualizer` for the tracker (`tracking.vis_freq` / `vis_inside_freq`, folder `tracking_vis`) and one for the mapper
@@ -59,6 +68,7 @@ from .tracker import CameraParameter, TrackerIteration, camera_learning_rates
 MAP_KEYS = ('grid_middle', 'grid_fine', 'grid_color')
 SCHEDULES = ('dense', 'reference')
 DEPTH_ON_EVENT_FRAMES = ('measured', 'forecast', 'none')
+MOTION_PRIORS = ('const_speed', 'cmax')
 
 
 class FrameStep(typing.NamedTuple):
@@ -192,6 +202,20 @@ class SLAM:
         self.forecast_radius = float(e.get('forecast_radius', 1.0))
         self.forecast_fill = bool(e.get('forecast_fill', True))
         self._last_rgbd = None                              # (frame index, its depth image) of the last frame with RGB-D
+        tr = cfg['tracking']
+        self.motion_prior = tr.get('motion_prior', 'const_speed')
+        if self.motion_prior not in MOTION_PRIORS:
+            raise ValueError(f"tracking.motion_prior must be one of {MOTION_PRIORS} (got {self.motion_prior!r})")
+        self.cmax_min_events, self.cmax_iters = int(tr.get('cmax_min_events', 500)), int(tr.get('cmax_iters', 10))
+        # frames whose initial pose came from the events, the fallbacks by cause, and the seconds the prior took
+        self.motion_prior_stats = dict(cmax=0, few_events=0, no_depth=0, not_finite=0, no_rise=0, seconds=0.0)
+        if self.motion_prior == 'cmax':
+            if getattr(dataset, '_stream', None) is None:
+                raise ValueError("tracking.motion_prior = 'cmax' needs the time-stamped events of data.event_stream and "
+                                 "data.frame_stamps")
+            if cfg['cam']['crop_edge'] != 0 or cfg['cam'].get('crop_size') is not None:
+                raise ValueError("tracking.motion_prior = 'cmax' needs an uncropped sensor (cam.crop_edge 0, no cam.crop_size): "
+                                 "the stream's pixels are the raw frame's")
         self._gtracks = {}                                  # captured camera iterations (_track_graphed)
         self.keyframe_dict, self.keyframe_list = [], []
         self.timing = dict(track=0.0, map=0.0)
@@ -228,6 +252,9 @@ class SLAM:
             est = delta @ pre
         else:
             est = pre
+        prior = 'const_speed'
+        if self.motion_prior == 'cmax':
+            est, prior = self._cmax_prior(idx, est)
         # (predictor 'model': the contrast-threshold model predicts the events, no network is needed)
         has_predictor = self.event_net is not None or self.cfg['event'].get('predictor', 'net') == 'model'
         use_event = has_predictor and self.cfg['event'].get('activate_events', False)
@@ -267,9 +294,51 @@ class SLAM:
         c2w[:3] = get_camera_from_tensor(best)
         if self.verbose:
             gt = self.gt_c2w_list[idx][:3, 3].to(self.device)
-            print(f'frame {idx}: tracking loss {first_loss} -> {best_loss}; translation error init '
+            print(f'frame {idx}: tracking loss {first_loss} -> {best_loss}; translation error init ({prior}) '
                   f'{float((est[:3, 3] - gt).norm()):.4f} -> {float((c2w[:3, 3] - gt).norm()):.4f} m', flush=True)
         return c2w
+
+    def _cmax_prior(self, idx, fallback):
+        """(est, what made it) of frame idx under tracking.motion_prior = 'cmax': the previous estimated pose composed with
+        the camera motion that the events of (stamp[idx-1], stamp[idx]] imply.  The six velocity components maximise the
+        contrast of those events (event_cmax.estimate_motion('rigid'), from the velocity of the last two estimated poses) under
+        the depth image of the last frame with RGB-D warped into the previous pose at the sensor's full size.  `fallback`, the
+        constant-speed pose, is returned -- and the cause counted in motion_prior_stats -- when the interval has fewer than
+        tracking.cmax_min_events events, when no depth image has been kept yet, when the result is not finite and when the
+        contrast did not rise above f(theta0)."""
+        from . import event_cmax as CM
+        stats, t_start = self.motion_prior_stats, time.perf_counter()
+
+        def back(cause):
+            stats[cause] += 1
+            stats['seconds'] += time.perf_counter() - t_start
+            return fallback, f'const_speed, cmax fell back: {cause}'
+        stream, t0, t1 = self.dataset.event_slice(idx)
+        if len(stream) < self.cmax_min_events:
+            return back('few_events')
+        if self._last_rgbd is None:
+            return back('no_depth')
+        pre = self.estimate_c2w_list[idx - 1].double()
+        theta0 = [0.0] * 6
+        if idx >= 2:
+            ta = self.dataset.event_slice(idx - 1)[1]
+            if t0 > ta:
+                theta0 = CM.camera_velocity(self.estimate_c2w_list[idx - 2], pre, t0 - ta)
+        src, depth = self._last_rgbd
+        M = EF.relative_camera_matrix(self.estimate_c2w_list[src], pre)
+        depth = EF.depth_forecast(depth.float().contiguous(), self.cam, M, (self.H, self.W), radius=self.forecast_radius, z_near=0.0,
+                                  fill=self.forecast_fill).to(stream.device)
+        res = CM.estimate_motion(stream, (self.fx, self.fy, self.cx, self.cy), 'rigid', self.H, self.W, theta0=theta0, t_ref=t0,
+                                 iters=self.cmax_iters, depth=depth)
+        self.motion_prior_last = res
+        if not (np.all(np.isfinite(res['theta'])) and np.isfinite(res['trace'][-1])):
+            return back('not_finite')
+        if not res['trace'][-1] > res['trace'][0]:
+            return back('no_rise')
+        est = (pre @ CM.relative_motion(res['theta'], t1 - t0)).float().to(self.device)
+        stats['cmax'] += 1
+        stats['seconds'] += time.perf_counter() - t_start
+        return est, 'cmax'
 
     def _forecast_depth(self, est):
         """Guidance depth of a frame without RGB-D at the event resolution: the depth image of the last frame that had one, at that
@@ -504,11 +573,13 @@ class SLAM:
                 pre_color = gt_color.float()
             elif step.reset:                                                 # Tracker.py:461-466
                 pre_color, integrated = gt_color.float(), None
-            if not dense and step.rgbd and self.depth_mode == 'forecast':
+            if step.rgbd and ((not dense and self.depth_mode == 'forecast') or (self.motion_prior == 'cmax' and gt_depth is not None)):
                 self._last_rgbd = (idx, gt_depth)
         self.last_idx = n - 1
         ckpt = self.logger.log(n - 1, self.keyframe_dict, self.keyframe_list, selected_keyframes=None)
         out = dict(ckpt=ckpt, frames=n, fps=n / max(self.timing['track'] + self.timing['map'], 1e-9), timing=dict(self.timing))
+        if self.motion_prior == 'cmax':
+            out['motion_prior'] = dict(self.motion_prior_stats)
         if mesh_file is not None:
             out['mesh'] = self.get_mesh(mesh_file)
         return out

@@ -1379,8 +1379,9 @@ int enslam_event_model_loss(const float *cur, const float *prev, const float *gt
  * the same tree; what is then left (one value per 65536 elements) added in ascending order from 0.0.  No float atomics.
  *
  * Outputs: iwe; blurred float64 [H,W] = J, or NULL; stats float64 [2 + P] = (mu, f, df/dtheta..., the latter 0.0 without
- * want_grad); dropped.  workspace: enslam_event_cmax_workspace bytes, 8-byte aligned.  A fixed set of launches and memsets on
- * the stream, no host synchronisation: safe inside a stream capture.  Inputs are only read.
+ * want_grad); dropped.  workspace: enslam_event_cmax_workspace bytes, 8-byte aligned.  A fixed set of launches on the stream
+ * (the outputs are zeroed by a kernel, not by memsets), no host synchronisation: safe inside a stream capture, replayed any
+ * number of times.  Inputs are only read.
  * ENSLAM_EINVAL without a launch: a NULL theta_host, taps_host, workspace, iwe, stats or dropped; a NULL stream array with
  * N > 0; N < 0; H or W <= 0; a non-finite theta, t_ref or intrinsic; fx or fy equal to 0; an unknown model; k even or <= 0
  * (checked before its size); a non-finite tap; a workspace too small or misaligned; iwe, blurred, stats or dropped not 8-byte
@@ -1398,6 +1399,41 @@ int enslam_event_cmax_eval(const double *t, const uint16_t *x, const uint16_t *y
                            double t_ref, int32_t sign_votes, int32_t k, const double *taps_host, void *workspace,
                            int64_t workspace_bytes, int64_t *iwe, double *blurred, double *stats, uint64_t *dropped,
                            int32_t want_grad, void *stream);
+
+/* The rigid-motion model of the same objective: the six velocity components of a camera that moves through a scene of known
+ * depth, at metric scale.  Its own entry points, because the pair above refuses a third model and P outside 2..3 and keeps
+ * doing so; both *_eval entries run one validating body and one set of kernels (csrc/event_cmax.hip).
+ *
+ * The arguments are enslam_event_cmax_eval's without `model`, plus: depth, a device float32 [H,W] image in the sensor's own
+ * resolution (only read); theta_host, a HOST float64 [6] = (w_x, w_y, w_z, v_x, v_y, v_z): the angular velocity in rad / s,
+ * then the linear velocity in depth units / s, both in the pinhole frame of ROTATION (x right, y down, z forward); dropped,
+ * uint64 [4].  ALL arithmetic is float64, every operation on its own, in exactly this order; u, v, uv, pu, pv, dt, mx, my are
+ * ROTATION's:
+ *     z   = depth[y * W + x]                (the event's own, already checked, pixel: no interpolation)
+ *     rho = 1 / (float64)z
+ *     Bu  = (uv, -pu,  v, -rho, 0.0, u * rho)
+ *     Bv  = (pv, -uv, -u, 0.0, -rho, v * rho)
+ *     du  = ((uv * w_x - pu * w_y) + v * w_z) + rho * (u * v_z - v_x)
+ *     dv  = ((pv * w_x - uv * w_y) - u * w_z) + rho * (v * v_z - v_y)
+ *     x'  = xd + mx * du                    y'  = yd + my * dv
+ * the motion field (Longuet-Higgins and Prazdny) of a camera whose pose obeys c2w(t + dt) = c2w(t) exp(dt xi), to first order
+ * in |xi| dt; an event's depth is held constant over the window.
+ * Checks, in this order, each with its counter: x >= W or y >= H -> dropped[ENSLAM_CMAX_DROP_SENSOR]; t not finite ->
+ * dropped[ENSLAM_CMAX_DROP_TIME]; z not finite or z <= 0 -> dropped[ENSLAM_CMAX_DROP_DEPTH] (the depth is read only after the
+ * sensor check: no address comes from an unchecked value); then the float64 range check on x', y' ->
+ * dropped[ENSLAM_CMAX_DROP_WARP] (a subnormal float32 z is a valid depth with rho up to 2^149: its x', far outside the
+ * image, infinite or NaN, fails here).
+ * The vote, the blur, mu, f, D, Gx, Gy, g_k (k = 0..5), SUM, the outputs and the capture safety are the ones above; stats is
+ * float64 [2 + 6]; the workspace is the formula above with P = 6 (enslam_event_cmax_rigid_workspace).
+ * The refusals are the ones above (without the model), plus ENSLAM_EINVAL for a NULL depth with N > 0 and for a non-finite
+ * component of the six-element theta. */
+#define ENSLAM_CMAX_DROP_DEPTH 3
+int enslam_event_cmax_rigid_workspace(int32_t H, int32_t W, int64_t N, int64_t *bytes_host);
+int enslam_event_cmax_rigid_eval(const double *t, const uint16_t *x, const uint16_t *y, const uint8_t *p, int64_t N, int32_t H,
+                                 int32_t W, double fx, double fy, double cx, double cy, const float *depth,
+                                 const double *theta_host, double t_ref, int32_t sign_votes, int32_t k,
+                                 const double *taps_host, void *workspace, int64_t workspace_bytes, int64_t *iwe,
+                                 double *blurred, double *stats, uint64_t *dropped, int32_t want_grad, void *stream);
 
 /* Depth forecast (csrc/depth_forecast.hip, functional.depth_forecast): a measured depth image forward-warped into another
  * camera pose and image size by a z-buffered point splat -- the guidance depth of the tracker's reduced-resolution render on a

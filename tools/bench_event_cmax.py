@@ -11,6 +11,9 @@ The device route and the numpy route ALTERNATE in one process: `--repeat` (10) t
 [min - max] each -- the device call by device events with a synchronise behind it, the host by a wall clock.
 `device_below_numpy` says whether the slowest device run is below the fastest numpy run; `equal_to_numpy` whether the two
 routes return the same bits (image, counters, mu, f, gradient).
+Every shape and order also has a `<shape>_<order>_rigid` row: one evaluation with gradient of the rigid-motion model at
+(omega, v) = (OMEGA, (0.1, -0.05, 0.2) units / s) under a seeded depth image in [0.5, 4] with 5 % invalid pixels, timed in the
+same alternation, with the same two fields.
 
 The vote atomics: `vote_ms` is the median of an evaluation without gradient minus the median of the same evaluation of an
 EMPTY stream on the same sensor (the same memsets, blur and sums; only the vote launch differs), `vote_atomics` the number of
@@ -35,6 +38,7 @@ import torch  # noqa: E402
 
 NOISE = dict(refractory=1e-3, leak_rate=30.0, shot_rate=30.0, seed=1)
 OMEGA = [0.2, -0.3, 0.5]
+VELOCITY = [0.1, -0.05, 0.2]
 STAMPS = (0.0, 0.04)
 SIGMA = 1.5
 
@@ -49,6 +53,14 @@ def simulator_stream(H, W, device):
     a, b = a.astype(np.uint8), np.clip(a + step, 0, 255).astype(np.uint8)
     sim = EventSimulator(H, W, device=device, noise=EventNoise(**NOISE)).reset(a)
     return sim.step_images(a, b, stamps=STAMPS)[1]
+
+
+def depth_image(H, W):
+    """float32 [H, W] in [0.5, 4], every twentieth pixel or so invalid (0)"""
+    rng = np.random.default_rng(2)
+    d = rng.uniform(0.5, 4.0, (H, W)).astype(np.float32)
+    d[rng.random((H, W)) < 0.05] = 0.0
+    return d
 
 
 def calib_of(H, W):
@@ -93,11 +105,12 @@ def main():
     taps = M.blur_taps(SIGMA)
     t_ref = 0.5 * (STAMPS[0] + STAMPS[1])
 
-    def device_ms(stream, H, W, cal, want_grad=True):
+    def device_ms(stream, H, W, cal, want_grad=True, depth=None):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        model, theta = ('rotation', OMEGA) if depth is None else ('rigid', OMEGA + VELOCITY)
         torch.cuda.synchronize()
         a.record()
-        out = EF.event_cmax_eval(*stream.arrays(), H, W, cal, 'rotation', OMEGA, t_ref, taps, want_grad=want_grad)
+        out = EF.event_cmax_eval(*stream.arrays(), H, W, cal, model, theta, t_ref, taps, want_grad=want_grad, depth=depth)
         b.record()
         torch.cuda.synchronize()
         return a.elapsed_time(b), out
@@ -108,10 +121,12 @@ def main():
         emitted = simulator_stream(H, W, dev)
         streams = dict(pixel_major=emitted, time=emitted.time_sorted())
         empty = EventStream.empty(dev)
+        depth_host = depth_image(H, W)
+        depth = torch.from_numpy(depth_host).to(dev)
         for order in names:
             stream = streams[order]
             host = stream.numpy()
-            total, nograd, idle, host_ms = [], [], [], []
+            total, nograd, idle, host_ms, rigid, rigid_host_ms = [], [], [], [], [], []
             for r in range(args.repeat + 1):                 # the first pair warms up
                 ms, out = device_ms(stream, H, W, cal)
                 ms_ng = device_ms(stream, H, W, cal, want_grad=False)[0]
@@ -125,6 +140,14 @@ def main():
                     ref = M.cmax_numpy(*host, H, W, cal, 'rotation', OMEGA, t_ref, taps)
                     if r:
                         host_ms.append((time.perf_counter() - t0) * 1e3)
+                ms_r, out_r = device_ms(stream, H, W, cal, depth=depth)
+                if r:
+                    rigid.append(ms_r)
+                if not args.no_numpy:
+                    t0 = time.perf_counter()
+                    ref_r = M.cmax_numpy(*host, H, W, cal, 'rigid', OMEGA + VELOCITY, t_ref, taps, depth=depth_host)
+                    if r:
+                        rigid_host_ms.append((time.perf_counter() - t0) * 1e3)
             n_atomics = vote_atomics(stream, H, W, cal, OMEGA, t_ref)
             vote_ms = float(np.median(nograd) - np.median(idle))
             row = dict(events=len(stream), device_ms_med_min_max=span(total), device_no_grad_ms_med_min_max=span(nograd),
@@ -137,6 +160,14 @@ def main():
                 row.update(numpy_ms_med_min_max=span(host_ms), device_below_numpy='yes' if max(total) < min(host_ms) else 'no',
                            equal_to_numpy=bool(same))
             rows[f'{shape}_{order}'] = row
+            row = dict(events=len(stream), device_ms_med_min_max=span(rigid), dropped=dict(zip(M.DROPPED_RIGID, out_r[3].cpu().tolist())),
+                       f=float(out_r[2][1]))
+            if not args.no_numpy:
+                same = (np.array_equal(out_r[0].cpu().numpy(), ref_r[0]) and np.array_equal(out_r[3].cpu().numpy(), ref_r[3])
+                        and np.array_equal(out_r[2].cpu().numpy().view(np.int64), ref_r[2].view(np.int64)))
+                row.update(numpy_ms_med_min_max=span(rigid_host_ms), device_below_numpy='yes' if max(rigid) < min(rigid_host_ms) else 'no',
+                           equal_to_numpy=bool(same))
+            rows[f'{shape}_{order}_rigid'] = row
             print(f'{shape}_{order}: done', file=sys.stderr, flush=True)
         # a whole estimate from zero
         stream = streams[names[-1]]
@@ -157,7 +188,7 @@ def main():
             est.update(numpy_ms_once=(time.perf_counter() - t0) * 1e3, same_trace_as_numpy=bool(ref['thetas'] == res['thetas']))
         estimates[shape] = est
         print(f'{shape}_estimate: done', file=sys.stderr, flush=True)
-    print(json.dumps(dict(repeat=args.repeat, estimate_repeat=args.estimate_repeat, model='rotation', omega=OMEGA, sigma=SIGMA,
+    print(json.dumps(dict(repeat=args.repeat, estimate_repeat=args.estimate_repeat, model='rotation', omega=OMEGA, rigid_velocity=VELOCITY, sigma=SIGMA,
                           ksize=len(taps), stamps=STAMPS, noise=NOISE, rows=rows, estimate=estimates,
                           device=torch.cuda.get_device_name(0))))
 

@@ -1,16 +1,18 @@
 """Motion compensation of a time-stamped event stream by contrast maximisation (evennicer_slam_amd/event_cmax.py): per frame
-interval the image flow or the camera's angular velocity that makes the image of warped events sharpest.
+interval the image flow, the camera's angular velocity or, with a depth image, its six velocity components that make the image
+of warped events sharpest.
 
     python tools/event_motion.py --stream EVENTS --size H W --calib FX FY CX CY (--stamps FILE | --fps F)
-                                 [--model rotation|flow] [--gap 1] [--sigma 1.5] [--ksize K] [--iters 40] [--signed]
+                                 [--model rotation|flow|rigid] [--depth PATH [--depth-scale S]] [--gap 1] [--sigma 1.5] [--ksize K] [--iters 40] [--signed]
                                  [--max-intervals N] [--out DIR [--images]] [--device cuda:0]
-    python tools/event_motion.py --demo N [--yaw-deg 8.0] [--step 0.002] [--device cuda:0] [--out DIR [--images]]
+    python tools/event_motion.py --demo N [--model rigid] [--yaw-deg 8.0] [--step 0.002] [--device cuda:0] [--out DIR [--images]]
 
 EVENTS is a `.npz` of event_stream.EventStream.save or the text layout `t x y p`.  The frame times come from --stamps (first
 field per non-comment line) or are i / --fps from the first event's time to the last; every --gap-th frame bounds an interval,
 and an event at a frame's own time belongs to the interval that ends there (the bin rule of event_stream.py).  The reference
 time of an interval is its middle.  'rotation' is in rad / s in the pinhole frame of the calibration (x right, y down, z
-forward); 'flow' in pixels / s.
+forward); 'flow' in pixels / s; 'rigid' is (angular velocity, linear velocity in depth units / s) in the same frame and needs
+--depth PATH: one `.npy` image or one 16-bit PNG divided by --depth-scale (1), at the sensor's size, used for every interval.
 
 --out DIR writes theta.json (per interval: the times, the number of events, theta, the contrast before and after, the number
 of evaluations) and with --images the uncompensated and the compensated event image of every interval as PNGs (each scaled by
@@ -18,7 +20,9 @@ its own maximum).
 
 --demo N runs the analytic room of synthetic.py under EventSimulator.step_scene(..., stamps=...) for N frames at 30 Hz and
 prints the estimated angular velocities beside the ones implied by the ground-truth poses (event_cmax.angular_velocity).  The
-camera also translates there, which a pure rotation cannot explain: the comparison is a record, not a bar.
+camera also translates there, which a pure rotation cannot explain: the comparison is a record, not a bar.  --demo N --model
+rigid estimates all six components under the room's own depth frame at the start of each interval and prints them beside
+event_cmax.camera_velocity of the ground-truth poses.
 
 --device cpu runs the numpy route of the same model.  Prints one JSON line."""
 import argparse
@@ -46,9 +50,26 @@ def intervals_of(stream, edges):
         yield float(a), float(b), stream.take(keep.nonzero().reshape(-1))
 
 
-def estimate(stream, a, b, cal, H, W, args, out_dir=None, index=0):
+def read_depth(path, scale, H, W):
+    """float32 [H, W] from a `.npy` file or a 16-bit PNG divided by scale"""
+    import numpy as np
+    if str(path).endswith('.npy'):
+        d = np.load(path)
+    else:
+        from PIL import Image
+        with Image.open(path) as im:
+            d = np.asarray(im)
+    d = np.ascontiguousarray(d, dtype=np.float32) / np.float32(scale)
+    if d.shape != (H, W):
+        raise SystemExit(f"{path}: the depth image is {d.shape}, the sensor {H} x {W}")
+    return d
+
+
+def estimate(stream, a, b, cal, H, W, args, out_dir=None, index=0, depth=None):
     from evennicer_slam_amd import event_cmax as M
     kw = dict(H=H, W=W, t_ref=0.5 * (a + b), sigma=args.sigma, ksize=args.ksize, signed=args.signed)
+    if depth is not None:
+        kw['depth'] = depth
     res = M.estimate_motion(stream, cal, args.model, iters=args.iters, **kw)
     row = dict(t_a=a, t_b=b, events=len(stream), theta=res['theta'], contrast_before=res['trace'][0], contrast_after=res['trace'][-1],
                evaluations=res['evals'], steps=len(res['trace']) - 1)
@@ -67,7 +88,9 @@ def main(argv=None):
     ap.add_argument('--stamps', default=None)
     ap.add_argument('--fps', type=float, default=None)
     ap.add_argument('--gap', type=int, default=1)
-    ap.add_argument('--model', choices=('rotation', 'flow'), default='rotation')
+    ap.add_argument('--model', choices=('rotation', 'flow', 'rigid'), default='rotation', metavar='{rotation,flow}|rigid')
+    ap.add_argument('--depth', default=None)
+    ap.add_argument('--depth-scale', type=float, default=1.0)
     ap.add_argument('--sigma', type=float, default=1.5)
     ap.add_argument('--ksize', type=int, default=None)
     ap.add_argument('--iters', type=int, default=40)
@@ -84,6 +107,10 @@ def main(argv=None):
         ap.error("give either --stream EVENTS or --demo N")
     if args.images and args.out is None:
         ap.error("--images needs --out DIR")
+    if args.demo is None and (args.model == 'rigid') != (args.depth is not None):
+        ap.error("--model rigid and --depth PATH come together")
+    if args.demo is not None and args.depth is not None:
+        ap.error("--demo takes its depth from the room")
 
     import numpy as np
     from evennicer_slam_amd import event_cmax as M
@@ -99,7 +126,8 @@ def main(argv=None):
         from evennicer_slam_amd.event_sim import EventSimulator
         from evennicer_slam_amd.scene import scene_bound
         from evennicer_slam_amd.synthetic import BoxRoom, trajectory
-        args.model = out['model'] = 'rotation'
+        if args.model != 'rigid':
+            args.model = out['model'] = 'rotation'
         cam = DEMO_CAM
         H, W = cam['H'], cam['W']
         room = BoxRoom.for_bound(scene_bound([[-1.0, 1.1], [-0.9, 0.8], [-0.7, 0.6]], 1.0, 0.32), margin=0.12, seed=1)
@@ -109,8 +137,13 @@ def main(argv=None):
         cal = M.calib_tuple(cam)
         for i in range(args.demo - 1):
             stream = sim.step_scene(room, poses[i], poses[i + 1], cam, stamps=(times[i], times[i + 1]))[1]
-            row = estimate(stream, times[i], times[i + 1], cal, H, W, args, args.out, i)
-            row['omega_from_poses'] = M.angular_velocity(poses[i], poses[i + 1], times[i + 1] - times[i])
+            if args.model == 'rigid':
+                depth = room.render(poses[i], cam)[1].float().contiguous().to(stream.device)
+                row = estimate(stream, times[i], times[i + 1], cal, H, W, args, args.out, i, depth=depth)
+                row['velocity_from_poses'] = M.camera_velocity(poses[i], poses[i + 1], times[i + 1] - times[i])
+            else:
+                row = estimate(stream, times[i], times[i + 1], cal, H, W, args, args.out, i)
+                row['omega_from_poses'] = M.angular_velocity(poses[i], poses[i + 1], times[i + 1] - times[i])
             rows.append(row)
         out.update(demo=args.demo, yaw_deg=args.yaw_deg, step=args.step, sensor=f'{H}x{W}')
     else:
@@ -120,6 +153,10 @@ def main(argv=None):
             ap.error("give the frame times with either --stamps FILE or --fps F")
         H, W = args.size
         stream = load_stream(args.stream, device=args.device)
+        depth = None
+        if args.model == 'rigid':
+            import torch
+            depth = torch.from_numpy(read_depth(args.depth, args.depth_scale, H, W)).to(stream.device)
         if args.stamps is not None:
             times = read_stamps(args.stamps)
         else:
@@ -134,7 +171,7 @@ def main(argv=None):
         for i, (a, b, part) in enumerate(intervals_of(stream, edges)):
             if args.max_intervals is not None and i >= args.max_intervals:
                 break
-            rows.append(estimate(part, a, b, tuple(args.calib), H, W, args, args.out, i))
+            rows.append(estimate(part, a, b, tuple(args.calib), H, W, args, args.out, i, depth=depth))
         out.update(stream=args.stream, events=len(stream), sensor=f'{H}x{W}', gap=args.gap)
     out.update(intervals=len(rows), rows=rows)
     if args.out is not None:

@@ -4,7 +4,7 @@
                                     [--max-frames N] [--prepare host|device] [--prefit ITERS] [--device cuda:0]
                                     [--event-net PATH] [--net-backend hip|torch] [--event-predictor net|model] [--vis]
                                     [--schedule dense|reference] [--rgbd-every K]
-                                    [--depth-on-event-frames measured|forecast|none]
+                                    [--depth-on-event-frames measured|forecast|none] [--motion-prior const_speed|cmax]
 
 CONFIG may name parents with `inherit_from` (config.load_config); --default-config is the root under a chain that names
 none (the reference passes configs/nice_slam.yaml).  The reference's YAML files are not part of this repository: point at
@@ -17,7 +17,9 @@ model sets `event.predictor`: the event term from the contrast-threshold model (
 `event.c_neg`, `event.eps` of the configuration), which needs no network.  --schedule, --rgbd-every and
 --depth-on-event-frames override `event.schedule`, `event.rgbd_every_frame` and `event.depth_on_event_frames` (slam.py: 'dense' --
 the default, also for a configuration that sets rgbd_every_frame -- runs RGB-D on every frame; 'reference' is the reference
-tracker's sparse schedule).  Prints one JSON line: checkpoint path, frames, frames per second and the ATE."""
+tracker's sparse schedule).  --motion-prior overrides `tracking.motion_prior`: 'cmax' starts every frame from the camera motion
+its events imply (slam.py, THE POSE PRIOR; needs data.event_stream and data.frame_stamps) and adds the prior's counters to the
+line.  Prints one JSON line: checkpoint path, frames, frames per second and the ATE."""
 import argparse
 import copy
 import json
@@ -45,15 +47,18 @@ def add_schedule_arguments(ap):
     ap.add_argument('--schedule', choices=('dense', 'reference'), default=None)
     ap.add_argument('--rgbd-every', type=int, default=None)
     ap.add_argument('--depth-on-event-frames', choices=('measured', 'forecast', 'none'), default=None)
+    ap.add_argument('--motion-prior', choices=('const_speed', 'cmax'), default=None)
 
 
 def apply_schedule_arguments(cfg, args):
-    """--schedule, --rgbd-every and --depth-on-event-frames over cfg['event']."""
+    """--schedule, --rgbd-every and --depth-on-event-frames over cfg['event'], --motion-prior over cfg['tracking']."""
     ev = cfg.setdefault('event', {})
     for key, value in (('schedule', args.schedule), ('rgbd_every_frame', args.rgbd_every),
                        ('depth_on_event_frames', args.depth_on_event_frames)):
         if value is not None:
             ev[key] = value
+    if getattr(args, 'motion_prior', None) is not None:
+        cfg.setdefault('tracking', {})['motion_prior'] = args.motion_prior
     return cfg
 
 
@@ -108,7 +113,8 @@ def main(argv=None):
     ate = slam.evaluate(res['ckpt'])
     print(json.dumps(dict(ckpt=res['ckpt'], frames=res['frames'], fps=res['fps'], prepare=ds.prepare,
                           ate_rmse=float(ate['absolute_translational_error.rmse']),
-                          compared_pose_pairs=int(ate['compared_pose_pairs']))), flush=True)
+                          compared_pose_pairs=int(ate['compared_pose_pairs']),
+                          **({'motion_prior': res['motion_prior']} if 'motion_prior' in res else {}))), flush=True)
     return res
 
 

@@ -17,7 +17,9 @@ stages' vis_freq / vis_inside_freq); with --events simulate, [--refractory S] [-
 switch the simulator to the noisy sensor (event_sim.EventNoise; the frame times are i / 30 s, those of
 tools/simulate_events.py's default --fps); [--schedule dense|reference] [--rgbd-every K] [--depth-on-event-frames
 measured|forecast|none] set event.schedule, event.rgbd_every_frame and event.depth_on_event_frames (slam.py; the sparse RGB-D
-schedule) and [--no-events] keeps event.activate_events off with simulated events (the "events off" arm).  SEED (environment, default 0) seeds torch and numpy for each run."""
+schedule), [--motion-prior const_speed|cmax] sets tracking.motion_prior ('cmax' needs --events simulate: the sequence is then
+simulated with time stamps, 30 frames per second, and the stream and the stamps are written beside it as data.event_stream and
+data.frame_stamps; the result carries the prior's counters; CMAX_MIN_EVENTS in the environment sets tracking.cmax_min_events) and [--no-events] keeps event.activate_events off with simulated events (the "events off" arm).  SEED (environment, default 0) seeds torch and numpy for each run."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -61,7 +63,8 @@ def parse_args(args):
     opts = {}
     for flag, key in (('--events', 'events'), ('--event-net', 'event_net'), ('--net-backend', 'net_backend'), ('--vis', 'vis'),
                       ('--event-predictor', 'event_predictor'), ('--c-pos', 'c_pos'), ('--c-neg', 'c_neg'),
-                      ('--schedule', 'schedule'), ('--rgbd-every', 'rgbd_every'), ('--depth-on-event-frames', 'depth_on_event_frames')):
+                      ('--schedule', 'schedule'), ('--rgbd-every', 'rgbd_every'), ('--depth-on-event-frames', 'depth_on_event_frames'),
+                      ('--motion-prior', 'motion_prior')):
         if flag in args:
             k = args.index(flag)
             opts[key] = args[k + 1]
@@ -74,6 +77,10 @@ def parse_args(args):
         raise SystemExit("--schedule takes 'dense' or 'reference'")
     if opts.get('depth_on_event_frames') not in (None, 'measured', 'forecast', 'none'):
         raise SystemExit("--depth-on-event-frames takes 'measured', 'forecast' or 'none'")
+    if opts.get('motion_prior') not in (None, 'const_speed', 'cmax'):
+        raise SystemExit("--motion-prior takes 'const_speed' or 'cmax'")
+    if opts.get('motion_prior') == 'cmax' and opts.get('events') != 'simulate':
+        raise SystemExit("--motion-prior cmax needs --events simulate")
     if 'rgbd_every' in opts:
         opts['rgbd_every'] = int(opts['rgbd_every'])
     noise = {}
@@ -134,7 +141,7 @@ def mesh_metrics(slam, path, n_gt=200000, tsdf=False):
 
 def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=None, event_net=None, net_backend=None, vis=None,
         noise=None, event_predictor=None, c_pos=None, c_neg=None, schedule=None, rgbd_every=None, depth_on_event_frames=None,
-        no_events=False):
+        no_events=False, motion_prior=None):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -145,10 +152,22 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=Non
             sim = EventSimulator(cam['H'], cam['W'], c_pos=c, c_neg=c, device=DEV, noise=noise)
         elif noise is not None:
             raise SystemExit("the noise options need --events simulate")
+        stamps = [i / 30.0 for i in range(n)]
+        streams = [] if motion_prior == 'cmax' else None
         (inp, evf), poses = write_demo_sequence(os.path.join(tmp, 'data'), n, cam, step=float(os.environ.get('STEP', 0.012)), yaw_deg=float(os.environ.get('YAW', 0.5)),
-                                                events=events, sim=sim,
-                                                stamps=None if noise is None else [i / 30.0 for i in range(n)])
+                                                events=events, sim=sim, streams=streams,
+                                                stamps=None if (noise is None and streams is None) else stamps)
         cfg = demo_config(inp, evf, cam, device=DEV, env=os.environ)
+        if motion_prior is not None:
+            cfg['tracking'] = dict(cfg['tracking'], motion_prior=motion_prior)
+            if 'CMAX_MIN_EVENTS' in os.environ:
+                cfg['tracking']['cmax_min_events'] = int(os.environ['CMAX_MIN_EVENTS'])
+        if streams is not None:                             # the stream and the frame times the prior reads
+            from evennicer_slam_amd.event_stream import EventStream
+            EventStream.concatenate(streams).save(os.path.join(tmp, 'events.npz'))
+            with open(os.path.join(tmp, 'stamps.txt'), 'w') as f:
+                f.write(''.join(f'{v!r}\n' for v in stamps))
+            cfg['data'] = dict(cfg['data'], event_stream=os.path.join(tmp, 'events.npz'), frame_stamps=os.path.join(tmp, 'stamps.txt'))
         extra = {}
         if events == 'simulate':
             cfg['event'] = dict(cfg['event'], activate_events=True)
@@ -184,7 +203,7 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=Non
             ck = torch.load(res['ckpt'], map_location='cpu', weights_only=False)
             err = (ck['estimate_c2w_list'][:, :3, 3] - ck['gt_c2w_list'][:, :3, 3]).norm(dim=1)
             out[tag] = dict(ate=ate['absolute_translational_error.rmse'], raw_rmse=float((err ** 2).mean().sqrt()), raw_max=float(err.max()),
-                            fps=res['fps'], prefit_loss=fit)
+                            fps=res['fps'], prefit_loss=fit, **({'motion_prior': res['motion_prior']} if 'motion_prior' in res else {}))
             if mesh_dir is not None and tag == 'tracked':
                 os.makedirs(mesh_dir, exist_ok=True)
                 out[tag]['mesh'] = mesh_metrics(slam, os.path.join(mesh_dir, 'mesh.ply'), tsdf=tsdf)
