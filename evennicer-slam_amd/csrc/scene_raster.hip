@@ -8,12 +8,8 @@
 // in every run and do not depend on how the views are batched.
 //
 //   fill     the buffer with 0xFF bytes (nothing)
-//   small    one thread per (triangle, view): mesh_depth.hip's arithmetic -- with a, b, c the vertices in camera space,
-//            n0 = b x c, n1 = c x a, n2 = a x b, det = a . n0 and s_i = d . n_i: inside iff s0, s1, s2 share a sign (zeros
-//            count), t = det / (s0 + s1 + s2) -- over the pixel box of the projected vertices (the whole image when a
-//            vertex is at or behind the camera plane); a box of at most SR_SMALL pixels is rasterised by the thread, a
-//            larger one is appended to a list (when the list is full the thread rasterises it after all)
-//   large    a workgroup per listed (triangle, view), grid-stride over the list: 256 threads share the box
+//   small    \ the rasteriser of tri_raster.hpp (the one mesh_depth.hip runs; the arithmetic is set out there) with culling;
+//   large    / a covered pixel takes the minimum of what it holds and (bit pattern of t, face)
 //   points   one thread per (point, view): a point of camera depth z = -p_z in (z_near, z_far] covers the point_size x
 //            point_size pixel square whose first column is ceil(u - point_size / 2) and first row ceil(w - point_size / 2),
 //            u = cx + fx (p_x / z), w = cy - fy (p_y / z), clipped to the image, at the constant depth z
@@ -24,103 +20,27 @@
 // Vertex normals (Open3D's compute_vertex_normals): per vertex the unnormalised face normals (b - a) x (c - a) of its
 // incident faces summed in ascending face order from a CSR incidence -- no float atomics -- then normalised; a zero sum
 // stays zero.
-#include "../../include/enslam_hip.h"
-#include "common.hpp"
+#include "tri_raster.hpp"
 
 namespace {
 
-constexpr int SR_BLOCK = 256;
-constexpr int SR_SMALL = 256;                           // pixels a single thread rasterises
-constexpr int SR_LARGE_GRID = 2048;
-constexpr int64_t SR_LIST_CAP = (int64_t)1 << 22;       // listed (triangle, view) pairs: 32 MB
 constexpr uint64_t SR_NONE = ~(uint64_t)0;
 constexpr uint32_t SR_POINT = 0x80000000u;
 constexpr int64_t SR_HEAD = 256;                        // bytes in front of the visibility buffer: the list counter
 
-struct SrArgs {
-    const double* verts;
-    const int32_t* faces;
+struct SrArgs : TriArgs {           // F is 0 without a mesh
     const uint8_t* vcol;            // [V,3] or NULL
     const double* vnrm;             // [V,3] or NULL
     const double* pts;              // [P,3]
     const uint8_t* pcol;            // [P,3]
-    const double* w2c;              // [K,12]
-    int64_t F;
-    int32_t V, P, K, H, W, psize, cull;
-    double fx, fy, cx, cy, z_near, z_far, ambient;
+    int32_t P, psize;
+    double ambient;
     uint32_t background;            // r | g << 8 | b << 16
     uint64_t* vis;                  // [K,H,W]
-    int32_t* list_count;
-    int64_t* list;                  // [list_cap] entries  view * F + triangle
-    int64_t list_cap;
     uint8_t* rgb;                   // [K,H,W,3]
     float* depth;                   // [K,H,W] or NULL
     int32_t* id;                    // [K,H,W] or NULL
 };
-
-struct SrTri {
-    double n0[3], n1[3], n2[3], det;
-    int i0, i1, j0, j1;             // inclusive pixel box
-};
-
-ENS_DEV void sr_cross(const double* a, const double* b, double* o) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// floor / ceil of a pixel coordinate clamped into [-1, n] first (the value may be huge)
-ENS_DEV int sr_pix(double x, int n) { return (int)(x < -1.0 ? -1.0 : (x > (double)n ? (double)n : x)); }
-
-// camera-space vertices of face f in view k; false for an index outside [0, V)
-ENS_DEV bool sr_face(const SrArgs& A, int64_t f, int k, int (&vi)[3], double (&p)[3][3]) {
-    vi[0] = A.faces[3 * f]; vi[1] = A.faces[3 * f + 1]; vi[2] = A.faces[3 * f + 2];
-    if ((uint32_t)vi[0] >= (uint32_t)A.V || (uint32_t)vi[1] >= (uint32_t)A.V || (uint32_t)vi[2] >= (uint32_t)A.V) return false;
-    const double* m = A.w2c + 12 * (int64_t)k;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double* w = A.verts + 3 * (int64_t)vi[j];
-        const double x = w[0], y = w[1], z = w[2];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) p[j][r] = ((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3];
-    }
-    return true;
-}
-
-// The edge normals and the pixel box of triangle f in view k.  Returns false when the triangle cannot be hit or is culled.
-ENS_DEV bool sr_setup(const SrArgs& A, int64_t f, int k, SrTri& T) {
-    int vi[3];
-    double p[3][3];
-    if (!sr_face(A, f, k, vi, p)) return false;
-    sr_cross(p[1], p[2], T.n0);
-    sr_cross(p[2], p[0], T.n1);
-    sr_cross(p[0], p[1], T.n2);
-    T.det = (p[0][0] * T.n0[0] + p[0][1] * T.n0[1]) + p[0][2] * T.n0[2];
-    // the triangle's normal (b - a) x (c - a) = n0 + n1 + n2: zero for a repeated vertex (n1 = -n0 and n2 = 0 to the bit)
-    const double nx = T.n0[0] + T.n1[0] + T.n2[0], ny = T.n0[1] + T.n1[1] + T.n2[1], nz = T.n0[2] + T.n1[2] + T.n2[2];
-    if ((nx == 0.0 && ny == 0.0 && nz == 0.0) || !(T.det != 0.0) || !(T.det - T.det == 0.0)) return false;
-    if ((A.cull == 1 && !(T.det > 0.0)) || (A.cull == 2 && !(T.det < 0.0))) return false;
-    const double za = -p[0][2], zb = -p[1][2], zc = -p[2][2];          // depths
-    const double zmin = fmin(za, fmin(zb, zc)), zmax = fmax(za, fmax(zb, zc));
-    if (!(zmax > A.z_near) || !(zmin <= A.z_far)) return false;         // every hit has its depth in [zmin, zmax]
-    T.i0 = 0; T.i1 = A.W - 1; T.j0 = 0; T.j1 = A.H - 1;
-    if (zmin > 0.0) {                                   // all in front: the projection of the triangle is inside the box
-        double u0 = __builtin_huge_val(), u1 = -u0, w0 = u0, w1 = -u0;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double u = A.cx + A.fx * (p[j][0] / -p[j][2]), w = A.cy - A.fy * (p[j][1] / -p[j][2]);
-            u0 = fmin(u0, u); u1 = fmax(u1, u);
-            w0 = fmin(w0, w); w1 = fmax(w1, w);
-        }
-        // one thousandth of a pixel covers the rounding of the projection
-        const int i0 = sr_pix(floor(u0 - 1e-3), A.W), i1 = sr_pix(ceil(u1 + 1e-3), A.W);
-        const int j0 = sr_pix(floor(w0 - 1e-3), A.H), j1 = sr_pix(ceil(w1 + 1e-3), A.H);
-        T.i0 = i0 < 0 ? 0 : i0; T.i1 = i1 > A.W - 1 ? A.W - 1 : i1;
-        T.j0 = j0 < 0 ? 0 : j0; T.j1 = j1 > A.H - 1 ? A.H - 1 : j1;
-        if (T.i0 > T.i1 || T.j0 > T.j1) return false;
-    }
-    return true;
-}
 
 ENS_DEV void sr_put(uint64_t* px, uint32_t depth_bits, uint32_t prim) {
     const uint64_t key = ((uint64_t)depth_bits << 32) | prim;
@@ -129,57 +49,15 @@ ENS_DEV void sr_put(uint64_t* px, uint32_t depth_bits, uint32_t prim) {
     if (key < *px) atomicMin((unsigned long long*)px, (unsigned long long)key);
 }
 
-ENS_DEV void sr_pixel(const SrArgs& A, const SrTri& T, uint32_t f, int k, int j, int i) {
-    const double dx = ((double)i - A.cx) / A.fx, dy = -((double)j - A.cy) / A.fy;
-    const double s0 = (dx * T.n0[0] + dy * T.n0[1]) - T.n0[2];
-    const double s1 = (dx * T.n1[0] + dy * T.n1[1]) - T.n1[2];
-    const double s2 = (dx * T.n2[0] + dy * T.n2[1]) - T.n2[2];
-    const bool inside = (s0 >= 0.0 && s1 >= 0.0 && s2 >= 0.0) || (s0 <= 0.0 && s1 <= 0.0 && s2 <= 0.0);
-    const double S = (s0 + s1) + s2;
-    if (!inside || S == 0.0) return;
-    const double t = T.det / S;
-    if (!(t > A.z_near) || !(t <= A.z_far)) return;
-    sr_put(A.vis + ((int64_t)k * A.H + j) * A.W + i, __float_as_uint((float)t), f);
-}
+struct SrSink {
+    static constexpr bool CULLS = true;
+    uint64_t* vis;
+    int32_t H, W, cull;
+    ENS_DEV void put(int k, int j, int i, uint32_t bits, uint32_t face) const { sr_put(vis + ((int64_t)k * H + j) * W + i, bits, face); }
+};
 
-__global__ __launch_bounds__(SR_BLOCK) void sr_small_kernel(SrArgs A) {
-    const int64_t e = (int64_t)blockIdx.x * SR_BLOCK + threadIdx.x;
-    if (e >= A.F * A.K) return;
-    const int k = (int)(e / A.F);
-    const int64_t f = e - (int64_t)k * A.F;
-    SrTri T;
-    if (!sr_setup(A, f, k, T)) return;
-    const int64_t box = (int64_t)(T.i1 - T.i0 + 1) * (T.j1 - T.j0 + 1);
-    if (box > SR_SMALL) {
-        const int64_t slot = atomicAdd(A.list_count, 1);
-        if (slot < A.list_cap) {
-            A.list[slot] = e;
-            return;
-        }
-    }
-    for (int j = T.j0; j <= T.j1; ++j)
-        for (int i = T.i0; i <= T.i1; ++i) sr_pixel(A, T, (uint32_t)f, k, j, i);
-}
-
-__global__ __launch_bounds__(SR_BLOCK) void sr_large_kernel(SrArgs A) {
-    int64_t count = *A.list_count;
-    count = count < A.list_cap ? count : A.list_cap;
-    for (int64_t s = blockIdx.x; s < count; s += gridDim.x) {
-        const int64_t e = A.list[s];
-        if (e < 0 || e >= A.F * A.K) continue;
-        const int k = (int)(e / A.F);
-        const int64_t f = e - (int64_t)k * A.F;
-        SrTri T;
-        if (!sr_setup(A, f, k, T)) continue;
-        const int bw = T.i1 - T.i0 + 1;
-        const uint32_t box = (uint32_t)bw * (uint32_t)(T.j1 - T.j0 + 1);               // H * W <= 2^31
-        for (uint32_t q = threadIdx.x; q < box; q += SR_BLOCK)
-            sr_pixel(A, T, (uint32_t)f, k, T.j0 + (int)(q / (uint32_t)bw), T.i0 + (int)(q % (uint32_t)bw));
-    }
-}
-
-__global__ __launch_bounds__(SR_BLOCK) void sr_point_kernel(SrArgs A) {
-    const int64_t e = (int64_t)blockIdx.x * SR_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(TRI_BLOCK) void sr_point_kernel(SrArgs A) {
+    const int64_t e = (int64_t)blockIdx.x * TRI_BLOCK + threadIdx.x;
     if (e >= (int64_t)A.P * A.K) return;
     const int k = (int)(e / A.P);
     const int32_t p = (int32_t)(e - (int64_t)k * A.P);
@@ -207,8 +85,8 @@ ENS_DEV uint8_t sr_level(double x) {
     return (uint8_t)(v < 0.0 ? 0.0 : (v > 255.0 ? 255.0 : v));                // a NaN gives 0
 }
 
-__global__ __launch_bounds__(SR_BLOCK) void sr_resolve_kernel(SrArgs A) {
-    const int64_t e = (int64_t)blockIdx.x * SR_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(TRI_BLOCK) void sr_resolve_kernel(SrArgs A) {
+    const int64_t e = (int64_t)blockIdx.x * TRI_BLOCK + threadIdx.x;
     const int64_t hw = (int64_t)A.H * A.W;
     if (e >= hw * A.K) return;
     const uint64_t key = A.vis[e];
@@ -230,10 +108,10 @@ __global__ __launch_bounds__(SR_BLOCK) void sr_resolve_kernel(SrArgs A) {
             const int j = (int)(r / A.W), i = (int)(r - (int64_t)j * A.W);
             int vi[3];
             double p[3][3], n0[3], n1[3], n2[3];
-            sr_face(A, prim, k, vi, p);                                         // in range: the face made it into the buffer
-            sr_cross(p[1], p[2], n0);
-            sr_cross(p[2], p[0], n1);
-            sr_cross(p[0], p[1], n2);
+            tri_face(A, prim, k, vi, p);                                        // in range: the face made it into the buffer
+            tri_cross(p[1], p[2], n0);
+            tri_cross(p[2], p[0], n1);
+            tri_cross(p[0], p[1], n2);
             const double dx = ((double)i - A.cx) / A.fx, dy = -((double)j - A.cy) / A.fy;
             const double s0 = (dx * n0[0] + dy * n0[1]) - n0[2];
             const double s1 = (dx * n1[0] + dy * n1[1]) - n1[2];
@@ -250,7 +128,7 @@ __global__ __launch_bounds__(SR_BLOCK) void sr_resolve_kernel(SrArgs A) {
                 const double *va = A.verts + 3 * (int64_t)vi[0], *vb = A.verts + 3 * (int64_t)vi[1], *vc = A.verts + 3 * (int64_t)vi[2];
                 const double e1[3] = {vb[0] - va[0], vb[1] - va[1], vb[2] - va[2]};
                 const double e2[3] = {vc[0] - va[0], vc[1] - va[1], vc[2] - va[2]};
-                sr_cross(e1, e2, n);
+                tri_cross(e1, e2, n);
             }
             // the pixel direction in world space: the rotation of w2c transposed
             const double* m = A.w2c + 12 * (int64_t)k;
@@ -279,9 +157,9 @@ __global__ __launch_bounds__(SR_BLOCK) void sr_resolve_kernel(SrArgs A) {
 }
 
 // one thread per vertex: the face normals of off[v] .. off[v + 1] summed in the order of the list
-__global__ __launch_bounds__(SR_BLOCK) void sr_normals_kernel(const double* verts, int32_t V, const int32_t* faces, int32_t F,
+__global__ __launch_bounds__(TRI_BLOCK) void sr_normals_kernel(const double* verts, int32_t V, const int32_t* faces, int32_t F,
                                                               const int64_t* off, const int32_t* inc, int64_t n_inc, double* out) {
-    const int32_t v = (int32_t)((int64_t)blockIdx.x * SR_BLOCK + threadIdx.x);
+    const int32_t v = (int32_t)((int64_t)blockIdx.x * TRI_BLOCK + threadIdx.x);
     if (v >= V) return;
     double acc[3] = {0.0, 0.0, 0.0};
     int64_t lo = off[v], hi = off[v + 1];
@@ -296,7 +174,7 @@ __global__ __launch_bounds__(SR_BLOCK) void sr_normals_kernel(const double* vert
         const double e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
         const double e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
         double fn[3];
-        sr_cross(e1, e2, fn);
+        tri_cross(e1, e2, fn);
         acc[0] += fn[0]; acc[1] += fn[1]; acc[2] += fn[2];
     }
     const double len = sqrt((acc[0] * acc[0] + acc[1] * acc[1]) + acc[2] * acc[2]);
@@ -304,20 +182,7 @@ __global__ __launch_bounds__(SR_BLOCK) void sr_normals_kernel(const double* vert
     out[3 * (int64_t)v] = acc[0]; out[3 * (int64_t)v + 1] = acc[1]; out[3 * (int64_t)v + 2] = acc[2];
 }
 
-bool sr_finite(double x) { return x == x && x - x == 0.0; }
-
-int64_t sr_list_cap(int64_t F, int64_t K) { return F * K < SR_LIST_CAP ? (F * K < 1 ? 1 : F * K) : SR_LIST_CAP; }
-
 int64_t sr_vis_bytes(int64_t K, int64_t H, int64_t W) { return (8 * K * H * W + 255) / 256 * 256; }
-
-int sr_sizes(int32_t n_verts, int32_t n_faces, int32_t n_points, int32_t n_views, int32_t H, int32_t W) {
-    if (n_verts < 0 || n_faces < 0 || n_points < 0 || n_views < 0 || H <= 0 || W <= 0) return ENSLAM_EINVAL;
-    // the list counter is an int32, a box is counted in 32 bits, a point id keeps 31
-    if ((int64_t)n_views * H * W > ((int64_t)1 << 31) || (int64_t)n_faces * n_views > INT32_MAX ||
-        (int64_t)n_points * n_views > INT32_MAX)
-        return ENSLAM_EUNSUPPORTED;
-    return ENSLAM_OK;
-}
 
 }  // namespace
 
@@ -329,7 +194,7 @@ int enslam_scene_normals(const double* vertices, int32_t n_verts, const int32_t*
     if (n_verts < 0 || n_faces < 0 || n_incident < 0) return ENSLAM_EINVAL;
     if (n_verts == 0) return ENSLAM_OK;
     if (!vertices || !vf_offsets || !normals_out || (n_incident > 0 && (!faces || !vf_faces))) return ENSLAM_EINVAL;
-    sr_normals_kernel<<<(unsigned)((n_verts + SR_BLOCK - 1) / SR_BLOCK), SR_BLOCK, 0, (hipStream_t)stream>>>(
+    sr_normals_kernel<<<(unsigned)((n_verts + TRI_BLOCK - 1) / TRI_BLOCK), TRI_BLOCK, 0, (hipStream_t)stream>>>(
         vertices, n_verts, faces, n_faces, vf_offsets, vf_faces, n_incident, normals_out);
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
@@ -337,7 +202,7 @@ int enslam_scene_normals(const double* vertices, int32_t n_verts, const int32_t*
 int enslam_scene_raster_workspace(int32_t n_faces, int32_t n_views, int32_t H, int32_t W, int64_t* bytes_host) {
     if (n_faces < 0 || n_views < 0 || H <= 0 || W <= 0 || !bytes_host) return ENSLAM_EINVAL;
     if ((int64_t)n_views * H * W > ((int64_t)1 << 31)) return ENSLAM_EUNSUPPORTED;
-    *bytes_host = SR_HEAD + sr_vis_bytes(n_views, H, W) + 8 * sr_list_cap(n_faces, n_views);
+    *bytes_host = SR_HEAD + sr_vis_bytes(n_views, H, W) + 8 * tri_list_cap(n_faces, n_views);
     return ENSLAM_OK;
 }
 
@@ -347,10 +212,8 @@ int enslam_scene_raster(const double* vertices, int32_t n_verts, const int32_t* 
                         int32_t W, double fx, double fy, double cx, double cy, double z_near, double z_far, int32_t cull,
                         double ambient, uint32_t background, int32_t passes, void* workspace, int64_t workspace_bytes,
                         uint8_t* rgb_out, float* depth_out, int32_t* id_out, void* stream) {
-    const int rc = sr_sizes(n_verts, n_faces, n_points, n_views, H, W);
+    const int rc = tri_refuse(n_verts, n_faces, n_points, n_views, H, W, fx, fy, cx, cy, z_near, z_far);
     if (rc != ENSLAM_OK) return rc;
-    if (!sr_finite(fx) || !sr_finite(fy) || !sr_finite(cx) || !sr_finite(cy) || fx == 0.0 || fy == 0.0) return ENSLAM_EINVAL;
-    if (!sr_finite(z_near) || z_far != z_far || z_near < 0.0 || !(z_far > z_near)) return ENSLAM_EINVAL;
     if (passes < 1 || passes > 7 || cull < 0 || cull > 2 || point_size < 1 || point_size > 64 || !(ambient >= 0.0) || !(ambient <= 1.0)) return ENSLAM_EINVAL;
     if (n_views == 0) return ENSLAM_OK;
     const int64_t vis_bytes = sr_vis_bytes(n_views, H, W);
@@ -364,29 +227,25 @@ int enslam_scene_raster(const double* vertices, int32_t n_verts, const int32_t* 
     A.verts = vertices; A.faces = faces; A.vcol = vertex_colors; A.vnrm = vertex_normals;
     A.pts = points; A.pcol = point_colors; A.w2c = w2c;
     A.F = mesh ? n_faces : 0; A.V = n_verts; A.P = n_points; A.K = n_views; A.H = H; A.W = W;
-    A.psize = point_size; A.cull = cull;
+    A.psize = point_size;
     A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy; A.z_near = z_near; A.z_far = z_far; A.ambient = ambient;
     A.background = background;
     A.list_count = (int32_t*)workspace;
     A.vis = (uint64_t*)((char*)workspace + SR_HEAD);
     A.list = (int64_t*)((char*)workspace + SR_HEAD + vis_bytes);
-    const int64_t room = (workspace_bytes - SR_HEAD - vis_bytes) / 8, want = sr_list_cap(n_faces, n_views);
+    const int64_t room = (workspace_bytes - SR_HEAD - vis_bytes) / 8, want = tri_list_cap(n_faces, n_views);
     A.list_cap = room < want ? room : want;
     A.rgb = rgb_out; A.depth = depth_out; A.id = id_out;
     if (passes & 1) {
         if (hipMemsetAsync(A.vis, 0xFF, 8 * (size_t)n_px, s) != hipSuccess) return ENSLAM_ELAUNCH;
         if (hipMemsetAsync(A.list_count, 0, 4, s) != hipSuccess) return ENSLAM_ELAUNCH;
     }
-    if (mesh && (passes & 1)) {
-        const unsigned blocks = (unsigned)(((int64_t)n_faces * n_views + SR_BLOCK - 1) / SR_BLOCK);
-        sr_small_kernel<<<blocks, SR_BLOCK, 0, s>>>(A);
-        sr_large_kernel<<<SR_LARGE_GRID, SR_BLOCK, 0, s>>>(A);
-    }
+    if (mesh && (passes & 1)) tri_launch(A, SrSink{A.vis, H, W, cull}, s);
     if (n_points > 0 && (passes & 2)) {
-        const unsigned blocks = (unsigned)(((int64_t)n_points * n_views + SR_BLOCK - 1) / SR_BLOCK);
-        sr_point_kernel<<<blocks, SR_BLOCK, 0, s>>>(A);
+        const unsigned blocks = (unsigned)(((int64_t)n_points * n_views + TRI_BLOCK - 1) / TRI_BLOCK);
+        sr_point_kernel<<<blocks, TRI_BLOCK, 0, s>>>(A);
     }
-    if (passes & 4) sr_resolve_kernel<<<(unsigned)((n_px + SR_BLOCK - 1) / SR_BLOCK), SR_BLOCK, 0, s>>>(A);
+    if (passes & 4) sr_resolve_kernel<<<(unsigned)((n_px + TRI_BLOCK - 1) / TRI_BLOCK), TRI_BLOCK, 0, s>>>(A);
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
 

@@ -2071,6 +2071,29 @@ def nearest(query, ref, max_dist=None, max_rings=None, stats=None):
     return NearestIndex(ref).query(query, max_dist=max_dist, max_rings=max_rings, stats=stats)
 
 
+def _mesh_args(what, vertices, faces):
+    """(lib, vertices, V, faces, F, device) of the mesh of `what`: float64 [V,3] and int32 [F,3], contiguous, on one HIP device"""
+    if not vertices.is_cuda:
+        raise NotImplementedError(f"{what} needs a HIP device")
+    lib = L.lib()
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype is not torch.float64:
+        raise L.EnslamError(f"vertices must be float64 [V,3] (got {vertices.dtype} {tuple(vertices.shape)})")
+    v = vertices.detach().contiguous()
+    f = _mesh_faces(faces, v.shape[0])
+    if f.device != v.device:
+        raise L.EnslamError("vertices and faces must live on one device")
+    return lib, v, int(v.shape[0]), f, int(f.shape[0]), v.device
+
+
+def _views(w2c, cam, dev):
+    """(w2c float64 [K,3,4] on dev, K, H, W, (fx, fy, cx, cy)) of K cameras ([K,3,4] or [K,4,4], numpy or tensor) and a cam dict"""
+    w = torch.as_tensor(w2c)
+    if w.dim() != 3 or tuple(w.shape[1:]) not in ((3, 4), (4, 4)):
+        raise L.EnslamError(f"w2c must be [K,3,4] or [K,4,4] (got shape {tuple(w.shape)})")
+    w = w[:, :3].to(torch.float64).contiguous().to(dev)
+    return w, int(w.shape[0]), int(cam['H']), int(cam['W']), tuple(float(cam[k]) for k in ('fx', 'fy', 'cx', 'cy'))
+
+
 def mesh_depth(vertices, faces, w2c, cam, z_near=0.0, z_far=20.0):
     """float32 [K,H,W] depth images of a triangle mesh (vertices float64 [V,3], faces int32 [F,3], HIP device) from the K
     cameras w2c ([K,3,4] or [K,4,4], numpy or tensor, the convention of `visibility` / `world_to_camera`: the camera looks
@@ -2079,23 +2102,8 @@ def mesh_depth(vertices, faces, w2c, cam, z_near=0.0, z_far=20.0):
     triangle, 0.0 where none does (enslam_mesh_depth, enslam_hip.h): both sides count, edges are inclusive, float64 up to the
     rounding of t.  z_far = 20 is the reference's far plane; z_near = 0 is a difference: the reference's renderer derives
     its near plane from the scene's bounding box."""
-    if not vertices.is_cuda:
-        raise NotImplementedError("mesh_depth needs a HIP device")
-    lib = L.lib()
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype is not torch.float64:
-        raise L.EnslamError(f"vertices must be float64 [V,3] (got {vertices.dtype} {tuple(vertices.shape)})")
-    v = vertices.detach().contiguous()
-    V, dev = int(v.shape[0]), v.device
-    f = _mesh_faces(faces, V)
-    if f.device != dev:
-        raise L.EnslamError("vertices and faces must live on one device")
-    F = int(f.shape[0])
-    w = torch.as_tensor(w2c)
-    if w.dim() != 3 or tuple(w.shape[1:]) not in ((3, 4), (4, 4)):
-        raise L.EnslamError(f"w2c must be [K,3,4] or [K,4,4] (got shape {tuple(w.shape)})")
-    K = int(w.shape[0])
-    w = w[:, :3].to(torch.float64).contiguous().to(dev)
-    H, W = int(cam['H']), int(cam['W'])
+    lib, v, V, f, F, dev = _mesh_args("mesh_depth", vertices, faces)
+    w, K, H, W, pinhole = _views(w2c, cam, dev)
     depth = torch.empty((K, H, W), dtype=torch.float32, device=dev)
     if K == 0:
         return depth
@@ -2103,35 +2111,20 @@ def mesh_depth(vertices, faces, w2c, cam, z_near=0.0, z_far=20.0):
         nbytes = ctypes.c_int64()
         L.check(lib.enslam_mesh_depth_workspace(F, K, ctypes.byref(nbytes)), "enslam_mesh_depth_workspace")
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        L.check(lib.enslam_mesh_depth(_ptr(v) if V else None, V, _ptr(f) if F else None, F, _ptr(w), K, H, W, float(cam['fx']),
-                                      float(cam['fy']), float(cam['cx']), float(cam['cy']), float(z_near), float(z_far),
-                                      _ptr(ws), _ptr(depth), _stream()), "enslam_mesh_depth")
+        L.check(lib.enslam_mesh_depth(_ptr(v) if V else None, V, _ptr(f) if F else None, F, _ptr(w), K, H, W, *pinhole,
+                                      float(z_near), float(z_far), _ptr(ws), _ptr(depth), _stream()), "enslam_mesh_depth")
     return depth
 
 
 # ------------------------------------------------------------------------------------------------
 # Scene rasteriser (csrc/scene_raster.hip): the colour renderer of the headless visualiser (viz.py)
 # ------------------------------------------------------------------------------------------------
-def _mesh_vertices(vertices):
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype is not torch.float64:
-        raise L.EnslamError(f"vertices must be float64 [V,3] (got {vertices.dtype} {tuple(vertices.shape)})")
-    return vertices.detach().contiguous()
-
-
 def vertex_normals(vertices, faces):
     """float64 [V,3]: Open3D's compute_vertex_normals of a mesh on a HIP device (vertices float64 [V,3], faces int32 [F,3]):
     per vertex the unnormalised face normals (b - a) x (c - a) of its incident faces, summed in ascending face order by one
     thread (enslam_scene_normals: the same bits in every run), then normalised; a vertex no face uses, or whose sum is zero,
     gets zero.  A face with an index outside [0, V) is dropped.  The vertex -> face incidence is built here with torch sorts."""
-    if not vertices.is_cuda:
-        raise NotImplementedError("vertex_normals needs a HIP device")
-    lib = L.lib()
-    v = _mesh_vertices(vertices)
-    V, dev = int(v.shape[0]), v.device
-    f = _mesh_faces(faces, V)
-    if f.device != dev:
-        raise L.EnslamError("vertices and faces must live on one device")
-    F = int(f.shape[0])
+    lib, v, V, f, F, dev = _mesh_args("vertex_normals", vertices, faces)
     out = torch.empty((V, 3), dtype=torch.float64, device=dev)
     if V == 0:
         return out
@@ -2163,13 +2156,7 @@ def scene_raster(vertices, faces, w2c, cam, colors=None, normals=None, points=No
     [K,H,W] or None): depth 0 and id -1 where empty, id -2 - p for point p.  workspace_bytes: the size of the scratch
     allocation (default: enslam_scene_raster_workspace); a smaller one shortens the list of large triangles and changes
     nothing in the images."""
-    if not vertices.is_cuda:
-        raise NotImplementedError("scene_raster needs a HIP device")
-    lib = L.lib()
-    v = _mesh_vertices(vertices)
-    V, dev = int(v.shape[0]), v.device
-    f = _mesh_faces(faces, V)
-    F = int(f.shape[0])
+    lib, v, V, f, F, dev = _mesh_args("scene_raster", vertices, faces)
 
     def per(t, n, dtype, what):
         if t is None:
@@ -2178,22 +2165,15 @@ def scene_raster(vertices, faces, w2c, cam, colors=None, normals=None, points=No
             raise L.EnslamError(f"{what} must be {dtype} [{n},3] on {dev}")
         return t.detach().contiguous()
 
-    if f.device != dev:
-        raise L.EnslamError("vertices and faces must live on one device")
     col, nrm = per(colors, V, torch.uint8, "colors"), per(normals, V, torch.float64, "normals")
     P = 0 if points is None else int(points.shape[0])
     pts, pcol = per(points, P, torch.float64, "points"), per(point_colors, P, torch.uint8, "point_colors")
     if (pts is None) != (pcol is None):
         raise L.EnslamError("points and point_colors come together")
-    w = torch.as_tensor(w2c)
-    if w.dim() != 3 or tuple(w.shape[1:]) not in ((3, 4), (4, 4)):
-        raise L.EnslamError(f"w2c must be [K,3,4] or [K,4,4] (got shape {tuple(w.shape)})")
-    K = int(w.shape[0])
-    w = w[:, :3].to(torch.float64).contiguous().to(dev)
+    w, K, H, W, pinhole = _views(w2c, cam, dev)
     bg = [int(c) for c in background]
     if len(bg) != 3 or min(bg) < 0 or max(bg) > 255:
         raise L.EnslamError(f"background must be three levels in 0..255 (got {background})")
-    H, W = int(cam['H']), int(cam['W'])
     rgb = torch.empty((K, H, W, 3), dtype=torch.uint8, device=dev)
     depth = torch.empty((K, H, W), dtype=torch.float32, device=dev) if want_depth else None
     ids = torch.empty((K, H, W), dtype=torch.int32, device=dev) if want_id else None
@@ -2204,8 +2184,8 @@ def scene_raster(vertices, faces, w2c, cam, colors=None, normals=None, points=No
         ws = torch.empty(max(nbytes, 0), dtype=torch.uint8, device=dev)
         L.check(lib.enslam_scene_raster(_ptr(v) if V else None, V, _ptr(f) if F else None, F, _ptr(col), _ptr(nrm),
                                         _ptr(pts) if P else None, P, _ptr(pcol) if P else None, int(point_size), _ptr(w), K, H, W,
-                                        float(cam['fx']), float(cam['fy']), float(cam['cx']), float(cam['cy']), float(z_near),
-                                        float(z_far), int(cull), float(ambient), bg[0] | bg[1] << 8 | bg[2] << 16, 7,
+                                        *pinhole, float(z_near), float(z_far), int(cull), float(ambient),
+                                        bg[0] | bg[1] << 8 | bg[2] << 16, 7,
                                         _ptr(ws) if nbytes > 0 else None, nbytes, _ptr(rgb), _ptr(depth), _ptr(ids), _stream()),
                 "enslam_scene_raster")
     return (rgb, depth, ids) if (want_depth or want_id) else rgb

@@ -2,7 +2,7 @@
 contracts are decided, and yardsticks in exact arithmetic (tests/test_recon_edges_cpu.py, tests/test_hip_recon_edges.py).
 
 Mesh depth.  Intrinsics, world-to-camera entries and vertex coordinates are small dyadic rationals, so every float64
-intermediate of md_pixel (the edge normals n_i, det, the s_i and S) is exact; only t = det / S (correctly rounded) and
+intermediate of tri_cover (the edge normals n_i, det, the s_i and S) is exact; only t = det / S (correctly rounded) and
 (float)t round.  exact_depth evaluates the contract -- both sides count, edges inclusive, degenerate triangles and triangles
 whose plane holds the camera centre hit nothing, z_near < t <= z_far -- in fractions.Fraction and integers and returns
 np.float32(float(t)): a ray through a vertex, along an edge or at t == z_far is decided, not excused by a margin.  Every case
@@ -152,7 +152,7 @@ def assert_budget(vertices, faces, w2c, cam):
         m = np.asarray(m, np.float64)
         for v in used:
             x, y, z = (float(c) for c in vertices[v])
-            got = [((m[r, 0] * x + m[r, 1] * y) + m[r, 2] * z) + m[r, 3] for r in range(3)]          # md_setup's expression
+            got = [((m[r, 0] * x + m[r, 1] * y) + m[r, 2] * z) + m[r, 3] for r in range(3)]          # tri_face's expression
             assert all(Fraction(got[r]) == p[v][r] for r in range(3)), "camera-space coordinates are not exact"
         bits = 0
         for axis in range(3):
@@ -165,7 +165,7 @@ def assert_budget(vertices, faces, w2c, cam):
 
 
 def pixel_box(a, b, c, cam):
-    """(i0, i1, j0, j1): md_setup's inclusive pixel box of a camera-space triangle in front of the camera, restated: the
+    """(i0, i1, j0, j1): tri_setup's inclusive pixel box of a camera-space triangle in front of the camera, restated: the
     projected vertices, 1e-3 px of slack, floor / ceil, the clamp into the image"""
     p = np.array([a, b, c], np.float64)
     assert (-p[:, 2]).min() > 0
@@ -242,7 +242,7 @@ def _depth_case_list():
               _case('limits/near_below', seam, z_near=down),
               _case('limits/near_above', seam, z_near=up)]
     # a triangle in the plane depth = 4 + x: t = 4 exactly down column 16 while its vertices are at depths 2, 6 and 4, so the
-    # limits are decided per pixel (md_pixel), not by the cull on the triangle's depth range (md_setup)
+    # limits are decided per pixel (tri_cover), not by the cull on the triangle's depth range (tri_setup)
     ramp = _mesh(((-2.0, -2.0, -2.0), (2.0, -2.0, -6.0), (0.0, 3.0, -4.0)), BACK_QUAD)
     cases += [_case('limits/ramp', ramp),
               _case('limits/ramp_far_eq', ramp, z_far=4.0, decides=('far_strict',)),
@@ -284,7 +284,7 @@ def _depth_case_list():
     return cases
 
 
-BOX_SPLIT = {'box_split/256': (16, 16), 'box_split/272': (16, 17)}      # (width, height) of md_setup's box
+BOX_SPLIT = {'box_split/256': (16, 16), 'box_split/272': (16, 17)}      # (width, height) of tri_setup's box
 
 
 @functools.lru_cache(maxsize=None)

@@ -53,7 +53,7 @@ def test_mesh_depth_equals_the_exact_contract(name):
 
 
 def test_mesh_depth_box_split_routes_agree():
-    """16 x 16 = MD_SMALL pixels of box: the thread rasterises it; 16 x 17: a workgroup does; together: both in one call"""
+    """16 x 16 = TRI_SMALL pixels of box: the thread rasterises it; 16 x 17: a workgroup does; together: both in one call"""
     c = E.depth_cases()
     small, large, both = (_depth(c[n]) for n in ('box_split/256', 'box_split/272', 'box_split/both'))
     for n, got in (('box_split/256', small), ('box_split/272', large), ('box_split/both', both)):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import recon_edge_cases as E
 from tests import viz_cases as C
 from tests import viz_numpy as Y
 
@@ -144,6 +145,30 @@ def test_depth_equals_mesh_depth_to_the_bit(rendered):
     torch.cuda.synchronize()
     assert (want > 0).all()
     assert np.array_equal(rendered('room_cull0_plain')[1].view(np.uint32), want.cpu().numpy().view(np.uint32))
+
+
+@pytest.mark.parametrize("name", E.DEPTH_NAMES)
+def test_exact_cases_equal_mesh_depth_and_the_exact_contract(name):
+    """the exact cases of tests/recon_edge_cases.py (rays through vertices and along edges, t == z_far, degenerate triangles,
+    the camera plane, both sides of the box split) through the renderer: its depth is mesh depth's and exact_depth's bit for
+    bit, a pixel has no primitive exactly where its depth is 0, and a list of large triangles with room for one entry
+    changes no byte"""
+    from evennicer_slam_amd import functional as EF
+    c = E.depth_cases()[name]
+    args = dict(vertices=c['vertices'], faces=c['faces'], views=c['w2c'], cull=0, z_near=c['z_near'], z_far=c['z_far'])
+    whole = _raster(args, cam=c['cam'])
+    md = EF.mesh_depth(dev(c['vertices']), dev(c['faces'], torch.int32), np.array(c['w2c']), c['cam'], z_near=c['z_near'],
+                       z_far=c['z_far'])
+    torch.cuda.synchronize()
+    got, md = whole[1].view(np.uint32), md.cpu().numpy().view(np.uint32)
+    print(f"{name}: hit {int((c['want'] > 0).sum())} of {got.size}, differing from mesh depth {int((got != md).sum())}, from the "
+          f"exact contract {int((got != c['want'].view(np.uint32)).sum())}")
+    assert np.array_equal(got, md)
+    assert np.array_equal(got, c['want'].view(np.uint32)) and np.array_equal(md, c['want'].view(np.uint32))
+    assert np.array_equal(whole[2] == -1, got == 0) and (whole[2] >= -1).all()
+    small = _raster(args, cam=c['cam'], workspace_bytes=C.tiny_workspace(len(c['w2c']), c['cam']))
+    for part in range(3):
+        assert small[part].tobytes() == whole[part].tobytes()
 
 
 # ---- the tool, end to end ---------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """The exact cases of tests/recon_edge_cases.py on the host: the yardsticks are right (against the float64 yardsticks of
-tests/recon_numpy.py where those are safe), every mesh-depth case is exact in float64 (a numpy restatement of md_setup and
-md_pixel equals the Fraction yardstick bit for bit), and each case decides the rule it is named for: with that one rule
+tests/recon_numpy.py where those are safe), every mesh-depth case is exact in float64 (a numpy restatement of tri_setup and
+tri_cover equals the Fraction yardstick bit for bit), and each case decides the rule it is named for: with that one rule
 broken the yardstick changes in at least 8 pixels or queries."""
 import numpy as np
 import pytest
@@ -41,10 +41,10 @@ def test_exact_nearest_equals_brute_force_where_nothing_ties():
     assert np.array_equal(last, i)                                          # ... so the tie rule does not matter here
 
 
-# ---- the budget check: md_setup and md_pixel in float64 numpy -----------------------------------------------------------------
+# ---- the budget check: tri_setup and tri_cover in float64 numpy -----------------------------------------------------------------
 def md_float64(vertices, faces, w2c, cam, z_near, z_far):
     """float32 [K,H,W]: csrc/mesh_depth.hip restated in float64 numpy, expression by expression in the kernel's order:
-    md_setup (camera space, n0 n1 n2, det, the zero-normal and det tests, the depth cull, the pixel box) and md_pixel over
+    tri_setup (camera space, n0 n1 n2, det, the zero-normal and det tests, the depth cull, the pixel box) and tri_cover over
     the box; the unsigned minimum on the float32 bits; 0.0 where nothing was written"""
     V, H, W = len(vertices), cam['H'], cam['W']
     fx, fy, cx, cy = (np.float64(cam[k]) for k in ('fx', 'fy', 'cx', 'cy'))
@@ -87,7 +87,7 @@ def md_float64(vertices, faces, w2c, cam, z_near, z_far):
 
 @pytest.mark.parametrize("name", E.DEPTH_NAMES)
 def test_every_depth_case_is_exact_in_float64(name):
-    """if this fails the case is not exact (or md_setup's box cuts a pixel of the contract): the case has to change"""
+    """if this fails the case is not exact (or tri_setup's box cuts a pixel of the contract): the case has to change"""
     c = E.depth_cases()[name]
     got = md_float64(c['vertices'], c['faces'], c['w2c'], c['cam'], c['z_near'], c['z_far'])
     differ = bits(got) != bits(c['want'])
@@ -156,7 +156,7 @@ def test_camera_plane_and_off_image_triangles_are_seen():
 
 
 def test_box_split_sizes():
-    """md_setup's box, restated, has 16 x 16 = MD_SMALL pixels for one triangle (the one-thread route) and 16 x 17 for the
+    """tri_setup's box, restated, has 16 x 16 = TRI_SMALL pixels for one triangle (the one-thread route) and 16 x 17 for the
     other (the one-workgroup route)"""
     c = E.depth_cases()
     for name, (bw, bh) in E.BOX_SPLIT.items():

@@ -25,9 +25,9 @@ def w2c_of(c2w):
     return np.stack([np.linalg.inv(m)[:3] for m in np.asarray(c2w, np.float64).reshape(-1, 4, 4)])
 
 
-def tiny_workspace(n_views=K):
+def tiny_workspace(n_views=K, cam=CAM):
     """bytes of a workspace whose list of large triangles has one entry"""
-    return 256 + (8 * n_views * CAM['H'] * CAM['W'] + 255) // 256 * 256 + 8
+    return 256 + (8 * n_views * cam['H'] * cam['W'] + 255) // 256 * 256 + 8
 
 
 def soup_views():
