@@ -158,7 +158,7 @@ struct SampleArgs {              // sample_kernel's scalar arguments (Renderer.p
     const float* t_lin;
     const double* t_surf;
     const float* t_rand;         // perturbation draws or null
-    const float* dmax;           // {max(gd), fl32(max * 1.2f)} when not reduced inline
+    float* dmax;                 // {max(gd), fl32(max * 1.2f)}: read when not reduced inline, else written by ray 0's wave
     double* zout;
 };
 int ens_launch_sample_prepare(int n_rays, int n_lin, int n_surf, const float* ro, const float* rd, const float* gd,

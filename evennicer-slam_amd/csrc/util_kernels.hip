@@ -51,6 +51,7 @@ ENS_DEV void sample_body(const SampleArgs& A, const MarkArgs& mk, const int ray,
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
             dmax0 = m; dmax1 = m * 1.2f;
+            if (ray == 0 && lane == 0) { A.dmax[0] = dmax0; A.dmax[1] = dmax1; }   // the caller's copy; no wave reads it in this mode
         } else {
             dmax0 = dmax[0]; dmax1 = dmax[1];
         }
@@ -872,7 +873,7 @@ int ens_launch_mark_blocks(int stage, int n_rays, int S, const float* ro, const 
 static bool fill_sample_args(int n_rays, int n_lin, int n_surf, const float* ro, const float* rd, const float* gd,
                              const double* b, const float* t_lin, const double* t_surf, int lindisp, const float* t_rand,
                              float* scratch, int dmax_given, double* z, const MarkArgs* mark, SampleArgs& A, MarkArgs& mk) {
-    if (n_lin + n_surf > MAX_S || n_lin < 1) return false;
+    if (n_lin + (gd ? n_surf : 0) > MAX_S || n_lin < 1) return false;    // n_surf counts only with depth
     A.n_rays = n_rays; A.n_lin = n_lin; A.n_surf = gd ? n_surf : 0; A.lindisp = lindisp;
     A.dmax_inline = (gd != nullptr && !dmax_given && n_rays <= 4096) ? 1 : 0;
     A.ro = ro; A.rd = rd; A.gd = gd; A.t_lin = t_lin; A.t_surf = t_surf; A.t_rand = t_rand; A.dmax = scratch; A.zout = z;

@@ -377,7 +377,15 @@ int enslam_tracker_tail(int32_t n_rays, int32_t n_samples, const float *raw, con
  *           depth_max_given != 0: read from scratch (a ray-sharded caller supplies the max of the WHOLE batch,
  *           so that every shard samples exactly what the unsharded reference would).
  *   z_vals  float64 [N, n_lin + n_surf] (n_surf forced to 0 when gt_depth is NULL)
- * Bit-exact with the reference's float64/float32 evaluation order. */
+ * n_lin >= 1 and at most 64 samples per ray, judged on the count that is written (n_lin alone when gt_depth is NULL):
+ * ENSLAM_EINVAL otherwise, without a launch.
+ * Bit-exact with the reference's float64/float32 evaluation order on every ray whose intermediates are numbers.
+ * Outside the contract: a face distance 0/0 (an origin exactly on a face of the bound with a zero direction component along
+ * that axis), a gt_depth that is not finite, and lindisp != 0 with near == 0 or far == 0 (a depth <= 0, an origin outside the
+ * bound).  torch's max / min hand a NaN on; the comparisons here do not (t0 > t1 ? t0 : t1, fmaxf), so such a ray's own row of
+ * z_vals is unspecified, and a gt_depth that is not finite makes the batch maxima, hence scratch and every depth-guided row
+ * of the call, unspecified.  In no other way does such a ray touch another ray's row, and nothing outside z_vals' [N, S]
+ * is written. */
 int enslam_sample_rays(int32_t n_rays, int32_t n_lin, int32_t n_surf, const float *rays_o, const float *rays_d,
                        const float *gt_depth, const double *bound_host, const float *t_lin, const double *t_surf,
                        int32_t lindisp, const float *t_rand, float *scratch, int32_t depth_max_given, double *z_vals,
