@@ -366,6 +366,11 @@ _SIGS = {
                                                     c_double, c_double, c_double, c_void_p, POINTER(c_double), c_double,
                                                     c_int32, c_int32, POINTER(c_double), c_void_p, c_int64, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "enslam_event_cmax_reg_workspace": (ctypes.c_int, [c_int32, c_int32, c_int64, c_int32, POINTER(c_int64)]),
+    "enslam_event_cmax_reg_eval": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_double,
+                                                  c_double, c_double, c_double, c_int32, c_void_p, POINTER(c_double), c_double,
+                                                  c_int32, c_int32, POINTER(c_double), c_void_p, c_int64, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "enslam_depth_forecast": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double,
                                              POINTER(c_double), c_int32, c_int32, c_double, c_double, c_int32, c_void_p,
                                              c_void_p, c_void_p]),

@@ -1,4 +1,5 @@
-// Event motion compensation by contrast maximisation (enslam_event_cmax_eval and enslam_event_cmax_rigid_eval; enslam_hip.h
+// Event motion compensation by contrast maximisation (enslam_event_cmax_eval, enslam_event_cmax_rigid_eval and
+// enslam_event_cmax_reg_eval; enslam_hip.h
 // holds the models and fixes the order of every float64 operation): the image of warped events of a stream under a candidate motion, the variance of its blur and
 // the gradient of that variance in the motion.  One evaluation is a fixed chain of launches on one stream:
 //
@@ -15,6 +16,14 @@
 //            and writes mu, f or the gradient
 //   centre   one thread per pixel: J - mu, and the first level of SUM((J - mu)^2)
 //   gather   one thread per event: the same warp, the four D values of its corners, its P products into the block tree in LDS
+//   reg      (enslam_event_cmax_reg_eval with a regulariser only) one thread per event, after everything above: the same warp
+//            and the same checks once more, then the event's |divergence| or |deformation| of the header and, with want_grad,
+//            its P derivatives through the block tree in LDS ((1 + P) x 256 doubles, 14 KB for rigid; 2 KB without the
+//            gradient), one row of 1 + P partials per workgroup.  Its own launch and not a part of the gather, because R is
+//            wanted without the gradient too and the gather only runs with it; the pass reads the stream (and the depth at the
+//            checked pixel) and nothing of the image, about 18 bytes per event.
+//   reg_upper  one workgroup: the upper levels of those partials, divided by M = N minus the drop counters, which it reads on
+//            the device (the vote that wrote them is earlier on the same stream: no read-back, no fence)
 // Integer atomics for the image, fixed trees for every float64 sum, no float atomics, no fences: two runs give the same
 // bits, and the numpy route of event_cmax.py, which performs the same operations in the same order, gives them too.
 // The three models share one warp (cm_warp<MODEL>), one vote and one gather; the kernels are templates of the model only so
@@ -31,7 +40,7 @@ namespace {
 constexpr int CM_BLOCK = 256;
 constexpr int CM_KMAX = ENSLAM_CMAX_MAX_KSIZE;
 constexpr int CM_PMAX = 6;
-constexpr int CM_RIGID = 2;                                 // the third model, behind its own entry point only
+constexpr int CM_RIGID = ENSLAM_CMAX_RIGID;                 // the third model: refused by enslam_event_cmax_eval
 constexpr int64_t CM_MAX_EVENTS = 2147483647;
 constexpr int64_t CM_MAX_PIXELS = (int64_t)1 << 28;
 constexpr double CM_TWO32 = 4294967296.0;
@@ -60,6 +69,7 @@ struct CmWarp {
     int x0, y0;
     double a, b, oa, ob, mx, my, s;
     double Bu[P], Bv[P];
+    double dt, u, v, rho;                                   // what the regulariser takes (flow: not set; rotation: rho = 0.0)
 };
 
 constexpr int cm_params(int model) { return model == ENSLAM_CMAX_FLOW ? 2 : model == ENSLAM_CMAX_ROTATION ? 3 : 6; }
@@ -76,6 +86,7 @@ __device__ __forceinline__ int cm_warp(const CmStream& S, int64_t i, CmWarp<cm_p
     const double xd = (double)ex, yd = (double)ey;
     const double dt = tv - S.t_ref;
     double du, dv;
+    Q.dt = dt;
     if constexpr (MODEL == ENSLAM_CMAX_FLOW) {
         Q.Bu[0] = 1.0 / S.fx; Q.Bu[1] = 0.0;
         Q.Bv[0] = 0.0; Q.Bv[1] = 1.0 / S.fy;
@@ -88,10 +99,12 @@ __device__ __forceinline__ int cm_warp(const CmStream& S, int64_t i, CmWarp<cm_p
         Q.Bv[0] = pv; Q.Bv[1] = -uv; Q.Bv[2] = -u;
         du = (uv * S.theta[0] - pu * S.theta[1]) + v * S.theta[2];
         dv = (pv * S.theta[0] - uv * S.theta[1]) - u * S.theta[2];
+        Q.u = u; Q.v = v; Q.rho = 0.0;
         if constexpr (MODEL == CM_RIGID) {
             const float z = S.depth[(int64_t)ey * S.W + ex];            // ex < W, ey < H: checked above
             if (!(std::isfinite(z) && z > 0.0f)) return ENSLAM_CMAX_DROP_DEPTH;
             const double rho = 1.0 / (double)z;
+            Q.rho = rho;
             Q.Bu[3] = -rho; Q.Bu[4] = 0.0; Q.Bu[5] = u * rho;
             Q.Bv[3] = 0.0; Q.Bv[4] = -rho; Q.Bv[5] = v * rho;
             du = du + rho * (u * S.theta[5] - S.theta[3]);
@@ -122,12 +135,14 @@ __device__ __forceinline__ bool cm_corner(const CmStream& S, const CmWarp<P>& Q,
 }
 
 __global__ __launch_bounds__(CM_BLOCK) void cmax_zero_kernel(long long* __restrict__ iwe, int64_t npix, unsigned long long* __restrict__ dropped,
-                                                             int n_dropped, double* __restrict__ stats, int n_stats) {
+                                                             int n_dropped, double* __restrict__ stats, int n_stats,
+                                                             double* __restrict__ reg_stats, int n_reg) {
     const int64_t o = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
     if (o < npix) iwe[o] = 0;
     if (blockIdx.x == 0) {
         if ((int)threadIdx.x < n_dropped) dropped[threadIdx.x] = 0ull;
         if ((int)threadIdx.x < n_stats) stats[threadIdx.x] = 0.0;
+        if ((int)threadIdx.x < n_reg) reg_stats[threadIdx.x] = 0.0;
     }
 }
 
@@ -272,6 +287,70 @@ __global__ __launch_bounds__(CM_BLOCK) void cmax_gather_kernel(CmStream S, const
     if ((int)threadIdx.x < P) partials[(int64_t)blockIdx.x * P + threadIdx.x] = s_red[threadIdx.x * CM_BLOCK];
 }
 
+// The collapse regulariser of the header: per event that reaches CM_OK, r = |d| with d the divergence of the warp's flow or
+// det(dx'/dx) - 1, and with GRAD its P derivatives, through the block tree; one row of COLS = 1 + P (GRAD) or 1 partials per
+// workgroup.  Rotation is the rho = 0 case of rigid (S.theta[3..5] are 0.0 for it); flow has no launch (R = 0 exactly).
+template <int MODEL, bool GRAD>
+__global__ __launch_bounds__(CM_BLOCK) void cmax_reg_kernel(CmStream S, int kind, double* __restrict__ partials) {
+    constexpr int P = cm_params(MODEL), COLS = GRAD ? 1 + P : 1;
+    __shared__ double s_red[COLS * CM_BLOCK];
+    const int64_t i = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
+    double out[COLS] = {};
+    if (i < S.N) {
+        CmWarp<P> Q;
+        if (cm_warp<MODEL>(S, i, Q) == CM_OK) {
+            const double u = Q.u, v = Q.v, rho = Q.rho, dt = Q.dt;
+            const double c11 = (v * S.theta[0] - (2.0 * u) * S.theta[1]) + rho * S.theta[5];
+            const double c22 = ((2.0 * v) * S.theta[0] - u * S.theta[1]) + rho * S.theta[5];
+            const double c12 = u * S.theta[0] + S.theta[2];
+            const double c21 = -(v * S.theta[1]) - S.theta[2];
+            const double dt2 = dt * dt;
+            const bool deform = kind == ENSLAM_CMAX_REG_DEFORMATION;
+            double d = -(dt * (c11 + c22));
+            if (deform) d = d + dt2 * (c11 * c22 - c12 * c21);
+            out[0] = fabs(d);
+            if constexpr (GRAD) {
+                const double sg = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
+                const double e11[6] = {v, -(2.0 * u), 0.0, 0.0, 0.0, rho}, e22[6] = {2.0 * v, -u, 0.0, 0.0, 0.0, rho};
+                const double e12[6] = {u, 0.0, 1.0, 0.0, 0.0, 0.0}, e21[6] = {0.0, -v, -1.0, 0.0, 0.0, 0.0};
+                for (int k = 0; k < P; ++k) {
+                    double dd = -(dt * (e11[k] + e22[k]));
+                    if (deform) dd = dd + dt2 * ((e11[k] * c22 + c11 * e22[k]) - (e12[k] * c21 + c12 * e21[k]));
+                    out[1 + k] = sg * dd;
+                }
+            }
+        }
+    }
+    for (int c = 0; c < COLS; ++c) s_red[c * CM_BLOCK + threadIdx.x] = out[c];
+    __syncthreads();
+    for (int s = CM_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int c = 0; c < COLS; ++c) s_red[c * CM_BLOCK + threadIdx.x] += s_red[c * CM_BLOCK + threadIdx.x + s];
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < COLS) partials[(int64_t)blockIdx.x * COLS + threadIdx.x] = s_red[threadIdx.x * CM_BLOCK];
+}
+
+// cmax_upper_kernel for the regulariser: column 0 of the n rows is R's, the others dR's; the divisor M = N - the drop counters
+// is taken from the device (the vote kernel is complete: it precedes this launch on the stream).  out = (R, M, dR...): the
+// columns a call without the gradient does not have keep the zero kernel's 0.0, and M = 0 gives 0.0 throughout.
+__global__ __launch_bounds__(CM_BLOCK) void cmax_reg_upper_kernel(const double* __restrict__ partials, int64_t n, int cols, int64_t N,
+                                                                  const unsigned long long* __restrict__ dropped, int n_dropped,
+                                                                  double* __restrict__ out) {
+    __shared__ double s_red[CM_BLOCK];
+    unsigned long long M = (unsigned long long)N;
+    for (int j = 0; j < n_dropped; ++j) M -= dropped[j];
+    for (int c = 0; c < cols; ++c) {
+        double acc = 0.0;
+        for (int64_t base = 0; base < n; base += CM_BLOCK) {
+            const int64_t i = base + threadIdx.x;
+            acc += cm_block_sum(s_red, i < n ? partials[i * cols + c] : 0.0);
+        }
+        if (threadIdx.x == 0) out[c == 0 ? 0 : 1 + c] = M ? acc / (double)M : 0.0;
+    }
+    if (threadIdx.x == 0) out[1] = (double)M;
+}
+
 int64_t cm_blocks(int64_t n) { return (n + CM_BLOCK - 1) / CM_BLOCK; }
 
 int cm_sizes(int32_t H, int32_t W, int64_t N) {
@@ -280,9 +359,10 @@ int cm_sizes(int32_t H, int32_t W, int64_t N) {
     return ENSLAM_OK;
 }
 
-// three float64 images (J or D, the row pass, J - mu) and the partials of the widest first level
-int64_t cm_workspace_bytes(int32_t H, int32_t W, int64_t N, int32_t P) {
-    const int64_t npix = (int64_t)H * W, a = cm_blocks(npix), b = cm_blocks(N) * P;
+// three float64 images (J or D, the row pass, J - mu) and the partials of the widest first level: `cols` per workgroup of
+// events, P for the gather and 1 + P for the regulariser's pass
+int64_t cm_workspace_bytes(int32_t H, int32_t W, int64_t N, int32_t cols) {
+    const int64_t npix = (int64_t)H * W, a = cm_blocks(npix), b = cm_blocks(N) * cols;
     return (3 * npix + (a > b ? a : b)) * (int64_t)sizeof(double);
 }
 
@@ -303,16 +383,35 @@ void cm_gather(int model, const CmStream& S, unsigned blocks, const double* D, d
     else cmax_gather_kernel<CM_RIGID><<<blocks, CM_BLOCK, 0, st>>>(S, D, partials);
 }
 
-// The one validating body of both *_eval entries.  rigid: the model is CM_RIGID whatever `model` says, depth is its image and
-// dropped has four counters; otherwise model is the caller's ENSLAM_CMAX_FLOW or ENSLAM_CMAX_ROTATION and depth is not looked at.
-int cm_eval(bool rigid, const double* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t N, int32_t H, int32_t W,
+void cm_reg(int model, bool grad, const CmStream& S, unsigned blocks, int kind, double* partials, hipStream_t st) {
+    if (model == ENSLAM_CMAX_ROTATION) {
+        if (grad) cmax_reg_kernel<ENSLAM_CMAX_ROTATION, true><<<blocks, CM_BLOCK, 0, st>>>(S, kind, partials);
+        else cmax_reg_kernel<ENSLAM_CMAX_ROTATION, false><<<blocks, CM_BLOCK, 0, st>>>(S, kind, partials);
+    } else {
+        if (grad) cmax_reg_kernel<CM_RIGID, true><<<blocks, CM_BLOCK, 0, st>>>(S, kind, partials);
+        else cmax_reg_kernel<CM_RIGID, false><<<blocks, CM_BLOCK, 0, st>>>(S, kind, partials);
+    }
+}
+
+enum CmEntry { CM_ENTRY_PAIR, CM_ENTRY_RIGID, CM_ENTRY_REG };
+
+// The one validating body of the three *_eval entries.  CM_ENTRY_PAIR: model is the caller's ENSLAM_CMAX_FLOW or
+// ENSLAM_CMAX_ROTATION and depth is not looked at.  CM_ENTRY_RIGID: the model is CM_RIGID whatever `model` says, depth is its
+// image and dropped has four counters.  CM_ENTRY_REG: any of the three models, depth NULL unless rigid, and reg_kind /
+// reg_stats, which the other two pass as ENSLAM_CMAX_REG_NONE / nullptr.
+int cm_eval(CmEntry entry, int32_t reg_kind, double* reg_stats, const double* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t N, int32_t H, int32_t W,
             double fx, double fy, double cx, double cy, int32_t model, const float* depth, const double* theta_host, double t_ref,
             int32_t sign_votes, int32_t k, const double* taps_host, void* workspace, int64_t workspace_bytes, int64_t* iwe,
             double* blurred, double* stats, uint64_t* dropped, int32_t want_grad, void* stream) {
-    if (!theta_host || !taps_host || !workspace || !iwe || !stats || !dropped) return ENSLAM_EINVAL;
+    const bool reg = entry == CM_ENTRY_REG;
+    if (!theta_host || !taps_host || !workspace || !iwe || !stats || !dropped || (reg && !reg_stats)) return ENSLAM_EINVAL;
+    if (entry == CM_ENTRY_RIGID) model = CM_RIGID;
+    else if (model != ENSLAM_CMAX_FLOW && model != ENSLAM_CMAX_ROTATION && !(reg && model == CM_RIGID)) return ENSLAM_EINVAL;
+    const bool rigid = model == CM_RIGID;
     if (N > 0 && (!t || !x || !y || !p || (rigid && !depth))) return ENSLAM_EINVAL;
-    if (rigid) model = CM_RIGID;
-    else if (model != ENSLAM_CMAX_FLOW && model != ENSLAM_CMAX_ROTATION) return ENSLAM_EINVAL;
+    if (reg && ((!rigid && depth) || (reg_kind != ENSLAM_CMAX_REG_NONE && reg_kind != ENSLAM_CMAX_REG_DIVERGENCE &&
+                                      reg_kind != ENSLAM_CMAX_REG_DEFORMATION)))
+        return ENSLAM_EINVAL;
     if (k <= 0 || k % 2 == 0) return ENSLAM_EINVAL;
     int rc = cm_sizes(H, W, N);
     if (rc == ENSLAM_EINVAL) return rc;
@@ -325,8 +424,10 @@ int cm_eval(bool rigid, const double* t, const uint16_t* x, const uint16_t* y, c
     if (k > CM_KMAX) return ENSLAM_EUNSUPPORTED;
     for (int i = 0; i < k; ++i)
         if (!cm_finite(taps_host[i])) return ENSLAM_EINVAL;
-    if (workspace_bytes < cm_workspace_bytes(H, W, N, P) || ((uintptr_t)workspace & 7u)) return ENSLAM_EINVAL;
-    if (((uintptr_t)iwe & 7u) || ((uintptr_t)blurred & 7u) || ((uintptr_t)stats & 7u) || ((uintptr_t)dropped & 7u)) return ENSLAM_EINVAL;
+    if (workspace_bytes < cm_workspace_bytes(H, W, N, reg ? 1 + P : P) || ((uintptr_t)workspace & 7u)) return ENSLAM_EINVAL;
+    if (((uintptr_t)iwe & 7u) || ((uintptr_t)blurred & 7u) || ((uintptr_t)stats & 7u) || ((uintptr_t)dropped & 7u) ||
+        ((uintptr_t)reg_stats & 7u))
+        return ENSLAM_EINVAL;
 
     const int64_t npix = (int64_t)H * W, pix_blocks = cm_blocks(npix), ev_blocks = cm_blocks(N);
     double* bufA = (double*)workspace;                      // J when the caller wants none, then D
@@ -345,7 +446,8 @@ int cm_eval(bool rigid, const double* t, const uint16_t* x, const uint16_t* y, c
     for (int i = 0; i < CM_KMAX; ++i) B.taps[i] = i < k ? taps_host[i] : 0.0;
 
     cmax_zero_kernel<<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(reinterpret_cast<long long*>(iwe), npix,
-                                                                 reinterpret_cast<unsigned long long*>(dropped), rigid ? 4 : 3, stats, 2 + P);
+                                                                 reinterpret_cast<unsigned long long*>(dropped), rigid ? 4 : 3, stats, 2 + P,
+                                                                 reg_stats, reg ? 2 + P : 0);
     if (N > 0) cm_vote(model, S, (unsigned)ev_blocks, iwe, dropped, st);
     cmax_rows_kernel<long long><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, reinterpret_cast<const long long*>(iwe), bufR);
     cmax_cols_kernel<true><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, bufR, J, partials);
@@ -357,6 +459,14 @@ int cm_eval(bool rigid, const double* t, const uint16_t* x, const uint16_t* y, c
         cmax_cols_kernel<false><<<(unsigned)pix_blocks, CM_BLOCK, 0, st>>>(B, bufR, bufA, nullptr);
         if (N > 0) cm_gather(model, S, (unsigned)ev_blocks, bufA, partials, st);
         cmax_upper_kernel<<<1, CM_BLOCK, 0, st>>>(partials, ev_blocks, P, 2.0 / (double)npix, 1, stats + 2);
+    }
+    if (reg && reg_kind != ENSLAM_CMAX_REG_NONE) {
+        // after the last reader of `partials`; flow launches no pass: no partials, R = 0.0 exactly, M still reported
+        const bool pass = N > 0 && model != ENSLAM_CMAX_FLOW;
+        const int cols = want_grad ? 1 + P : 1;
+        if (pass) cm_reg(model, want_grad != 0, S, (unsigned)ev_blocks, reg_kind, partials, st);
+        cmax_reg_upper_kernel<<<1, CM_BLOCK, 0, st>>>(partials, pass ? ev_blocks : 0, cols, N,
+                                                      reinterpret_cast<const unsigned long long*>(dropped), rigid ? 4 : 3, reg_stats);
     }
     return hipGetLastError() == hipSuccess ? ENSLAM_OK : ENSLAM_ELAUNCH;
 }
@@ -385,7 +495,7 @@ int enslam_event_cmax_eval(const double* t, const uint16_t* x, const uint16_t* y
                            double fx, double fy, double cx, double cy, int32_t model, const double* theta_host, double t_ref,
                            int32_t sign_votes, int32_t k, const double* taps_host, void* workspace, int64_t workspace_bytes,
                            int64_t* iwe, double* blurred, double* stats, uint64_t* dropped, int32_t want_grad, void* stream) {
-    return cm_eval(false, t, x, y, p, N, H, W, fx, fy, cx, cy, model, nullptr, theta_host, t_ref, sign_votes, k, taps_host, workspace,
+    return cm_eval(CM_ENTRY_PAIR, ENSLAM_CMAX_REG_NONE, nullptr, t, x, y, p, N, H, W, fx, fy, cx, cy, model, nullptr, theta_host, t_ref, sign_votes, k, taps_host, workspace,
                    workspace_bytes, iwe, blurred, stats, dropped, want_grad, stream);
 }
 
@@ -394,8 +504,25 @@ int enslam_event_cmax_rigid_eval(const double* t, const uint16_t* x, const uint1
                                  double t_ref, int32_t sign_votes, int32_t k, const double* taps_host, void* workspace,
                                  int64_t workspace_bytes, int64_t* iwe, double* blurred, double* stats, uint64_t* dropped,
                                  int32_t want_grad, void* stream) {
-    return cm_eval(true, t, x, y, p, N, H, W, fx, fy, cx, cy, 0, depth, theta_host, t_ref, sign_votes, k, taps_host, workspace,
+    return cm_eval(CM_ENTRY_RIGID, ENSLAM_CMAX_REG_NONE, nullptr, t, x, y, p, N, H, W, fx, fy, cx, cy, 0, depth, theta_host, t_ref, sign_votes, k, taps_host, workspace,
                    workspace_bytes, iwe, blurred, stats, dropped, want_grad, stream);
+}
+
+int enslam_event_cmax_reg_workspace(int32_t H, int32_t W, int64_t N, int32_t model, int64_t* bytes_host) {
+    if (!bytes_host || (model != ENSLAM_CMAX_FLOW && model != ENSLAM_CMAX_ROTATION && model != ENSLAM_CMAX_RIGID)) return ENSLAM_EINVAL;
+    const int rc = cm_sizes(H, W, N);
+    if (rc != ENSLAM_OK) return rc;
+    *bytes_host = cm_workspace_bytes(H, W, N, 1 + cm_params(model));
+    return ENSLAM_OK;
+}
+
+int enslam_event_cmax_reg_eval(const double* t, const uint16_t* x, const uint16_t* y, const uint8_t* p, int64_t N, int32_t H, int32_t W,
+                               double fx, double fy, double cx, double cy, int32_t model, const float* depth, const double* theta_host,
+                               double t_ref, int32_t sign_votes, int32_t k, const double* taps_host, void* workspace,
+                               int64_t workspace_bytes, int64_t* iwe, double* blurred, double* stats, uint64_t* dropped,
+                               int32_t reg_kind, double* reg_stats, int32_t want_grad, void* stream) {
+    return cm_eval(CM_ENTRY_REG, reg_kind, reg_stats, t, x, y, p, N, H, W, fx, fy, cx, cy, model, depth, theta_host, t_ref, sign_votes, k,
+                   taps_host, workspace, workspace_bytes, iwe, blurred, stats, dropped, want_grad, stream);
 }
 
 }  // extern "C"

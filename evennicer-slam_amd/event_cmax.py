@@ -6,12 +6,13 @@ velocity components of the camera at metric scale ('rigid').
 
     warp_image       the IWE (float64) of a stream under a motion, and its blur
     contrast         (f, grad): the variance of the blurred IWE and its gradient in the motion
-    estimate_motion  maximises f from theta0: BFGS on the 2, 3 or 6 parameters on the host, float64, deterministic
+    regulariser      (R, dR, M): the event-collapse regulariser of a motion, the mean absolute divergence or deformation of its warp
+    estimate_motion  maximises f (or f - lambda R) from theta0: BFGS on the 2, 3 or 6 parameters on the host, float64, deterministic
     relative_rotation  the 4 x 4 camera-to-camera delta of an angular velocity over dt, in the project's camera convention
     relative_motion  the same for a six-vector (w, v) of 'rigid': the exact SE(3) exponential; camera_velocity is its inverse
     cmax_numpy       the CPU route: the operations and the sum order of include/enslam_hip.h in numpy
 
-include/enslam_hip.h (enslam_event_cmax_eval, enslam_event_cmax_rigid_eval) fixes the model and the order of every float64 operation; a stream on a HIP
+include/enslam_hip.h (enslam_event_cmax_eval, enslam_event_cmax_rigid_eval, enslam_event_cmax_reg_eval) fixes the model and the order of every float64 operation; a stream on a HIP
 device runs csrc/event_cmax.hip, one on the CPU runs cmax_numpy, and the two return the same bits.
 
 Motion models ('flow': theta = image flow in pixels / s; 'rotation': theta = angular velocity in rad / s; 'rigid': theta =
@@ -30,6 +31,7 @@ MODELS = {'flow': 2, 'rotation': 3, 'rigid': 6}
 MAX_KSIZE = 31
 DROPPED = ('time', 'sensor', 'warp')
 DROPPED_RIGID = DROPPED + ('depth',)            # 'rigid' alone has the fourth counter
+REGS = ('divergence', 'deformation')            # the collapse regularisers of enslam_event_cmax_reg_eval
 _TWO32 = 4294967296.0
 
 
@@ -122,12 +124,19 @@ def _host_depth(depth, model, H, W):
     return depth
 
 
-def cmax_numpy(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False, want_grad=True, depth=None):
+def _check_reg(reg):
+    if reg is not None and reg not in REGS:
+        raise EnslamError(f"event_cmax: reg must be None or one of {list(REGS)} (got {reg!r})")
+
+
+def cmax_numpy(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False, want_grad=True, depth=None, reg=None):
     """The CPU route of enslam_event_cmax_eval and enslam_event_cmax_rigid_eval on numpy arrays: (iwe int64 [H,W], blurred
     float64 [H,W], stats float64 [2 + P], dropped int64 [3], or [4] = (time, sensor, warp, depth) for 'rigid') with every
-    operation and every sum in the header's order."""
+    operation and every sum in the header's order.  reg 'divergence' or 'deformation': the route of enslam_event_cmax_reg_eval,
+    the same four and a fifth, reg_stats float64 [2 + P] = (R, M, dR...)."""
     if model not in MODELS:
         raise EnslamError(f"event_cmax: model must be one of {sorted(MODELS)} (got {model!r})")
+    _check_reg(reg)
     P = MODELS[model]
     fx, fy, cx, cy = (np.float64(v) for v in calib_tuple(calib))
     th = [np.float64(v) for v in theta]
@@ -216,20 +225,50 @@ def cmax_numpy(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False,
                 stats[2 + k] = scale * np.float64(tree_sum(g))
     dropped = np.array([int(timed.sum()), int(sensor.sum()), int(warp.sum())] + ([int(deep.sum())] if model == 'rigid' else []),
                        dtype=np.int64)
-    return iwe, J, stats, dropped
+    if reg is None:
+        return iwe, J, stats, dropped
+    reg_stats = np.zeros(2 + P, dtype=np.float64)
+    M = N - int(dropped.sum())
+    reg_stats[1] = np.float64(M)
+    if model != 'flow' and M > 0:
+        with np.errstate(all='ignore'):
+            rho_, vz = (rho, th[5]) if model == 'rigid' else (zero, np.float64(0.0))      # 'rotation': the rho = 0 case
+            one = zero + 1.0
+            c11 = (v * th[0] - (2.0 * u) * th[1]) + rho_ * vz
+            c22 = ((2.0 * v) * th[0] - u * th[1]) + rho_ * vz
+            c12 = u * th[0] + th[2]
+            c21 = -(v * th[1]) - th[2]
+            e11, e22 = [v, -(2.0 * u), zero, zero, zero, rho_], [2.0 * v, -u, zero, zero, zero, rho_]
+            e12, e21 = [u, zero, one, zero, zero, zero], [zero, -v, -one, zero, zero, zero]
+            dt2, deform = dt * dt, reg == 'deformation'
+            d = -(dt * (c11 + c22))
+            if deform:
+                d = d + dt2 * (c11 * c22 - c12 * c21)
+            Mf = np.float64(M)
+            reg_stats[0] = np.float64(tree_sum(np.where(ok, np.abs(d), 0.0))) / Mf
+            if want_grad:
+                sg = np.where(d > 0.0, 1.0, np.where(d < 0.0, -1.0, 0.0))
+                for k in range(P):
+                    dd = -(dt * (e11[k] + e22[k]))
+                    if deform:
+                        dd = dd + dt2 * ((e11[k] * c22 + c11 * e22[k]) - (e12[k] * c21 + c12 * e21[k]))
+                    reg_stats[2 + k] = np.float64(tree_sum(np.where(ok, sg * dd, 0.0))) / Mf
+    return iwe, J, stats, dropped, reg_stats
 
 
-def _evaluate(stream, H, W, calib, model, theta, t_ref, taps, signed, want_grad, want_blurred=False, depth=None):
-    """(iwe, blurred or None, stats, dropped) as CPU tensors / numpy, from the route of the stream's device"""
+def _evaluate(stream, H, W, calib, model, theta, t_ref, taps, signed, want_grad, want_blurred=False, depth=None, reg=None):
+    """(iwe, blurred or None, stats, dropped) as CPU tensors / numpy, from the route of the stream's device; with reg also
+    reg_stats (numpy)"""
     cal = calib_tuple(calib)
+    more = {} if reg is None else dict(reg=reg)
     if stream.device.type == 'cuda':
         from . import functional as EF
-        iwe, J, stats, dropped = EF.event_cmax_eval(*stream.arrays(), H, W, cal, model, theta, t_ref, taps, signed=signed,
-                                                    want_grad=want_grad, want_blurred=want_blurred, depth=depth)
-        return iwe, J, stats.cpu().numpy(), dropped.cpu().numpy()
-    iwe, J, stats, dropped = cmax_numpy(*stream.numpy(), H, W, cal, model, theta, t_ref, taps, signed=signed, want_grad=want_grad,
-                                        depth=depth)
-    return torch.from_numpy(iwe), torch.from_numpy(J), stats, dropped
+        iwe, J, stats, dropped, *rs = EF.event_cmax_eval(*stream.arrays(), H, W, cal, model, theta, t_ref, taps, signed=signed,
+                                                         want_grad=want_grad, want_blurred=want_blurred, depth=depth, **more)
+        return (iwe, J, stats.cpu().numpy(), dropped.cpu().numpy()) + tuple(r.cpu().numpy() for r in rs)
+    iwe, J, stats, dropped, *rs = cmax_numpy(*stream.numpy(), H, W, cal, model, theta, t_ref, taps, signed=signed, want_grad=want_grad,
+                                             depth=depth, **more)
+    return (torch.from_numpy(iwe), torch.from_numpy(J), stats, dropped) + tuple(rs)
 
 
 def default_t_ref(stream):
@@ -252,11 +291,35 @@ def warp_image(stream, calib, model, theta, H, W, t_ref=None, sigma=1.5, ksize=N
     return (img, J, dict(zip(names, (int(v) for v in dropped)))) if with_dropped else (img, J)
 
 
-def contrast(stream, calib, model, theta, H, W, t_ref=None, sigma=1.5, ksize=None, signed=False, depth=None):
-    """(f, grad): the variance of the blurred IWE and its gradient in theta (numpy float64 [P])"""
+def contrast(stream, calib, model, theta, H, W, t_ref=None, sigma=1.5, ksize=None, signed=False, depth=None, reg=None, reg_weight=0.0):
+    """(f, grad): the variance of the blurred IWE and its gradient in theta (numpy float64 [P]).  With reg ('divergence' or
+    'deformation'): (F, grad F) of F = f - reg_weight R, reg_weight an ABSOLUTE weight (estimate_motion's is relative)."""
+    _check_reg(reg)
     t_ref = default_t_ref(stream) if t_ref is None else float(t_ref)
-    stats = _evaluate(stream, int(H), int(W), calib, model, theta, t_ref, blur_taps(sigma, ksize), signed, True, depth=depth)[2]
-    return float(stats[1]), stats[2:].copy()
+    if reg is None:
+        stats = _evaluate(stream, int(H), int(W), calib, model, theta, t_ref, blur_taps(sigma, ksize), signed, True, depth=depth)[2]
+        return float(stats[1]), stats[2:].copy()
+    lam = _finite_weight(reg_weight)
+    out = _evaluate(stream, int(H), int(W), calib, model, theta, t_ref, blur_taps(sigma, ksize), signed, True, depth=depth, reg=reg)
+    return float(out[2][1]) - lam * float(out[4][0]), out[2][2:] - lam * out[4][2:]
+
+
+def _finite_weight(w):
+    w = float(w)
+    if not math.isfinite(w):
+        raise EnslamError(f"event_cmax: reg_weight must be finite (got {w})")
+    return w
+
+
+def regulariser(stream, calib, model, theta, H, W, t_ref=None, kind='divergence', depth=None):
+    """(R, dR, M): the collapse regulariser of enslam_event_cmax_reg_eval at theta -- the mean over the M events that vote of
+    the absolute divergence of the warp's flow ('divergence') or of |det(dx'/dx) - 1| ('deformation') -- and its gradient in
+    theta (numpy float64 [P]).  An event's depth is held locally constant.  'flow' has R = 0 exactly."""
+    if kind not in REGS:
+        raise EnslamError(f"event_cmax: kind must be one of {list(REGS)} (got {kind!r})")
+    t_ref = default_t_ref(stream) if t_ref is None else float(t_ref)
+    rs = _evaluate(stream, int(H), int(W), calib, model, theta, t_ref, [1.0], False, True, depth=depth, reg=kind)[4]
+    return float(rs[0]), rs[2:].copy(), int(rs[1])
 
 
 def _largest_rho(depth):
@@ -268,7 +331,7 @@ def _largest_rho(depth):
 
 
 def estimate_motion(stream, calib, model, H, W, theta0=None, t_ref=None, sigma=1.5, ksize=None, signed=False, iters=40,
-                    tol_px=1e-3, max_halvings=20, depth=None):
+                    tol_px=1e-3, max_halvings=20, depth=None, reg=None, reg_weight=8.0):
     """Maximises the contrast over theta from theta0 (zeros): BFGS on the host in float64 with a backtracking line search
     whose every accepted step raises f (sufficient increase 1e-4 of the predicted one).  The first step, and every step after
     a reset of the curvature estimate, moves the fastest event of the window by one pixel.  Stops after `iters` accepted steps,
@@ -276,9 +339,17 @@ def estimate_motion(stream, calib, model, H, W, theta0=None, t_ref=None, sigma=1
     Deterministic: the same (f, grad) give the same steps, so the device and the CPU route follow the same trace to the bit.
     depth: the image of 'rigid' (float32 [H, W] on the stream's device).
     Returns dict(theta=[P], trace=[f after every accepted step, trace[0] = f(theta0)], thetas=[theta after every accepted step],
-    evals=the number of evaluations, t_ref=...)."""
+    evals=the number of evaluations, t_ref=...).
+    reg ('divergence' or 'deformation'): maximises F = f - lambda R instead, R the collapse regulariser (`regulariser`), with
+    lambda = reg_weight f(theta0) fixed at the first evaluation (reg_weight itself where f(theta0) == 0), so that the weight
+    does not scale with the number of events.  `trace` then holds F, and the result also has f_trace, reg_trace (f and R beside
+    every entry of trace) and reg_weight_abs = lambda; the step rules are the same.  R is an L1 term with a kink where an
+    event's divergence changes sign -- at theta = 0 for every event at once: a weight so large that no step from theta0 raises
+    F returns theta0 (the dead zone; about 16 on the 45 x 61 planted streams of the tests, where 4 - 8 recovers the motion)."""
     if model not in MODELS:
         raise EnslamError(f"event_cmax: model must be one of {sorted(MODELS)} (got {model!r})")
+    _check_reg(reg)
+    rel_weight = _finite_weight(reg_weight) if reg is not None else 0.0
     P = MODELS[model]
     fx, fy, cx, cy = calib_tuple(calib)
     H, W = int(H), int(W)
@@ -302,14 +373,23 @@ def estimate_motion(stream, calib, model, H, W, theta0=None, t_ref=None, sigma=1
             rho = _largest_rho(depth)
             px_per = np.concatenate([px_per, half * rho * np.array([abs(fx), abs(fy), abs(fx) * um + abs(fy) * vm])])
     evals = [0]
+    lam, parts = [None], {}                                 # lambda; (f, R) of the last evaluation
 
     def fg(th):
         evals[0] += 1
-        st = _evaluate(stream, H, W, (fx, fy, cx, cy), model, th.tolist(), t_ref, taps, signed, True, depth=depth)[2]
-        return float(st[1]), st[2:].astype(np.float64)
+        if reg is None:
+            st = _evaluate(stream, H, W, (fx, fy, cx, cy), model, th.tolist(), t_ref, taps, signed, True, depth=depth)[2]
+            return float(st[1]), st[2:].astype(np.float64)
+        out = _evaluate(stream, H, W, (fx, fy, cx, cy), model, th.tolist(), t_ref, taps, signed, True, depth=depth, reg=reg)
+        st, rs = out[2], out[4]
+        if lam[0] is None:
+            lam[0] = rel_weight * float(st[1]) if float(st[1]) != 0.0 else rel_weight
+        parts['last'] = (float(st[1]), float(rs[0]))
+        return float(st[1]) - lam[0] * float(rs[0]), st[2:].astype(np.float64) - lam[0] * rs[2:].astype(np.float64)
 
     f, g = fg(theta)
     trace, thetas = [f], [theta.tolist()]
+    f_trace, reg_trace = ([parts['last'][0]], [parts['last'][1]]) if reg is not None else (None, None)
     Hinv = None
     for _ in range(int(iters)):
         if not np.all(np.isfinite(g)) or not np.any(g != 0.0):
@@ -330,6 +410,7 @@ def estimate_motion(stream, calib, model, H, W, theta0=None, t_ref=None, sigma=1
             fc, gc = fg(cand)
             if math.isfinite(fc) and fc > f and fc >= f + 1e-4 * alpha * slope:
                 accepted = (cand, fc, gc)
+                kept = parts.get('last')
                 break
             alpha *= 0.5
         if accepted is None:
@@ -352,9 +433,15 @@ def estimate_motion(stream, calib, model, H, W, theta0=None, t_ref=None, sigma=1
         theta, f, g = cand, fc, gc
         trace.append(f)
         thetas.append(theta.tolist())
+        if reg is not None:
+            f_trace.append(kept[0])
+            reg_trace.append(kept[1])
         if moved < tol_px:
             break
-    return dict(theta=theta.tolist(), trace=trace, thetas=thetas, evals=evals[0], t_ref=t_ref)
+    res = dict(theta=theta.tolist(), trace=trace, thetas=thetas, evals=evals[0], t_ref=t_ref)
+    if reg is not None:
+        res.update(f_trace=f_trace, reg_trace=reg_trace, reg_weight_abs=lam[0])
+    return res
 
 
 def relative_rotation(omega, dt):

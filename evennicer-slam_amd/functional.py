@@ -3487,17 +3487,22 @@ def event_model_loss(cur, prev, gt, c_neg=0.2, c_pos=0.2, eps=1e-3, kernel_sizes
 EVENT_CMAX_MODELS = {'flow': (0, 2), 'rotation': (1, 3)}            # name -> (ENSLAM_CMAX_*, P)
 EVENT_CMAX_RIGID = 6                                                # 'rigid': its own entry point, P = 6, four drop counters
 EVENT_CMAX_MAX_KSIZE = 31
+EVENT_CMAX_REGS = {'divergence': 1, 'deformation': 2}               # name -> ENSLAM_CMAX_REG_*
 
 
 def event_cmax_eval(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=False, want_grad=True, want_blurred=False,
-                    depth=None):
+                    depth=None, reg=None):
     """enslam_event_cmax_eval (enslam_hip.h) on a stream on one HIP device: t float64 [N], x, y uint16 [N], p uint8 [N].  calib =
     (fx, fy, cx, cy) pinhole, model 'flow' or 'rotation', theta its P host numbers, taps the k float64 taps of the blur (a
     host sequence).  Returns (iwe int64 [H,W], blurred float64 [H,W] or None, stats float64 [2 + P] = (mu, f, df/dtheta...),
     dropped int64 [3] = (time, sensor, warp)) as device tensors; no synchronisation.
     model 'rigid' is enslam_event_cmax_rigid_eval: theta = (w, v), P = 6, depth a contiguous float32 [H,W] tensor on the
-    stream's device (required; refused for the other models), dropped int64 [4] = (time, sensor, warp, depth)."""
+    stream's device (required; refused for the other models), dropped int64 [4] = (time, sensor, warp, depth).
+    reg 'divergence' or 'deformation' is enslam_event_cmax_reg_eval for any of the three models: the same four tensors, bit for
+    bit, and a fifth, reg_stats float64 [2 + P] = (R, M, dR/dtheta...), the collapse regulariser of the header."""
     what = "event_cmax_eval"
+    if reg is not None and reg not in EVENT_CMAX_REGS:
+        raise L.EnslamError(f"{what}: reg must be None or one of {sorted(EVENT_CMAX_REGS)} (got {reg!r})")
     _event_arrays(what, t, x, y, p)
     H, W = _event_sensor(what, H, W)
     rigid = model == 'rigid'
@@ -3522,7 +3527,10 @@ def event_cmax_eval(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=F
     N, dev = int(t.shape[0]), t.device
     lib = L.lib()
     nbytes = ctypes.c_int64(0)
-    if rigid:
+    if reg is not None:
+        code = 2 if rigid else code
+        L.check(lib.enslam_event_cmax_reg_workspace(H, W, N, code, ctypes.byref(nbytes)), "enslam_event_cmax_reg_workspace")
+    elif rigid:
         L.check(lib.enslam_event_cmax_rigid_workspace(H, W, N, ctypes.byref(nbytes)), "enslam_event_cmax_rigid_workspace")
     else:
         L.check(lib.enslam_event_cmax_workspace(H, W, N, P, ctypes.byref(nbytes)), "enslam_event_cmax_workspace")
@@ -3532,6 +3540,14 @@ def event_cmax_eval(t, x, y, p, H, W, calib, model, theta, t_ref, taps, signed=F
         blurred = torch.empty((H, W), dtype=torch.float64, device=dev) if want_blurred else None
         stats = torch.empty(2 + P, dtype=torch.float64, device=dev)
         dropped = torch.empty(4 if rigid else 3, dtype=torch.int64, device=dev)
+        if reg is not None:
+            reg_stats = torch.empty(2 + P, dtype=torch.float64, device=dev)
+            L.check(lib.enslam_event_cmax_reg_eval(_ptr(t), _ptr(x), _ptr(y), _ptr(p), N, H, W, cal[0], cal[1], cal[2], cal[3], code,
+                                                   _ptr(depth) if rigid else None, (ctypes.c_double * P)(*th), float(t_ref),
+                                                   1 if signed else 0, k, (ctypes.c_double * k)(*tp), _ptr(ws), ws.numel() * 8,
+                                                   _ptr(iwe), _ptr(blurred), _ptr(stats), _ptr(dropped), EVENT_CMAX_REGS[reg],
+                                                   _ptr(reg_stats), 1 if want_grad else 0, _stream()), "enslam_event_cmax_reg_eval")
+            return iwe, blurred, stats, dropped, reg_stats
         if rigid:
             L.check(lib.enslam_event_cmax_rigid_eval(_ptr(t), _ptr(x), _ptr(y), _ptr(p), N, H, W, cal[0], cal[1], cal[2], cal[3],
                                                      _ptr(depth), (ctypes.c_double * P)(*th), float(t_ref), 1 if signed else 0, k,

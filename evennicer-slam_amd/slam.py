@@ -42,6 +42,9 @@ sensor; `tracking.cmax_min_events` (500) and `tracking.cmax_iters` (10 accepted 
 the constant-speed pose, counted in `motion_prior_stats`, with too few events, without a depth image yet, with a result that
 is not finite and with a contrast that did not rise above f(theta0).  Measured on the analytic room the prior does not
 help -- the six-parameter contrast rises without bound along v_z and the estimate follows it -- so the default stays 'const_speed'.
+`tracking.cmax_reg` ('none'; 'divergence' or 'deformation') with `tracking.cmax_reg_weight` (8) subtracts the collapse regulariser
+of event_cmax.py from that contrast, and `tracking.cmax_max_reg` (unset) adds a fallback, 'collapsed', for an estimate whose
+regulariser exceeds it.  Measured the same way, the regularised prior no longer loses the trajectory and still does not help.
 
 Mesh extraction is opt-in: `SLAM.get_mesh` (or `run(mesh_file=...)`) runs `mesher.Mesher.get_mesh` on the run's keyframes and
 poses.  The per-iteration figures of the reference's Visualizer are opt-in too: `SLAM(vis=True)` builds one
@@ -69,6 +72,7 @@ MAP_KEYS = ('grid_middle', 'grid_fine', 'grid_color')
 SCHEDULES = ('dense', 'reference')
 DEPTH_ON_EVENT_FRAMES = ('measured', 'forecast', 'none')
 MOTION_PRIORS = ('const_speed', 'cmax')
+CMAX_REGS = ('none', 'divergence', 'deformation')
 
 
 class FrameStep(typing.NamedTuple):
@@ -209,6 +213,17 @@ class SLAM:
         self.cmax_min_events, self.cmax_iters = int(tr.get('cmax_min_events', 500)), int(tr.get('cmax_iters', 10))
         # frames whose initial pose came from the events, the fallbacks by cause, and the seconds the prior took
         self.motion_prior_stats = dict(cmax=0, few_events=0, no_depth=0, not_finite=0, no_rise=0, seconds=0.0)
+        # the collapse regulariser of the prior's objective (event_cmax.estimate_motion's reg / reg_weight), and the optional
+        # ceiling on the estimate's R above which the frame falls back (counted under 'collapsed', a key only then)
+        self.cmax_reg = tr.get('cmax_reg', 'none')
+        if self.cmax_reg not in CMAX_REGS:
+            raise ValueError(f"tracking.cmax_reg must be one of {CMAX_REGS} (got {self.cmax_reg!r})")
+        self.cmax_reg_weight = float(tr.get('cmax_reg_weight', 8.0))
+        if not np.isfinite(self.cmax_reg_weight):
+            raise ValueError(f"tracking.cmax_reg_weight must be finite (got {self.cmax_reg_weight})")
+        self.cmax_max_reg = None if tr.get('cmax_max_reg') is None else float(tr['cmax_max_reg'])
+        if self.cmax_max_reg is not None:
+            self.motion_prior_stats['collapsed'] = 0
         if self.motion_prior == 'cmax':
             if getattr(dataset, '_stream', None) is None:
                 raise ValueError("tracking.motion_prior = 'cmax' needs the time-stamped events of data.event_stream and "
@@ -305,7 +320,10 @@ class SLAM:
         the depth image of the last frame with RGB-D warped into the previous pose at the sensor's full size.  `fallback`, the
         constant-speed pose, is returned -- and the cause counted in motion_prior_stats -- when the interval has fewer than
         tracking.cmax_min_events events, when no depth image has been kept yet, when the result is not finite and when the
-        contrast did not rise above f(theta0)."""
+        contrast did not rise above f(theta0).  tracking.cmax_reg ('divergence' or 'deformation') maximises the contrast less
+        tracking.cmax_reg_weight (8) times the collapse regulariser instead; the rise is still asked of the pure contrast.
+        tracking.cmax_max_reg, when set, also sends an estimate whose regulariser (the mean absolute divergence or
+        deformation of its warp) exceeds it back to the constant-speed pose, counted under 'collapsed'."""
         from . import event_cmax as CM
         stats, t_start = self.motion_prior_stats, time.perf_counter()
 
@@ -328,13 +346,20 @@ class SLAM:
         M = EF.relative_camera_matrix(self.estimate_c2w_list[src], pre)
         depth = EF.depth_forecast(depth.float().contiguous(), self.cam, M, (self.H, self.W), radius=self.forecast_radius, z_near=0.0,
                                   fill=self.forecast_fill).to(stream.device)
+        reg = {} if self.cmax_reg == 'none' else dict(reg=self.cmax_reg, reg_weight=self.cmax_reg_weight)
         res = CM.estimate_motion(stream, (self.fx, self.fy, self.cx, self.cy), 'rigid', self.H, self.W, theta0=theta0, t_ref=t0,
-                                 iters=self.cmax_iters, depth=depth)
+                                 iters=self.cmax_iters, depth=depth, **reg)
         self.motion_prior_last = res
         if not (np.all(np.isfinite(res['theta'])) and np.isfinite(res['trace'][-1])):
             return back('not_finite')
-        if not res['trace'][-1] > res['trace'][0]:
+        rise = res['f_trace'] if reg else res['trace']                  # the pure contrast, whatever was maximised
+        if not rise[-1] > rise[0]:
             return back('no_rise')
+        if self.cmax_max_reg is not None:
+            R = res['reg_trace'][-1] if reg else CM.regulariser(stream, (self.fx, self.fy, self.cx, self.cy), 'rigid', res['theta'],
+                                                                 self.H, self.W, t_ref=t0, depth=depth)[0]
+            if not R <= self.cmax_max_reg:
+                return back('collapsed')
         est = (pre @ CM.relative_motion(res['theta'], t1 - t0)).float().to(self.device)
         stats['cmax'] += 1
         stats['seconds'] += time.perf_counter() - t_start

@@ -1443,6 +1443,50 @@ int enslam_event_cmax_rigid_eval(const double *t, const uint16_t *x, const uint1
                                  const double *taps_host, void *workspace, int64_t workspace_bytes, int64_t *iwe,
                                  double *blurred, double *stats, uint64_t *dropped, int32_t want_grad, void *stream);
 
+/* Event-collapse regularisers of the same objective (Shiba, Aoki, Gallego: Event Collapse in Contrast Maximization Frameworks,
+ * 2022): with six parameters the contrast has no useful maximum -- v_z contracts the events towards the principal point and the
+ * variance rises without bound.  R, the mean over the events that voted of the absolute DIVERGENCE of the warp's flow or of
+ * the absolute DEFORMATION |det(dx'/dx) - 1| of the warp, is what a caller subtracts from f with a weight (event_cmax.py).
+ * A third entry, because the four above keep their signatures, workspace formulas and refusals; it runs the same validating
+ * body and the same kernels, and iwe, blurred, stats and dropped are bit-equal to theirs for every reg_kind.
+ *
+ * The arguments are enslam_event_cmax_rigid_eval's, plus: model, ENSLAM_CMAX_FLOW, ENSLAM_CMAX_ROTATION or ENSLAM_CMAX_RIGID
+ * (theta_host has the model's P = 2, 3 or 6 numbers, dropped 3 counters, 4 for RIGID; depth must be NULL unless RIGID);
+ * reg_kind, ENSLAM_CMAX_REG_NONE, _DIVERGENCE or _DEFORMATION; reg_stats, float64 [2 + P] = (R, M, dR / dtheta...).
+ * Per event that passes every check above (the same checks: the pass warps the event once more and reads the depth at the
+ * checked pixel only), with that warp's dt, u, v, rho (ROTATION is the rho = 0.0 case of RIGID, with v_z = 0.0 and k < 3) and
+ * theta = (w, v); float64, every operation on its own, in exactly this order:
+ *     c11 = (v * w_x - (2 u) * w_y) + rho * v_z          e11 = ( v, -(2 u),  0, 0, 0, rho)
+ *     c22 = ((2 v) * w_x - u * w_y) + rho * v_z          e22 = (2 v,    -u,  0, 0, 0, rho)
+ *     c12 = u * w_x + w_z                                e12 = ( u,      0,  1, 0, 0, 0)
+ *     c21 = -(v * w_y) - w_z                             e21 = ( 0,     -v, -1, 0, 0, 0)
+ *     d_div = -(dt * (c11 + c22))
+ *     d_def = d_div + (dt * dt) * (c11 * c22 - c12 * c21)
+ *     dd_div[k] = -(dt * (e11[k] + e22[k]))
+ *     dd_def[k] = dd_div[k] + (dt * dt) * ((e11[k] * c22 + c11 * e22[k]) - (e12[k] * c21 + c12 * e21[k]))
+ *     r = |d|,   dr[k] = sgn(d) * dd[k]   with sgn(0) = 0.0;   r = dr[k] = 0.0 for a dropped event
+ *     R = SUM(r) / M,   dR[k] = SUM(dr[k]) / M,   M = N minus the drop counters (the events that voted); M = 0: R = dR = 0.0
+ * c_ij is the Jacobian of the motion field (du, dv) in (u, v), so that dx'/dx = 1 - dt c: d_div is its trace times -dt and
+ * d_def = det(dx'/dx) - 1 (the factors fx / fy and fy / fx of the off-diagonal pair cancel in the product).  The depth of an
+ * event is held LOCALLY CONSTANT: there is no term in the gradient of rho -- a finite difference of a depth image across an
+ * occlusion edge is not a usable number.  FLOW has R = dR = 0.0 exactly (a constant flow has neither) and M as above.
+ * SUM is the tree above over the events in stream order; M is read from the drop counters on the device.  dR is 0.0 without
+ * want_grad; with ENSLAM_CMAX_REG_NONE nothing is added to the launches and reg_stats is all 0.0.  The launches stay one
+ * capturable chain on the stream.  workspace: enslam_event_cmax_reg_workspace bytes, the formula above with 1 + P partials per
+ * workgroup of events in place of P.
+ * The refusals are enslam_event_cmax_rigid_eval's, plus ENSLAM_EINVAL for an unknown model, an unknown reg_kind, a depth that is
+ * not NULL with FLOW or ROTATION, and a NULL or misaligned reg_stats; a NULL depth is refused for RIGID only. */
+#define ENSLAM_CMAX_RIGID 2
+#define ENSLAM_CMAX_REG_NONE 0
+#define ENSLAM_CMAX_REG_DIVERGENCE 1
+#define ENSLAM_CMAX_REG_DEFORMATION 2
+int enslam_event_cmax_reg_workspace(int32_t H, int32_t W, int64_t N, int32_t model, int64_t *bytes_host);
+int enslam_event_cmax_reg_eval(const double *t, const uint16_t *x, const uint16_t *y, const uint8_t *p, int64_t N, int32_t H,
+                               int32_t W, double fx, double fy, double cx, double cy, int32_t model, const float *depth,
+                               const double *theta_host, double t_ref, int32_t sign_votes, int32_t k, const double *taps_host,
+                               void *workspace, int64_t workspace_bytes, int64_t *iwe, double *blurred, double *stats,
+                               uint64_t *dropped, int32_t reg_kind, double *reg_stats, int32_t want_grad, void *stream);
+
 /* Depth forecast (csrc/depth_forecast.hip, functional.depth_forecast): a measured depth image forward-warped into another
  * camera pose and image size by a z-buffered point splat -- the guidance depth of the tracker's reduced-resolution render on a
  * frame without an RGB-D image (slam.py, event.depth_on_event_frames: 'forecast').

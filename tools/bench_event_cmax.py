@@ -23,7 +23,13 @@ the warp), `vote_atomic_gbytes_per_s` = 8 bytes x vote_atomics / vote_ms.
 `estimate` times a whole event_cmax.estimate_motion from zero on each shape on the device (--estimate-repeat, 3) and once on
 the numpy route for sim_260x346, with the number of evaluations it took.
 
-    python tools/bench_event_cmax.py [--repeat 10] [--estimate-repeat 3] [--no-numpy]"""
+--reg divergence|deformation adds a `<shape>_<order>_rigid_reg` row per shape (the last order of each): the rigid evaluation
+with gradient through enslam_event_cmax_reg_eval with that regulariser against the plain rigid evaluation of the same build,
+the two ALTERNATING in one process, --repeat timed pairs after a warm-up pair; `reg_over_plain` is the ratio of the medians,
+`plain_below_reg` whether the slowest plain run is below the fastest regularised one, `shared_outputs_equal` whether image,
+counters and stats of the two are the same bits.
+
+    python tools/bench_event_cmax.py [--repeat 10] [--estimate-repeat 3] [--no-numpy] [--reg divergence|deformation]"""
 import argparse
 import json
 import os
@@ -93,6 +99,7 @@ def main():
     ap.add_argument('--repeat', type=int, default=10)
     ap.add_argument('--estimate-repeat', type=int, default=3)
     ap.add_argument('--no-numpy', action='store_true')
+    ap.add_argument('--reg', choices=('divergence', 'deformation'), default=None)
     args = ap.parse_args()
     from evennicer_slam_amd import event_cmax as M
     from evennicer_slam_amd import functional as EF
@@ -105,12 +112,12 @@ def main():
     taps = M.blur_taps(SIGMA)
     t_ref = 0.5 * (STAMPS[0] + STAMPS[1])
 
-    def device_ms(stream, H, W, cal, want_grad=True, depth=None):
+    def device_ms(stream, H, W, cal, want_grad=True, depth=None, reg=None):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         model, theta = ('rotation', OMEGA) if depth is None else ('rigid', OMEGA + VELOCITY)
         torch.cuda.synchronize()
         a.record()
-        out = EF.event_cmax_eval(*stream.arrays(), H, W, cal, model, theta, t_ref, taps, want_grad=want_grad, depth=depth)
+        out = EF.event_cmax_eval(*stream.arrays(), H, W, cal, model, theta, t_ref, taps, want_grad=want_grad, depth=depth, reg=reg)
         b.record()
         torch.cuda.synchronize()
         return a.elapsed_time(b), out
@@ -169,8 +176,22 @@ def main():
                            equal_to_numpy=bool(same))
             rows[f'{shape}_{order}_rigid'] = row
             print(f'{shape}_{order}: done', file=sys.stderr, flush=True)
-        # a whole estimate from zero
         stream = streams[names[-1]]
+        if args.reg is not None:
+            plain, regd = [], []
+            for r in range(args.repeat + 1):
+                ms_p, out_p = device_ms(stream, H, W, cal, depth=depth)
+                ms_g, out_g = device_ms(stream, H, W, cal, depth=depth, reg=args.reg)
+                if r:
+                    plain.append(ms_p)
+                    regd.append(ms_g)
+            same = all(torch.equal(a.view(torch.int64), b.view(torch.int64)) for a, b in zip((out_p[0], out_p[2], out_p[3]), (out_g[0], out_g[2], out_g[3])))
+            rows[f'{shape}_{names[-1]}_rigid_reg'] = dict(
+                events=len(stream), reg=args.reg, plain_ms_med_min_max=span(plain), reg_ms_med_min_max=span(regd),
+                reg_over_plain=float(np.median(regd) / np.median(plain)), plain_below_reg='yes' if max(plain) < min(regd) else 'no',
+                shared_outputs_equal=bool(same), reg_stats=out_g[4].cpu().tolist())
+            print(f'{shape}_{names[-1]}_rigid_reg: done', file=sys.stderr, flush=True)
+        # a whole estimate from zero
         kw = dict(H=H, W=W, t_ref=t_ref, sigma=SIGMA)
         ms, res = [], None
         for r in range(args.estimate_repeat + 1):

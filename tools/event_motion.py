@@ -5,6 +5,7 @@ of warped events sharpest.
     python tools/event_motion.py --stream EVENTS --size H W --calib FX FY CX CY (--stamps FILE | --fps F)
                                  [--model rotation|flow|rigid] [--depth PATH [--depth-scale S]] [--gap 1] [--sigma 1.5] [--ksize K] [--iters 40] [--signed]
                                  [--max-intervals N] [--out DIR [--images]] [--device cuda:0]
+                                 [--reg divergence|deformation [--reg-weight 8] [--t-ref start|middle]]
     python tools/event_motion.py --demo N [--model rigid] [--yaw-deg 8.0] [--step 0.002] [--device cuda:0] [--out DIR [--images]]
 
 EVENTS is a `.npz` of event_stream.EventStream.save or the text layout `t x y p`.  The frame times come from --stamps (first
@@ -23,6 +24,12 @@ prints the estimated angular velocities beside the ones implied by the ground-tr
 camera also translates there, which a pure rotation cannot explain: the comparison is a record, not a bar.  --demo N --model
 rigid estimates all six components under the room's own depth frame at the start of each interval and prints them beside
 event_cmax.camera_velocity of the ground-truth poses.
+
+--reg maximises the contrast less --reg-weight times f(theta0) times the collapse regulariser of that kind
+(event_cmax.estimate_motion's reg / reg_weight: what keeps the six-parameter model from contracting every event onto the
+principal point); each row then also has `contrast_only_before` / `contrast_only_after` and `regulariser_after`, and
+`contrast_*` are the regularised objective.  --t-ref start puts the reference time at the start of each interval (the middle by
+default), where the pose prior of slam.py has it.
 
 --device cpu runs the numpy route of the same model.  Prints one JSON line."""
 import argparse
@@ -67,12 +74,16 @@ def read_depth(path, scale, H, W):
 
 def estimate(stream, a, b, cal, H, W, args, out_dir=None, index=0, depth=None):
     from evennicer_slam_amd import event_cmax as M
-    kw = dict(H=H, W=W, t_ref=0.5 * (a + b), sigma=args.sigma, ksize=args.ksize, signed=args.signed)
+    kw = dict(H=H, W=W, t_ref=a if args.t_ref == 'start' else 0.5 * (a + b), sigma=args.sigma, ksize=args.ksize, signed=args.signed)
     if depth is not None:
         kw['depth'] = depth
-    res = M.estimate_motion(stream, cal, args.model, iters=args.iters, **kw)
+    reg = {} if args.reg is None else dict(reg=args.reg, reg_weight=args.reg_weight)
+    res = M.estimate_motion(stream, cal, args.model, iters=args.iters, **kw, **reg)
     row = dict(t_a=a, t_b=b, events=len(stream), theta=res['theta'], contrast_before=res['trace'][0], contrast_after=res['trace'][-1],
                evaluations=res['evals'], steps=len(res['trace']) - 1)
+    if reg:
+        row.update(contrast_only_before=res['f_trace'][0], contrast_only_after=res['f_trace'][-1], regulariser_after=res['reg_trace'][-1],
+                   reg_weight_abs=res['reg_weight_abs'])
     if out_dir is not None and args.images:
         zero = [0.0] * len(res['theta'])
         write_png(os.path.join(out_dir, f'interval{index:05d}_raw.png'), M.warp_image(stream, cal, args.model, zero, **kw)[0])
@@ -102,6 +113,9 @@ def main(argv=None):
     ap.add_argument('--yaw-deg', type=float, default=8.0)
     ap.add_argument('--step', type=float, default=0.002)
     ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--reg', choices=('divergence', 'deformation'), default=None)
+    ap.add_argument('--reg-weight', type=float, default=8.0)
+    ap.add_argument('--t-ref', choices=('start', 'middle'), default='middle')
     args = ap.parse_args(argv)
     if (args.demo is None) == (args.stream is None):
         ap.error("give either --stream EVENTS or --demo N")
@@ -119,6 +133,8 @@ def main(argv=None):
     if args.out is not None:
         os.makedirs(args.out, exist_ok=True)
     out = dict(model=args.model, device=args.device, sigma=args.sigma)
+    if args.reg is not None:
+        out.update(reg=args.reg, reg_weight=args.reg_weight)
     rows = []
     if args.demo is not None:
         if args.demo < 2:

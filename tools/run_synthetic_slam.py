@@ -19,7 +19,9 @@ tools/simulate_events.py's default --fps); [--schedule dense|reference] [--rgbd-
 measured|forecast|none] set event.schedule, event.rgbd_every_frame and event.depth_on_event_frames (slam.py; the sparse RGB-D
 schedule), [--motion-prior const_speed|cmax] sets tracking.motion_prior ('cmax' needs --events simulate: the sequence is then
 simulated with time stamps, 30 frames per second, and the stream and the stamps are written beside it as data.event_stream and
-data.frame_stamps; the result carries the prior's counters; CMAX_MIN_EVENTS in the environment sets tracking.cmax_min_events) and [--no-events] keeps event.activate_events off with simulated events (the "events off" arm).  SEED (environment, default 0) seeds torch and numpy for each run."""
+data.frame_stamps; the result carries the prior's counters; CMAX_MIN_EVENTS in the environment sets tracking.cmax_min_events;
+[--cmax-reg none|divergence|deformation] [--cmax-reg-weight W] set tracking.cmax_reg and tracking.cmax_reg_weight, the prior's
+collapse regulariser) and [--no-events] keeps event.activate_events off with simulated events (the "events off" arm).  SEED (environment, default 0) seeds torch and numpy for each run."""
 import os, sys, tempfile, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -64,7 +66,7 @@ def parse_args(args):
     for flag, key in (('--events', 'events'), ('--event-net', 'event_net'), ('--net-backend', 'net_backend'), ('--vis', 'vis'),
                       ('--event-predictor', 'event_predictor'), ('--c-pos', 'c_pos'), ('--c-neg', 'c_neg'),
                       ('--schedule', 'schedule'), ('--rgbd-every', 'rgbd_every'), ('--depth-on-event-frames', 'depth_on_event_frames'),
-                      ('--motion-prior', 'motion_prior')):
+                      ('--motion-prior', 'motion_prior'), ('--cmax-reg', 'cmax_reg'), ('--cmax-reg-weight', 'cmax_reg_weight')):
         if flag in args:
             k = args.index(flag)
             opts[key] = args[k + 1]
@@ -81,6 +83,12 @@ def parse_args(args):
         raise SystemExit("--motion-prior takes 'const_speed' or 'cmax'")
     if opts.get('motion_prior') == 'cmax' and opts.get('events') != 'simulate':
         raise SystemExit("--motion-prior cmax needs --events simulate")
+    if opts.get('cmax_reg') not in (None, 'none', 'divergence', 'deformation'):
+        raise SystemExit("--cmax-reg takes 'none', 'divergence' or 'deformation'")
+    if ('cmax_reg' in opts or 'cmax_reg_weight' in opts) and opts.get('motion_prior') != 'cmax':
+        raise SystemExit("--cmax-reg and --cmax-reg-weight need --motion-prior cmax")
+    if 'cmax_reg_weight' in opts:
+        opts['cmax_reg_weight'] = float(opts['cmax_reg_weight'])
     if 'rgbd_every' in opts:
         opts['rgbd_every'] = int(opts['rgbd_every'])
     noise = {}
@@ -141,7 +149,7 @@ def mesh_metrics(slam, path, n_gt=200000, tsdf=False):
 
 def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=None, event_net=None, net_backend=None, vis=None,
         noise=None, event_predictor=None, c_pos=None, c_neg=None, schedule=None, rgbd_every=None, depth_on_event_frames=None,
-        no_events=False, motion_prior=None):
+        no_events=False, motion_prior=None, cmax_reg=None, cmax_reg_weight=None):
     cam = dict(H=60, W=80, fx=70.0, fy=70.0, cx=39.5, cy=29.5)
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
@@ -162,6 +170,10 @@ def run(n=30, verbose=True, mesh_dir=None, overlap=False, tsdf=False, events=Non
             cfg['tracking'] = dict(cfg['tracking'], motion_prior=motion_prior)
             if 'CMAX_MIN_EVENTS' in os.environ:
                 cfg['tracking']['cmax_min_events'] = int(os.environ['CMAX_MIN_EVENTS'])
+            if cmax_reg is not None:
+                cfg['tracking']['cmax_reg'] = cmax_reg
+            if cmax_reg_weight is not None:
+                cfg['tracking']['cmax_reg_weight'] = float(cmax_reg_weight)
         if streams is not None:                             # the stream and the frame times the prior reads
             from evennicer_slam_amd.event_stream import EventStream
             EventStream.concatenate(streams).save(os.path.join(tmp, 'events.npz'))
